@@ -46,6 +46,9 @@ Every native call goes through the C ABI of libvfi_hip.so (ctypes, vfidkr_amd/ca
   cpu_baseline      the CPU oracle (oracle/, a port: kind "port") timed on the host cores on a bounded sample
                     of the same workload (one of the step's six units, every call of it run in full) at 1 thread and at
                     all cores, rank 0 at N=1 only
+  dump_outputs      with --dump-outputs DIR: name -> full shape and elements written of each DIR/<name>.npy (rank 0's
+                    outputs of the last timed step, taken right after the timed region; inputs are seeded, so two builds
+                    can be compared file for file)
 """
 import argparse
 import json
@@ -88,7 +91,12 @@ def parse(argv=None):
     ap.add_argument("--no-graph", action="store_true", help="vimeo64: eager calls instead of one captured HIP graph per step")
     ap.add_argument("--stub-step", type=float, default=None, metavar="SECONDS",
                     help="plumbing test: a step is a sleep of SECONDS, no GPU is touched (tests/test_abi_and_host.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: an array larger than its share is a fixed, seeded sample of its elements)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.streams is None:
         args.streams = 1
     return args
@@ -158,6 +166,34 @@ def hip_timed(torch, dev, fn, iters, nsets=1, warm=3):
     e1.record()
     torch.cuda.synchronize(dev)
     return e0.elapsed_time(e1) / iters
+
+
+DUMP_BYTES = 60 * 2 ** 20      # data; with the .npy headers the files stay below 64 MB
+DUMP_SEED = 1234
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: writes {name: tensor} as directory/<name>.npy in float32, at most DUMP_BYTES in all.  The budget is
+    shared out smallest array first: an array within its share is written whole (its shape kept), a larger one as its
+    share of its elements at distinct flat indices drawn from DUMP_SEED, in index order (1-D; the same indices for the
+    same shape in every run).  Returns {name: {"shape": full shape, "elements": elements written}}."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    left, info = DUMP_BYTES // 4, {}
+    order = sorted(arrays, key=lambda n: (arrays[n].numel(), n))
+    for k, name in enumerate(order):
+        t = arrays[name].detach()
+        share = left // (len(order) - k)
+        if t.numel() <= share:
+            vals = t.float().cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), share, replace=False))
+            vals = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), vals)
+        left -= vals.size
+        info[name] = {"shape": list(t.shape), "elements": int(vals.size)}
+    return info
 
 
 # ------------------------------------------------------------------------------------------- one rank
@@ -265,6 +301,14 @@ def run_vimeo64(args, torch, cabi, runner, S, dev, rank, world):
     frames_total = runner.total_units(len(mine) * args.steps)
     h, w = pairs[0].h, pairs[0].w
     extra = {}
+    if args.dump_outputs and rank == 0:
+        # what the last step leaves in each batch's tensors: both frame warps, and the projection of direction 1 (direction 0
+        # projects into the same count and flow tensors before it).  The correlation volumes are not kept by the step.
+        outs = {}
+        for j, p in enumerate(pairs):
+            outs.update({"b%02d_warp_d0" % j: p.out[0], "b%02d_warp_d1" % j: p.out[1], "b%02d_proj_d1" % j: p.proj,
+                         "b%02d_count_d1" % j: p.count})
+        extra["dump_outputs"] = dump_outputs(args.dump_outputs, outs)
     if args.streams == 1 and not args.no_extras:
         # the same step with its independent batches dealt over four parallel branches of the graph (a schedule change, not
         # kernel work: reported beside the one-branch headline, which stays comparable from round to round)
@@ -303,13 +347,16 @@ def run_slowmo(args, torch, cabi, runner, S, dev, rank, world):
 
     flat_flows, flat_counts, flat_projs = wl.flows[0] + wl.flows[1], wl.counts[0] + wl.counts[1], wl.projs[0] + wl.projs[1]
     flat_depth = [wl.depth[0]] * len(TIMES) + [wl.depth[1]] * len(TIMES)
+    kept = {}                   # keep=True (the last timed step under --dump-outputs): the correlation volumes it returned
 
-    def step(i, record=False):
+    def step(i, record=False, keep=False):
         # the reference's order (networks/DAIN_slowmotion.py:147-171): both flow networks (their correlations), FlowProject
         # of both directions for every time offset, then per time offset FilterInterpolate_ctx and FilterInterpolate
         for d in range(2):
-            for a, b in wl.corr[d]:
-                cabi.correlation_forward(a, b, 4, 1, 4, 1, 1)
+            for lv, (a, b) in enumerate(wl.corr[d]):
+                corr = cabi.correlation_forward(a, b, 4, 1, 4, 1, 1)
+                if keep:
+                    kept["corr_d%d_l%d" % (d, lv)] = corr
         # [FlowProject(cur_offset_outputs[0], depth_inv[0]), FlowProject(cur_offset_outputs[1], depth_inv[1])]
         # (networks/DAIN_slowmotion.py:156-159): the two lists back to back = one library call (fused.FlowProject_directions)
         err = cabi.flowprojection_forward_batch(flat_flows, flat_counts, flat_projs, 1, flat_depth)
@@ -336,12 +383,14 @@ def run_slowmo(args, torch, cabi, runner, S, dev, rank, world):
     lanes = fused.DirectionStreams(dev)
     out_ctx2, out_img2 = torch.empty_like(wl.out_ctx), torch.empty_like(wl.out_img)
 
-    def step2(i, record=False):
+    def step2(i, record=False, keep=False):
         lanes.fork()
         for d, oc, oi in ((0, wl.out_ctx, wl.out_img), (1, out_ctx2, out_img2)):
             with lanes.direction(d):
-                for a, b in wl.corr[d]:
-                    cabi.correlation_forward(a, b, 4, 1, 4, 1, 1)
+                for lv, (a, b) in enumerate(wl.corr[d]):
+                    corr = cabi.correlation_forward(a, b, 4, 1, 4, 1, 1)
+                    if keep:
+                        kept["corr_d%d_l%d" % (d, lv)] = corr
                 err = cabi.flowprojection_forward_batch(wl.flows[d], wl.counts[d], wl.projs[d], 1, wl.depth[d])
                 assert err == 0, err
                 for ti in range(len(TIMES)):
@@ -358,10 +407,25 @@ def run_slowmo(args, torch, cabi, runner, S, dev, rank, world):
     run_step = step2 if args.streams == 2 else step
     for i in range(args.warmup):
         run_step(i)
-    elapsed = runner.timed_region(lambda i: run_step(i, record=True), args.steps, dev)
+    dump = args.dump_outputs is not None
+    elapsed = runner.timed_region(lambda i: run_step(i, record=True, keep=dump and i == args.steps - 1), args.steps, dev)
     frames_total = runner.total_units(len(TIMES) * args.steps)
     value = frames_total / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    dumped = None
+    if dump and rank == 0:
+        # taken before anything else runs on these tensors.  Every warp of a kind writes one output tensor per stream, so
+        # after the step it holds that stream's last warp: time offset 2 of direction 1 (and of direction 0 on two streams)
+        outs = dict(kept)
+        for d in range(2):
+            for ti in range(len(TIMES)):
+                outs["proj_d%d_t%d" % (d, ti)] = wl.projs[d][ti]
+                outs["count_d%d_t%d" % (d, ti)] = wl.counts[d][ti]
+        last = len(TIMES) - 1
+        warps = {0: (wl.out_ctx, wl.out_img), 1: (out_ctx2, out_img2)} if args.streams == 2 else {1: (wl.out_ctx, wl.out_img)}
+        for d, (oc, oi) in warps.items():
+            outs["ctx_warp_d%d_t%d" % (d, last)], outs["frame_warp_d%d_t%d" % (d, last)] = oc, oi
+        dumped = dump_outputs(args.dump_outputs, outs)
 
     # ---- roofline of the dominant kernel, from HIP events recorded inside the timed region
     torch.cuda.synchronize(dev)
@@ -391,6 +455,8 @@ def run_slowmo(args, torch, cabi, runner, S, dev, rank, world):
                    "parallelism": "replicas x%d (one pair per GPU, no collective)" % world},
         "roofline": roofline,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     # five more repetitions of the timed region (every rank takes part: the region ends in a barrier): box-to-box and
     # run-to-run spread is of the order of a kernel improvement
     reps = [elapsed] + [runner.timed_region(lambda i: run_step(i), args.steps, dev) for _ in range(4)]

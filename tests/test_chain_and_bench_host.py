@@ -62,3 +62,30 @@ def test_best_schedule_block_is_the_median_of_the_repetitions():
     assert blk["ms_per_step"] == 5.5 and blk["frames_per_s"] == round(3 / 5.5e-3, 1)
     assert blk["spread"]["min"] == round(3 / 6.0e-3, 1) and blk["spread"]["max"] == round(3 / 5.0e-3, 1)
     assert blk["vs_value"] == round((3 / 5.5e-3) / 400.0, 3)
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 files, whole arrays where they fit their share of the budget, a seeded sample of the
+    rest, never more than the budget in all, and the same files from the same inputs."""
+    import torch
+    import bench
+    budget = bench.DUMP_BYTES // 4
+    g = torch.Generator().manual_seed(3)
+    arrays = {"small": torch.randn((1, 2, 3, 5), generator=g, dtype=torch.float64),
+              "half": torch.randn((4, 8), generator=g).half(),
+              "big": torch.randn((2, budget), generator=g),
+              "bigger": torch.randn((3, budget), generator=g)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    files = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert all(f.dtype == np.float32 for f in files.values())
+    assert sum(f.nbytes for f in files.values()) <= bench.DUMP_BYTES
+    assert np.array_equal(files["small"], arrays["small"].float().numpy())
+    assert np.array_equal(files["half"], arrays["half"].float().numpy())
+    whole = 30 + 32                                     # shared out smallest first: two arrays whole, two halves of the rest
+    assert files["big"].size == files["bigger"].size == (budget - whole) // 2
+    for n in ("big", "bigger"):
+        assert info[n]["shape"] == list(arrays[n].shape) and info[n]["elements"] == files[n].size
+        assert np.isin(files[n], arrays[n].numpy()).all()
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    for n in arrays:
+        assert np.array_equal(files[n], np.load(str(tmp_path / "b" / (n + ".npy"))))
