@@ -78,6 +78,74 @@ def filterinterp_ori_fwd(img, flow, filt):
     return np.where(valid[:, None], out, img).astype(f32)
 
 
+class _Scatter:
+    """Image-gradient cells [B,C,H,W] of a scatter op: the float64 sum e of the addends, S = sum |addend| and the addend
+    count n per cell (the image gradient is e; S and n bound what any fp32 or fixed-point summation order may differ by)."""
+
+    def __init__(self, B, C, H, W):
+        self.shape = (B, C, H, W)
+        self.e, self.S, self.n = np.zeros(B * C * H * W), np.zeros(B * C * H * W), np.zeros(B * C * H * W, np.int64)
+
+    def add(self, cj, ci, vals, mask):
+        """vals [B,C,H,W] float64 added at cell (cj, ci) [B,H,W] of their own batch / channel where mask [B,H,W]"""
+        B, C, H, W = self.shape
+        flat = ((np.arange(B)[:, None, None] * C + np.arange(C)[None, :, None]) * (H * W) +
+                (cj.astype(np.int64) * W + ci.astype(np.int64)).reshape(B, 1, H * W))
+        m = np.broadcast_to(mask.reshape(B, 1, H * W), flat.shape)
+        idx, v = flat[m], vals.reshape(B, C, H * W)[m]
+        np.add.at(self.e, idx, v)
+        np.add.at(self.S, idx, np.abs(v))
+        np.add.at(self.n, idx, 1)
+
+    def result(self):
+        return tuple(a.reshape(self.shape) for a in (self.e, self.S, self.n))
+
+
+def filterinterp_ori_bwd_img(flow, filt, gout):
+    """Image gradient of FilterInterpolation _ori (any fs), float64 accumulation: (e, S, n) per cell.  A valid pixel's tap
+    (dj, di) of quadrant quad sends gout * bilinear weight of quad * filter tap to the clamped cell (the
+    backward is its adjoint in the image).  Geometry in fp32 as the forward computes it."""
+    flow, filt, gout = flow.astype(f32), filt.astype(f32), gout.astype(f32)
+    B, C, H, W = gout.shape
+    fs = int(np.sqrt(f32(filt.shape[1])))
+    valid, _, _, ix, iy, alpha, beta, L, T = _fi_geometry(flow, H, W, fs)
+    a, b = alpha.astype(np.float64), beta.astype(np.float64)
+    kq = [(1 - a) * (1 - b), a * (1 - b), (1 - a) * b, a * b]
+    g64, f64 = gout.astype(np.float64), filt.astype(np.float64)
+    acc = _Scatter(B, C, H, W)
+    for dj in range(fs):
+        for di in range(fs):
+            j, i = T + dj, L + di
+            quad = (j > iy) * 2 + (i > ix)
+            wq = np.choose(quad, kq) * f64[:, dj * fs + di]
+            acc.add(np.clip(j, 0, H - 1), np.clip(i, 0, W - 1), g64 * wq[:, None], valid)
+    return acc.result()
+
+
+def interp_bwd_img(flow, gout):
+    """Image gradient of Interpolation, float64 accumulation: (e, S, n) per cell.  A valid pixel sends gout times its four
+    bilinear weights to (T, L), (T, R), (Bm, L), (Bm, R), R and Bm clamped to the frame."""
+    flow, gout = flow.astype(f32), gout.astype(f32)
+    B, C, H, W = gout.shape
+    xs, ys = _grid(B, H, W)
+    x2 = xs + flow[:, 0]
+    y2 = ys + flow[:, 1]
+    valid = (x2 >= 0) & (y2 >= 0) & (x2 < f32(W)) & (y2 < f32(H))
+    x2 = np.where(valid, x2, f32(0))
+    y2 = np.where(valid, y2, f32(0))
+    L = np.trunc(x2).astype(np.int32)
+    T = np.trunc(y2).astype(np.int32)
+    R = np.minimum(L + 1, W - 1)
+    Bm = np.minimum(T + 1, H - 1)
+    a = (x2 - L.astype(f32)).astype(np.float64)[:, None]
+    b = (y2 - T.astype(f32)).astype(np.float64)[:, None]
+    g = gout.astype(np.float64)
+    acc = _Scatter(B, C, H, W)
+    for cj, ci, wt in ((T, L, (1 - a) * (1 - b)), (T, R, a * (1 - b)), (Bm, L, (1 - a) * b), (Bm, R, a * b)):
+        acc.add(cj, ci, g * wt, valid)
+    return acc.result()
+
+
 def _defor_tap(img, fracY, fracX):
     B, C, H, W = img.shape
     top = np.trunc(fracY).astype(np.int32)
@@ -129,8 +197,9 @@ def filterinterp_defor_fwd(variant, img, flow, filt, off):
     return np.where(valid[:, None], out, img).astype(f32)
 
 
-def filterinterp_defor_bwd(variant, img, flow, filt, off, gout):
-    """float64 formulation of the deformable backwards; returns (gimg, gflow, gfilt or None, goff)."""
+def filterinterp_defor_bwd(variant, img, flow, filt, off, gout, img_stats=False):
+    """float64 formulation of the deformable backwards; returns (gimg, gflow, gfilt or None, goff).
+    img_stats: gimg is the triple (e, S, n) per cell (_Scatter)."""
     img, flow, off, gout = (a.astype(np.float64) for a in (img, flow, off, gout))
     B, C, H, W = img.shape
     if variant == 2:
@@ -143,7 +212,7 @@ def filterinterp_defor_bwd(variant, img, flow, filt, off, gout):
     valid, x2, y2, ix, iy, alpha, beta, L, T = _fi_geometry(flow.astype(f32), H, W, fs)
     x2, y2, alpha, beta = (a.astype(np.float64) for a in (x2, y2, alpha, beta))
     kq = [(1 - alpha) * (1 - beta), alpha * (1 - beta), (1 - alpha) * beta, alpha * beta]
-    gimg = np.zeros((B, C, H * W))
+    gimg = _Scatter(B, C, H, W)
     gfilt = None if filt is None else np.zeros_like(filt)
     goff = np.zeros_like(off)
     q = [np.zeros((B, C, H, W)) for _ in range(4)]
@@ -170,10 +239,7 @@ def filterinterp_defor_bwd(variant, img, flow, filt, off, gout):
             wq = np.choose(quad, kq) * valid                         # [B,H,W]
             wgt = 1.0 if filt is None else filt[:, k]
             gw = gout * wq[:, None]                                   # [B,C,H,W]
-            idx = (cj * W + ci).reshape(B, 1, H * W)
-            for b in range(B):
-                for c in range(C):
-                    np.add.at(gimg[b, c], idx[b, 0], (gw[b, c] * (wgt if filt is None else wgt[b])).reshape(-1))
+            gimg.add(cj, ci, gw if filt is None else gw * wgt[:, None], valid)
             if filt is not None:
                 gfilt[:, k] = (gw * v).sum(1)
             goff[:, k] = (gw * dY).sum(1) * wgt
@@ -184,7 +250,7 @@ def filterinterp_defor_bwd(variant, img, flow, filt, off, gout):
     gx = (gout * ((1 - b_) * (q[1] - q[0]) + b_ * (q[3] - q[2]))).sum(1) * valid
     gy = (gout * ((1 - a) * (q[2] - q[0]) + a * (q[3] - q[1]))).sum(1) * valid
     gflow = np.stack([gx, gy], 1)
-    return gimg.reshape(B, C, H, W), gflow, gfilt, goff
+    return gimg.result() if img_stats else gimg.result()[0], gflow, gfilt, goff
 
 
 def _project_targets(flow, H, W):

@@ -560,6 +560,110 @@ def test_frame_ssim_matches_torch_formulation(oracle):
     assert abs(oracle.frame_ssim(flat, other) - (2 * a * b + 1e-4) / (a * a + b * b + 1e-4)) <= 1e-9
 
 
+# ------------------------------------------------------------------ 3a. float64 image-gradient references (e, S, n)
+
+U32 = 2.0 ** -24
+# fp32 roundings of one addend before it is summed: 1 - alpha, 1 - beta and the products (gout x weights x filter tap)
+ADDEND_ROUNDINGS = {"ori": 5, "defor": 5, "interp": 4}
+
+
+def _fwd64_ori(np_oracle, d, flow, filt, clamped_quads=False):
+    """FilterInterpolation _ori forward of a float64 image on the valid pixels (0 elsewhere), weights from fp32 geometry.
+    clamped_quads: a tap's quadrant from its clamped cell against the sample position (the deformable variants 1 and 2
+    at zero offsets) instead of from its window position"""
+    B, C, H, W = d.shape
+    fs = int(np.sqrt(filt.shape[1]))
+    valid, x2, y2, ix, iy, alpha, beta, L, T = np_oracle._fi_geometry(flow, H, W, fs)
+    a, b = alpha.astype(np.float64), beta.astype(np.float64)
+    kq = [(1 - a) * (1 - b), a * (1 - b), (1 - a) * b, a * b]
+    out = np.zeros(d.shape)
+    for dj in range(fs):
+        for di in range(fs):
+            j, i = T + dj, L + di
+            cj, ci = np.clip(j, 0, H - 1), np.clip(i, 0, W - 1)
+            quad = (cj > y2) * 2 + (ci > x2) if clamped_quads else (j > iy) * 2 + (i > ix)
+            w = np.choose(quad, kq) * filt[:, dj * fs + di].astype(np.float64)
+            out += w[:, None] * np_oracle._gather(d, cj, ci)
+    return out * valid[:, None]
+
+
+def _fwd64_interp(d, flow):
+    B, C, H, W = d.shape
+    x2 = np.arange(W, dtype=f32)[None, None, :] + flow[:, 0]
+    y2 = np.arange(H, dtype=f32)[None, :, None] + flow[:, 1]
+    valid = (x2 >= 0) & (y2 >= 0) & (x2 < f32(W)) & (y2 < f32(H))
+    x2, y2 = np.where(valid, x2, f32(0)), np.where(valid, y2, f32(0))
+    L, T = np.trunc(x2).astype(np.int64), np.trunc(y2).astype(np.int64)
+    R, Bm = np.minimum(L + 1, W - 1), np.minimum(T + 1, H - 1)
+    a = (x2 - L.astype(f32)).astype(np.float64)[:, None]
+    b = (y2 - T.astype(f32)).astype(np.float64)[:, None]
+    bi = np.arange(B)[:, None, None]
+
+    def g(ty, tx):
+        return np.moveaxis(d[bi, :, ty, tx], -1, 1)
+    out = (1 - a) * (1 - b) * g(T, L) + a * (1 - b) * g(T, R) + (1 - a) * b * g(Bm, L) + a * b * g(Bm, R)
+    return out * valid[:, None]
+
+
+def _bwd_flow_models(rng, B, H, W):
+    yield smooth_flow(rng, B, H, W, 2.0)
+    yield rng.uniform(-W / 2, W / 2, (B, 2, H, W)).astype(f32)                      # wild: many invalid pixels
+    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    yield np.stack([(W - 1 - xs) * 0.45, -ys * 0.45]).astype(f32)[None].repeat(B, 0)   # taps clamped onto the border
+
+
+@pytest.mark.parametrize("op,fs", [("ori", 2), ("ori", 3), ("ori", 4), ("ori", 5), ("ori", 6),
+                                   ("defor0", 4), ("defor1", 3), ("defor2", 4), ("interp", 0)])
+def test_image_gradient_float64_references(oracle, np_oracle, op, fs):
+    """The float64 references of the scattered image gradients: the C oracle's sequential fp32 sums lie within
+    (n + r) u S of the exact sum e (n addends per cell summed in order, r fp32 roundings per addend), are equal to e on
+    dyadic inputs, and e satisfies the adjoint identity <F(d), gout> = <d, e> in float64."""
+    rng = np.random.default_rng(sum(map(ord, op)) + fs)
+    B, C, H, W = 2, 3, 9, 13
+    kind = "defor" if op.startswith("defor") else op
+    variant = int(op[-1]) if kind == "defor" else None
+    taps = fs * fs if fs else 4
+    filt = rng.random((B, taps, H, W), dtype=f32)
+    off = rng.uniform(-1.2, 1.2, (B, 2 * taps, H, W)).astype(f32)
+    img = rng.random((B, C, H, W), dtype=f32)
+
+    def both(flow, filt, off, gout):
+        if kind == "ori":
+            return np_oracle.filterinterp_ori_bwd_img(flow, filt, gout), [
+                oracle.filterinterp_ori_bwd(img, flow, filt, gout, fmad=m)[0] for m in (0, 1)]
+        if kind == "interp":
+            return np_oracle.interp_bwd_img(flow, gout), [oracle.interp_bwd(img, flow, gout, fmad=m)[0] for m in (0, 1)]
+        return np_oracle.filterinterp_defor_bwd(variant, img, flow, filt, off, gout, img_stats=True)[0], [
+            oracle.filterinterp_defor_bwd(variant, img, flow, filt, off, gout, fmad=m)[0] for m in (0, 1)]
+
+    for flow in _bwd_flow_models(rng, B, H, W):
+        gout = rng.normal(size=(B, C, H, W)).astype(f32)
+        (e, S, n), seq = both(flow, filt, off, gout)
+        assert n.sum() > 0 and not S[n == 0].any()
+        bound = (n + ADDEND_ROUNDINGS[kind]) * U32 * S * (1 + 1e-6)
+        for got in seq:
+            assert np.all(np.abs(got - e) <= bound), np.abs(got - e).max()
+        # dyadic: gradoutput and filters in 1/16, flows in 1/4 (offsets in 1/4): every addend and sum exact in fp32
+        fq = (np.round(flow * 4) / 4).astype(f32)
+        gq = (np.round(gout * 16) / 16).astype(f32)
+        filtq = (np.round(filt * 16) / 16).astype(f32)
+        offq = (np.round(off * 4) / 4).astype(f32)
+        (eq, _, _), seqq = both(fq, filtq, offq, gq)
+        for got in seqq:
+            assert np.array_equal(got, eq.astype(f32)) and np.array_equal(got.astype(np.float64), eq)
+        # adjoint: the image gradient is the transpose of the forward's image map (the deformable backward scatters to the
+        # undeformed taps, i.e. the transpose of the zero-offset forward)
+        d = rng.normal(size=img.shape)
+        if kind == "interp":
+            fd = _fwd64_interp(d, flow)
+        else:
+            fd = _fwd64_ori(np_oracle, d, flow, filt if variant != 2 else np.ones((B, taps, H, W), f32), variant in (1, 2))
+            if kind == "defor":
+                e = np_oracle.filterinterp_defor_bwd(variant, img, flow, filt, np.zeros_like(off), gout, img_stats=True)[0][0]
+        lhs, rhs = float(np.sum(fd * gout)), float(np.sum(d * e))
+        assert abs(lhs - rhs) <= 1e-9 * float(np.sum(np.abs(fd * gout))), (lhs, rhs)
+
+
 # ------------------------------------------------------------------ 3b. random shapes (hypothesis): the two formulations agree
 
 def test_random_shapes_c_equals_numpy(oracle, np_oracle):

@@ -192,9 +192,9 @@ def filterinterp_backward_ori(input1, input2, input3, gradoutput, gradinput1, gr
     dims = _fi_checks(input1, input2, input3, gradinput1)
     if dims is None:
         return 1
-    if input2.stride(0) != gradinput2.stride(0) or input2.stride(1) != gradinput2.stride(1):
-        return 1
-    if input3.stride(1) != gradinput3.stride(1):
+    # the library addresses gradoutput / gradinput1 with input1's strides, gradinput2 with input2's, gradinput3 with input3's
+    if not _addressed_as(input1, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2) or \
+            not _addressed_as(input3, gradinput3) or not _fi_filter_ok(input1, input3):
         return 1
     b, c, h, w = dims
     with torch.cuda.device(_dev(input1)):
@@ -230,16 +230,15 @@ def filterinterp_backward_defor(variant, input1, input2, input3, input4, gradout
     dims = _fi_checks(input1, input2, input3, gradinput1)
     if dims is None:
         return 1
-    if input2.stride(0) != gradinput2.stride(0) or input2.stride(1) != gradinput2.stride(1):
-        return 1
-    if input3.stride(1) != gradinput3.stride(1):
+    if not _addressed_as(input1, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2) or \
+            not _addressed_as(input3, gradinput3) or not _fi_filter_ok(input1, input3):
         return 1
     b, c, h, w = dims
     if variant == DEFOR_NOFILTER:
         fs = int(math.sqrt(input3.size(1) // 2))
         p4, g4, s4 = ctypes.c_void_p(0), ctypes.c_void_p(0), _st(input3)
     else:
-        if input4.stride(3) != 1:
+        if input4.stride(3) != 1 or not _addressed_as(input4, gradinput4) or not _fi_filter_ok(input1, input4):
             return 1
         fs = int(math.sqrt(input3.size(1)))
         p4, g4, s4 = _ptr(input4), _ptr(gradinput4), _st(input4)
@@ -313,7 +312,7 @@ def flowprojection_backward(input1, count, gradoutput, gradinput1):
     b, _, h, w = input1.shape
     if input1.size(1) != 2 or tuple(count.shape) != (b, 1, h, w):
         return 1
-    if input1.stride(0) != gradinput1.stride(0) or input1.stride(1) != gradinput1.stride(1):
+    if not _addressed_as(input1, gradoutput, gradinput1):
         return 1
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_flowprojection_backward(_ptr(input1), _ptr(count), _ptr(gradoutput),
@@ -335,9 +334,10 @@ def depthflowprojection_forward(input1, input2, count, output, fillhole):
 
 def depthflowprojection_backward(input1, input2, count, output, gradoutput, gradinput1, gradinput2):
     b, _, h, w = input1.shape
-    if input1.size(1) != 2 or input2.size(1) != 1 or tuple(count.shape) != (b, 1, h, w):
+    if input1.size(1) != 2 or tuple(input2.shape) != (b, 1, h, w) or tuple(count.shape) != (b, 1, h, w):
         return 1
-    if input1.stride(0) != gradinput1.stride(0) or input1.stride(1) != gradinput1.stride(1):
+    # output, gradoutput and gradinput1 are addressed with input1's strides, gradinput2 with input2's
+    if not _addressed_as(input1, output, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2):
         return 1
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_depthflowprojection_backward(
@@ -361,9 +361,9 @@ def mindepthflowprojection_forward(input1, input2, count, output, fillhole):
 def mindepthflowprojection_backward(input1, input2, count, output, gradoutput, gradinput1, gradinput2):
     """mindepthflowprojection_cuda.cc:68-139; `output` and `gradinput2` are accepted and unused, as in the reference."""
     b, _, h, w = input1.shape
-    if input1.size(1) != 2 or input2.size(1) != 1 or tuple(count.shape) != (b, 1, h, w):
+    if input1.size(1) != 2 or tuple(input2.shape) != (b, 1, h, w) or tuple(count.shape) != (b, 1, h, w):
         return 1
-    if input1.stride(0) != gradinput1.stride(0) or input1.stride(1) != gradinput1.stride(1):
+    if not _addressed_as(input1, gradoutput, gradinput1):
         return 1
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_mindepthflowprojection_backward(
@@ -390,11 +390,9 @@ def interpolation_backward(input1, input2, gradoutput, gradinput1, gradinput2, r
     b, c, h, w = input1.shape
     if require_c3 and c != 3:
         return 1
-    if tuple(input2.shape) != (b, 2, h, w):
+    if tuple(input2.shape) != (b, 2, h, w) or input1.stride(3) != 1 or input2.stride(3) != 1:
         return 1
-    if input1.stride(0) != gradinput1.stride(0) or input1.stride(1) != gradinput1.stride(1):
-        return 1
-    if input2.stride(0) != gradinput2.stride(0) or input2.stride(1) != gradinput2.stride(1):
+    if not _addressed_as(input1, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2):
         return 1
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_interpolation_backward(_ptr(input1), _ptr(input2), _ptr(gradoutput),
@@ -433,7 +431,11 @@ def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradi
     dims = _sep_checks(input1, input2, input3)
     if dims is None or gradoutput.stride(3) != 1:
         return 1
+    if not _addressed_as(input1, gradinput1) or not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):
+        return 1
     b, c, h, w, fs = dims
+    if tuple(gradoutput.shape) != (b, c, h - fs + 1, w - fs + 1):
+        return 1
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_separableconv_backward(
             _ptr(input1), _ptr(input2), _ptr(input3), _ptr(gradoutput), _ptr(gradinput1), _ptr(gradinput2),
@@ -456,7 +458,11 @@ def separableconvflow_backward(input1, input2, input3, gradflow_output, gradinpu
     dims = _sep_checks(input1, input2, input3)
     if dims is None or gradflow_output.stride(3) != 1:
         return 1
+    if not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):
+        return 1
     b, c, h, w, fs = dims
+    if tuple(gradflow_output.shape) != (b, 2, h - fs + 1, w - fs + 1):
+        return 1
     with torch.cuda.device(_dev(input2)):
         return _finish(lib().vfi_separableconvflow_backward(
             _ptr(input2), _ptr(input3), _ptr(gradflow_output), _ptr(gradinput2), _ptr(gradinput3), b, h, w, fs,
@@ -520,6 +526,9 @@ def correlation_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displace
 def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_displacement, stride1, stride2):
     input1, input2, gradoutput = input1.contiguous(), input2.contiguous(), gradoutput.contiguous()
     b, c, h, w = input1.shape
+    if input2.shape != input1.shape or \
+            tuple(gradoutput.shape) != (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2):
+        raise RuntimeError("correlation_backward: input2 / gradoutput do not match input1's shape and the output dimensions")
     g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
     with torch.cuda.device(_dev(input1)):
         err = lib().vfi_correlation_backward(_ptr(input1), _ptr(input2), _ptr(gradoutput), _ptr(g1), _ptr(g2), b, c,
@@ -576,6 +585,17 @@ def depthflowprojection_forward_up4(flow_q, input2, count, output, mul0, mul1, f
 def _same_strides(a, b):
     """same layout: the stride of a dimension of size 1 is never used (torch leaves it arbitrary, e.g. after slicing)"""
     return a.shape == b.shape and all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n != 1)
+
+
+def _addressed_as(ref, *tensors):
+    """tensors the library reads or writes with ref's strides: same shape and layout as ref, or the call would address
+    other elements than the caller's"""
+    return all(t is not None and t.dim() == 4 and _same_strides(t, ref) for t in tensors)
+
+
+def _fi_filter_ok(input1, filt):
+    """a per-pixel filter / offset tensor: one plane of taps per pixel of input1"""
+    return filt.dim() == 4 and filt.size(0) == input1.size(0) and tuple(filt.shape[2:]) == tuple(input1.shape[2:])
 
 
 def filterinterp_blend_forward(ref0, ref2, flow0, flow2, filt0, filt2, blend, out0, out2, w0, w2):

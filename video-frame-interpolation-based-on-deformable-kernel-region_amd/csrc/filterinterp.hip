@@ -219,7 +219,7 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
     // whole DMA instructions, so that a window's last instruction stays inside its slot
     const int slot_floats = (n + FB_THREADS - 1) & ~(FB_THREADS - 1);
     const int pc = min(FB_CH, FB_CELLS / slot_floats);
-    if (gctx.nonfinite || pc == 0 || (int64_t)h * hs * 4 > INT_MAX) {     // (workgroup-uniform) left to fi_backward_ori
+    if (!gradacc_staged_ok(gctx) || pc == 0 || (int64_t)h * hs * 4 > INT_MAX) {     // (workgroup-uniform) left to fi_backward_ori
         if (tid == 0) tileflag[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = 1;
         return;
     }
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_defor(
         if (box[0] == INT_MAX) return;                      // (block-uniform: no pixel of the block has a gradient)
         bx0 = box[0]; by0 = box[1]; bw = box[2] - box[0] + 1;
         n = bw * (box[3] - box[1] + 1);
-        if (gctx.nonfinite || n * min(FD_CH, channel) > FD_CELLS) {      // (block-uniform) left to the !STAGED instance
+        if (!gradacc_staged_ok(gctx) || n * min(FD_CH, channel) > FD_CELLS) {      // (block-uniform) left to the !STAGED instance
             if (tid == 0) tileflag[tile] = 1;
             return;
         }

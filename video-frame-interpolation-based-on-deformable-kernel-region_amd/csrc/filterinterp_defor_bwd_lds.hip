@@ -137,7 +137,7 @@ __global__ __launch_bounds__(DB_THREADS, 2) void fi_backward_defor_lds(
     const int pitch = (bw + 31) & ~31;                      // (a multiple of the 32 banks: fi_pitch_for's fp32 case)
     const int64_t n64 = (int64_t)pitch * bh;
     const int pc = min(DB_CH, DB_CELLS / max(ncell, 1));   // channels per pass: as many as the gradient cells allow
-    if (gctx.nonfinite || box[8] || n64 > DB_WIN_FLOATS || pc == 0) {      // (block-uniform)
+    if (!gradacc_staged_ok(gctx) || box[8] || n64 > DB_WIN_FLOATS || pc == 0) {      // (block-uniform)
         if (tid == 0) tileflag[tile] = 1;                   // left to fi_backward_defor<VARIANT, false, 4>
         return;
     }

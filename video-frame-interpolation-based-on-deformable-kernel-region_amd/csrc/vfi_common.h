@@ -91,33 +91,54 @@ int fi_channel_groups(int ntiles, int channel, double prologue);
 // (the filter tensor; 1 where the weights are bilinear fractions only) and T = the taps of a pixel (fs x fs; 4 for a
 // bilinear sample): an addend is below 2^(62 - ceil(log2(h w T))) and even a cell that EVERY tap of EVERY pixel of the frame
 // hits (border clamping folds a pixel's taps onto one cell) stays inside 63 bits -- no combination of finite inputs overflows.
-// Non-finite inputs: the first pass raises a flag when gradoutput or the weights hold a NaN or an infinity, and the
-// kernels then scatter with the reference's own fp32 atomics for that call (NaN / Inf propagate to exactly the cells
-// the reference would poison; the integer path would turn them into finite garbage).
+// The scale is applied as two power-of-two factors (2^min(k, 126), then 2^(k - min(k, 126))): k exceeds 126 when the inputs
+// are tiny, and one fp32 factor clamped at 2^126 would round those addends onto a coarse grid.  Where k <= 126 the second
+// factor is 1 and the bits are those of a single multiply.
+// fp32 atomics instead: the first pass raises a flag when gradoutput or the weights hold a NaN or an infinity, and the
+// kernels scatter with the reference's own fp32 atomics for that call when the flag is up OR when 2^eg x 2^ew reaches
+// 2^128, i.e. when finite inputs admit a product that overflows to an infinity (NaN / Inf propagate to exactly the cells
+// the reference would poison; the integer path would turn them into finite garbage).  gradacc_fp32 is that one predicate.
 //   host:   gradacc_begin (zeroes the scratch; largest |gradoutput|, largest |weight|, non-finite flag)  ->  the backward kernel
 //           ->  gradacc_finish
 //   device: gradacc_ctx(hdr) once per thread, gradacc_add(...) per addend; cells are indexed densely [b][c][y][x] whatever
 //           the strides of the gradient tensor.
 // hdr words: [0] bits of max |gradoutput|, [1] non-finite flag, [2] bits of max |weight| (0: none given), [3] ceil(log2(h w T))
-struct GradAccCtx { float scale; bool nonfinite; };
-__device__ __forceinline__ int gradacc_exponent(const int* __restrict__ hdr) {
+struct GradAccCtx { float scale, scale2; bool nonfinite; };
+// eg + ew: 2^eg > max |gradoutput|, 2^ew > max |tap weight|
+__device__ __forceinline__ int gradacc_magnitude(const int* __restrict__ hdr) {
     int eg = 0, ew = 1;                                     // no weight tensor: |weight| <= 1 < 2^1
     (void)frexpf(__int_as_float(hdr[0]), &eg);
     if (hdr[2] != 0) (void)frexpf(__int_as_float(hdr[2]), &ew);
-    return max(-126, min(126, 62 - hdr[3] - eg - max(ew, 1)));
+    return eg + max(ew, 1);
+}
+// the scale exponent k (not clamped: from 62 - L - 256 to 62 - L + 147; the integer path only sees k >= -66 - L)
+__device__ __forceinline__ int gradacc_exponent(const int* __restrict__ hdr) {
+    return 62 - hdr[3] - gradacc_magnitude(hdr);
+}
+// true: this call scatters with fp32 atomics (a non-finite input, or finite inputs whose product can reach 2^128)
+__device__ __forceinline__ bool gradacc_fp32(const int* __restrict__ hdr) {
+    return hdr[1] != 0 || gradacc_magnitude(hdr) > 128;
 }
 __device__ __forceinline__ GradAccCtx gradacc_ctx(const int* __restrict__ hdr) {
     GradAccCtx c;
-    c.scale = ldexpf(1.0f, gradacc_exponent(hdr));
-    c.nonfinite = hdr[1] != 0;
+    const int k = gradacc_exponent(hdr);
+    const int k1 = max(-126, min(126, k));
+    c.scale = ldexpf(1.0f, k1);
+    c.scale2 = ldexpf(1.0f, max(-126, min(126, k - k1)));    // 1 unless k > 126 (k - k1 <= 81 then)
+    c.nonfinite = gradacc_fp32(hdr);
     return c;
 }
+// v * 2^k: exact (a power-of-two scaling of an fp32 value that stays in range), bit-identical to v * scale when k <= 126
+__device__ __forceinline__ float gradacc_scaled(float v, const GradAccCtx& cx) { return v * cx.scale * cx.scale2; }
+// The LDS-staged kernels multiply by `scale` alone (one multiply per addend in their inner loops) and leave a call whose scale
+// needs the second factor (k > 126: tiny gradients) to the per-tap kernels, as they do a call that scatters in fp32.
+__device__ __forceinline__ bool gradacc_staged_ok(const GradAccCtx& cx) { return !cx.nonfinite && cx.scale2 == 1.0f; }
 // acc_plane / g_plane: the channel's plane of the dense scratch and of the caller's gradient tensor; di / gi: the cell's
 // index in each
 __device__ __forceinline__ void gradacc_add(unsigned long long* acc_plane, float* g_plane, int64_t di, int64_t gi, float v,
                                             const GradAccCtx& cx) {
     if (cx.nonfinite) atomicAdd(&g_plane[gi], v);
-    else atomicAdd(&acc_plane[di], (unsigned long long)__float2ll_rn(v * cx.scale));
+    else atomicAdd(&acc_plane[di], (unsigned long long)__float2ll_rn(gradacc_scaled(v, cx)));
 }
 // weights (may be null): a [batch, wchannel, h, w] tensor whose largest |element| bounds the tap weights; wchannel = the taps
 // of a pixel (also when weights is null; below 4: 4);

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(IB_THREADS) void interp_backward_lds(
     const int bx0 = box[0], by0 = box[1], bw = box[2] - box[0] + 1, bh = box[3] - box[1] + 1;
     const int n = bw * bh;
     const int pc = min(IB_CH, IB_CELLS / n);                // channels per pass: as many as the cells allow
-    if (gctx.nonfinite || pc == 0) {                        // (workgroup-uniform) left to interp_backward
+    if (!gradacc_staged_ok(gctx) || pc == 0) {                        // (workgroup-uniform) left to interp_backward
         if (tid == 0) tileflag[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = 1;
         return;
     }

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void gradacc_max(const float* __restrict__ g, 
 
 __global__ __launch_bounds__(256) void gradacc_convert(const unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
                                                        float* __restrict__ g1, int channel, int h, int w, vfi_strides s1, int64_t n) {
-    if (hdr[1] != 0) return;                                // the call scattered with fp32 atomics: nothing in the scratch
+    if (gradacc_fp32(hdr)) return;                          // the call scattered with fp32 atomics: nothing in the scratch
     const int k = gradacc_exponent(hdr);
     const int rows = (int)(n / w);
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
