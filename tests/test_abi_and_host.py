@@ -51,7 +51,7 @@ def test_library_exports_every_declared_symbol(built):
 
 
 def test_product_library_exports_no_development_knobs(built):
-    """Kernel-selection knobs exist only in -DVFI_DEV builds: the product exports the declared ABI, the internal
+    """Kernel-selection thresholds are compile-time constants: the library exports the declared ABI, the internal
     single-path entry points the tests and tools time, and nothing that mutates process-global state."""
     out = subprocess.run(["nm", "-D", "--defined-only", built.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("vfi_")}
@@ -319,7 +319,7 @@ def test_no_register_spills_inside_the_counted_vmcnt_pipelines(built):
                 if m and int(m.group(1)) > 0 and b["loop"]:
                     counted.add(b["loop"])
         for b in blocks:
-            # (the multi-flow kernel keeps 2 x 3 pixel states: its straight-line prologue, which also issues the first
+            # (the multi-flow kernel keeps 2 x 2 pixel states: its straight-line prologue, which also issues the first
             #  windows, spills a few registers once per tile; what must stay clean there is the channel loop)
             prologue_ok = name == "filterinterp_multi.s"
             if "fi_forward_ori_ldsILb1E" in b["func"]:

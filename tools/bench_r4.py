@@ -4,7 +4,8 @@
     python tools/bench_r4.py [--what projbatch,multi,single] [--flows smooth,quarter] [--iters 100]
 projbatch  FlowProjection / DepthFlowProjection: n single calls against ONE batched call of n items (n = 1, 2, 6), hot
            (same buffers every call) and cold (rotation through > 512 MB of sets)
-multi      fi_forward_ori_multi<3> and <2> on the 196-channel context tensor (three / two time offsets of a direction)
+multi      the shared-window entry point on the 196-channel context tensor with three / two time offsets of a direction
+           (three go as a two-flow launch + a single-flow one)
 single     fi_forward_ori_lds C=196 and C=3 for reference
 """
 import argparse
@@ -43,11 +44,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--lib", default=None)
-    ap.add_argument("--kpair", type=int, default=None, help="development build: largest K staged as pairs by the shared-window kernel (0 = never)")
-    ap.add_argument("--group", type=int, default=3, help="development build: flows per shared-window launch (2 or 3)")
     args = ap.parse_args()
-    if args.kpair is not None:
-        cabi.lib().vfi_dev_multi(args.kpair, args.group)
     dev = torch.device("cuda:0")
     h, w = S.padded_size(args.height, args.width)
     px = h * w

@@ -1,5 +1,6 @@
+"""C=196-style FilterInterpolation launch time against the channel count (1080p, smooth flow)."""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import vfidkr_amd
 from vfidkr_amd import cabi, synthetic as S
@@ -17,9 +18,7 @@ def timed(fn, n=20):
     b.record(); torch.cuda.synchronize()
     return a.elapsed_time(b) / n
 timed(lambda: cabi.filterinterp_forward_ori(full, flow, filt, torch.empty_like(full)))
-for groups in (1, 2):
-    cabi.lib().vfi_dev_filterinterp(0, groups)
-    for C in (12, 24, 49, 98, 196):
-        x = full[:, :C].contiguous(); o = torch.empty_like(x)
-        ms = timed(lambda: cabi.filterinterp_forward_ori(x, flow, filt, o))
-        print("groups %d C=%3d  %8.4f ms  per channel %7.2f us" % (groups, C, ms, ms * 1e3 / C), flush=True)
+for C in (12, 24, 49, 98, 196):
+    x = full[:, :C].contiguous(); o = torch.empty_like(x)
+    ms = timed(lambda: cabi.filterinterp_forward_ori(x, flow, filt, o))
+    print("C=%3d  %8.4f ms  per channel %7.2f us" % (C, ms, ms * 1e3 / C), flush=True)

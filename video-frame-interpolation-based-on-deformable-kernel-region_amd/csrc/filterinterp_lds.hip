@@ -27,8 +27,8 @@
 // A tile whose tap window does not fit the LDS budget (wildly divergent flow)
 // gathers from global memory instead -- same results, decided per workgroup.
 //
-// Launch: 1-D grid of tiles in row-major order (an XCD-contiguous band mapping
-// was measured slower, see the kernel).  An optional split of the channel range
+// Launch: 1-D grid of tiles in row-major order, four consecutive tiles per XCD
+// (see the kernel).  An optional split of the channel range
 // over blockIdx.y shortens the tail when the tile count does not fill the chip
 // evenly.
 #include "filterinterp_dev.h"
@@ -50,40 +50,22 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 #define FI_TW 64
-#ifndef FI_TH
 #define FI_TH 16
-#endif
-#ifndef FI_PX
 #define FI_PX 2                                     // pixels per thread (rows y, y + FI_TH/FI_PX, ...)
-#endif
 #define FI_THREADS (FI_TW * FI_TH / FI_PX)          // 512
 #define FI_PASS_ROWS (FI_TH / FI_PX)
 #define FI_KS (FI_PX / 2)                           // staged elements per thread scale with the pixels per thread
 #define FI_HDR 16                                   // floats at the head of the LDS array (bounding box)
-#ifndef FI_RING_FLOATS
 #define FI_RING_FLOATS 20464                        // LDS ring: 20480 floats = 81,920 B with the header: two workgroups = a CU's 160 KB (round 4; 64,000 B before)
-#endif
-#ifndef FI_RMAX
 #define FI_RMAX 5                                   // ring slots, at most (4 windows in flight)
-#endif
-#define FI_KTOP ((FI_RING_FLOATS / (2 * FI_THREADS)) < 15 * FI_KS ? 12 * FI_KS : 15 * FI_KS)    // staged elements per thread and channel, at most (two ring slots)
+#define FI_WAVES (8 / FI_PX)                        // waves per SIMD the kernel must fit (4: two 512-thread workgroups per CU)
+#define FI_KTOP (15 * FI_KS)                        // staged elements per thread and channel, at most (two ring slots)
+static_assert(2 * FI_KTOP * FI_THREADS <= FI_RING_FLOATS, "the largest window takes two ring slots");
 #define FI_XCDS 8
 #define FI_B64_MIN_BH 34                             // bounding box from which a tile takes the aligned 8-byte tap reads
 #define FI_B64_MIN_BW 92
-#ifdef VFI_DEV
-#define FI_ABL(flags) (((flags) >> 20) & 255)       // development: parts of the lean loop switched off or aliased (wrong results, timing only)
-#else
-#define FI_ABL(flags) 0
-#endif
 
 typedef __attribute__((address_space(3))) void* fi_lptr_t;
-
-#ifdef FI_STAMPS            // development build only: where a channel step's cycles go (tools/fm_stamps.py --single)
-__device__ unsigned long long g_fi_stamps[8];       // s_memtime ticks: [0] staging issue, [1] compute, [2] vmcnt wait, [3] barrier, [4] steps
-#define FI_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define FI_T(v)
-#endif
 
 __device__ __forceinline__ int wave_min(int v) { return wave_min_i32(v); }
 __device__ __forceinline__ int wave_max(int v) { return wave_max_i32(v); }
@@ -121,9 +103,9 @@ __device__ __forceinline__ void fi_wait_windows(int younger_groups) {
 template <int K, bool BLEND>
 __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
                                                 int c_begin, int c_end, int tid, const FiWindow& win,
-                                                const FiPixel (&px)[FI_PX], float* __restrict__ ring, int R,
-                                                int flags, const FiBlend& bl) {
-    static_assert((FI_RING_FLOATS / (K * FI_THREADS) < FI_RMAX ? FI_RING_FLOATS / (K * FI_THREADS) - 2 : FI_RMAX - 2) * K <= 63, "vmcnt is a 6-bit counter");
+                                                const FiPixel (&px)[FI_PX], float* __restrict__ ring, const FiBlend& bl) {
+    constexpr int R = (FI_RING_FLOATS / (K * FI_THREADS)) < FI_RMAX ? (FI_RING_FLOATS / (K * FI_THREADS)) : FI_RMAX;
+    static_assert(R >= 2 && (R - 2) * K <= 63, "vmcnt is a 6-bit counter");
     // Element e = tid + k*FI_THREADS of the staged window, row-major with row pitch `pitch` = bw
     // rounded up to a multiple of 32 floats: with the pitch a multiple of the 32 LDS banks a tap's
     // bank depends on its column only, so lanes of a wave whose windows sit on different rows do
@@ -146,7 +128,7 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
     }
     const int plane_bytes = 4 * ((win.h - 1) * win.hs + win.w);
     constexpr int NP = K * FI_THREADS;                      // floats per ring slot
-    const int D = R - 1;                                    // windows in flight
+    constexpr int D = R - 1;                                // windows in flight
     auto issue = [&](int c, int slot) {
         const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * cs), 0, plane_bytes, 0x00020000);
         // (the LDS destination is M0 = the wave's first element.  Formed on the scalar unit from a provably uniform wave id it
@@ -197,10 +179,9 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
     int slot = 0;
     for (int c = c_begin; c <= last; ++c) {
         // the slot read in the previous iteration is free: every wave passed that barrier
-        // (issuing before the compute phase measured ~5 % faster than after it: flag bit 0)
-        if (!(flags & 1) && c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);
+        // (issuing before the compute phase measured ~5 % faster than after it)
+        if (c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);
         compute(c, slot);
-        if ((flags & 1) && c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);
         if (c < last) fi_wait_windows<K>(min(c + D, last) - (c + 1));
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
@@ -238,11 +219,11 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
 //    16-byte aligned, starts on a multiple of four columns and is staged in 16-byte units (K counts units per thread): a
 //    quarter of the DMA instructions.  Same window contents, same tap reads, same bits.  With the 64,000-byte ring of round 3
 //    the coarser units cost two ring slots and the launch 4-8 %; with 81,920 bytes (K = 2 units: four slots) it gains
-//    1.5-3 % on the smooth field and 5 % on the quarter field (tools/fi_variant_check.py --flags 0x8,0x10000008).
+//    1.5-3 % on the smooth field and 5 % on the quarter field (profiles/EXPERIMENTS.md).
 template <int K, bool B64, bool DMA16 = false>
 __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
                                                      int c_begin, int c_end, int tid, const FiWindow& win,
-                                                     const FiPixel (&px)[FI_PX], float* __restrict__ ring, int abl) {
+                                                     const FiPixel (&px)[FI_PX], float* __restrict__ ring) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     constexpr int EPT = DMA16 ? 4 : 1;                      // floats per staged element
     constexpr int NP = K * FI_THREADS * EPT;
@@ -283,7 +264,6 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     const int last = c_end - 1;
     const float* pdma = img + (int64_t)c_begin * cs;            // plane the next window is staged from
     float* pout = out + (int64_t)c_begin * cs;                  // plane the next results go to
-    int alias_in = 0, alias_out = 0;                            // (development: abl bits 6 / 7 keep the planes read / written inside 16)
     // 16-byte-staging instances: ONE descriptor per tensor, the plane in the instruction's scalar offset -- one scalar add per
     // channel and tensor instead of a 64-bit pointer add and a descriptor rebuild (a fifth of the loop's scalar instructions;
     // 2 % of the C=196 launch).  The descriptor spans 2^31 - 1 bytes from its base; when the next plane would end beyond that
@@ -304,7 +284,6 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             sin = 0;
         }
         sin += cs4;
-        if ((abl & 64) && (++alias_in & 15) == 0) sin -= 16 * cs4;
     };
     auto next_out = [&]() {                                    // (the skewed loop still stores to the plane before: offset sout - cs4 >= 0)
         if (__builtin_expect(sout > soff_max, 0)) {
@@ -314,22 +293,18 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             sout = 0;
         }
         sout += cs4;
-        if ((abl & 128) && ++alias_out == 16) { alias_out = 1; sout -= 15 * cs4; }
     };
     constexpr unsigned SLOT = NP * 4, RING = R * SLOT;       // bytes
     auto issue = [&](unsigned slot) {                           // (slots by their byte offset in the ring: one scalar add per step instead of a multiply)
         const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, plane_bytes, 0x00020000);
         float* l = ring + (slot >> 2) + wave_first * EPT;
-        if (!(abl & 2)) {
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                if constexpr (ONE) __builtin_amdgcn_raw_ptr_buffer_load_lds(din, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], sin, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], 0, 0, 0);
-            }
+        for (int k = 0; k < K; ++k) {
+            if constexpr (ONE) __builtin_amdgcn_raw_ptr_buffer_load_lds(din, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], sin, 0, 0);
+            else __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], 0, 0, 0);
         }
         if constexpr (ONE) { next_in(); return; }
         pdma += cs;
-        if ((abl & 64) && (++alias_in & 15) == 0) pdma -= 16 * cs;
     };
 #define FI_READ2(dst, addr, o0, o1) asm volatile("ds_read2_b32 %0, %1 offset0:" #o0 " offset1:" #o1 : "=v"(dst) : "v"(addr))
 #define FI_READ64(dst, addr, o) asm volatile("ds_read_b64 %0, %1 offset:" #o : "=v"(dst) : "v"(addr))
@@ -341,13 +316,9 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         constexpr int NQ = B64 ? 12 : 8;                    // register pairs per pixel
         constexpr int PART0 = B64 ? 3 : 4;                  // reads in the first part
         v2f q[2][NQ];
-        if (abl & 4) {
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) { q[0][i] = v2f{(float)i, 1.0f}; q[1][i] = v2f{2.0f, (float)i}; }
-        }
-        auto reads = [&](auto P, auto H) {
+        // (explicit captures: with [&] the allocator spills 4 more bytes per thread in the kernel's prologue)
+        auto reads = [&q, &lb, so, pitch4](auto P, auto H) {
             constexpr int p = decltype(P)::value, h = decltype(H)::value;
-            if (abl & 4) return;
             v2f (&d)[NQ] = q[p & 1];
             if constexpr (B64) {
                 if constexpr (h == 0) {
@@ -404,10 +375,8 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
                 bot = __builtin_elementwise_fma(d[7], F[p][7], bot);
                 val = blend4(px[p].alpha, px[p].beta, top.x, top.y, bot.x, bot.y);
             }
-            if (!(abl & 1) || val == 123456.789f) {
-                if constexpr (ONE) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout, 0);
-                else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), oplane, soff[p], 0, 0);
-            }
+            if constexpr (ONE) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout, 0);
+            else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), oplane, soff[p], 0, 0);
         };
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
@@ -422,7 +391,6 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         });
         if constexpr (ONE) { next_out(); return; }
         pout += cs;
-        if ((abl & 128) && ++alias_out == 16) { alias_out = 1; pout -= 15 * cs; }    // (planes 1 .. 15 after the first lap: the skewed store reaches one plane back)
     };
     // Two pixels, 4-byte reads: the pipeline is skewed by one pixel across the barrier.  In channel c a wave issues pixel 0's
     // reads, multiplies pixel 1 of channel c - 1 (its taps were read before the barrier and wait in registers), issues pixel
@@ -492,9 +460,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         arrived_s(qb, std::integral_constant<int, 0>{});
         if constexpr (ONE) { next_out(); return; }
         pout += cs;
-        if ((abl & 128) && ++alias_out == 16) { alias_out = 1; pout -= 15 * cs; }    // (planes 1 .. 15 after the first lap: the skewed store reaches one plane back)
     };
-    const bool skew = SKEW && !(abl & 32);
     // prologue: the first D windows
     const int n0 = min(D, c_end - c_begin);
     // (The waits count staging loads only.  vmcnt also holds the FI_PX result stores of every step, in issue order, so "all but
@@ -506,31 +472,14 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     __builtin_amdgcn_s_barrier();                               // ... in every wave
     int c = c_begin;
     unsigned slot = 0, freed = RING - SLOT;                      // the window being read; the slot every wave finished reading before the last barrier
-    if constexpr (SKEW) if (skew) {
-#ifdef FI_STAMPS
-        unsigned long long acc_i = 0, acc_c = 0, acc_w = 0, acc_b = 0, acc_n = 0;
-#endif
+    if constexpr (SKEW) {
         for (; c + D <= last; ++c) {
-            FI_T(t0);
             issue(freed);
-            FI_T(t1);
             compute_skewed(slot, c == c_begin);
-            FI_T(t2);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * K) : "memory");
-            FI_T(t3);
             __builtin_amdgcn_s_barrier();
-#ifdef FI_STAMPS
-            const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-            acc_i += t1 - t0; acc_c += t2 - t1; acc_w += t3 - t2; acc_b += t4 - t3; acc_n += 1;
-#endif
             freed = slot; slot = (slot + SLOT == RING) ? 0u : slot + SLOT;
         }
-#ifdef FI_STAMPS
-        if ((tid & 63) == 0) {
-            atomicAdd(&g_fi_stamps[0], acc_i); atomicAdd(&g_fi_stamps[1], acc_c); atomicAdd(&g_fi_stamps[2], acc_w);
-            atomicAdd(&g_fi_stamps[3], acc_b); atomicAdd(&g_fi_stamps[4], acc_n);
-        }
-#endif
         for (; c <= last; ++c) {
             compute_skewed(slot, c == c_begin);
             if (c < last) {
@@ -544,8 +493,8 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     for (; c + D <= last; ++c) {                                // steady state: window c + D exists
         issue(freed);
         compute(slot);
-        if (!(abl & 16)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * K) : "memory");      // all but the D - 1 youngest windows: c + 1 has landed
-        if (!(abl & 8)) __builtin_amdgcn_s_barrier();
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * K) : "memory");     // all but the D - 1 youngest windows: c + 1 has landed
+        __builtin_amdgcn_s_barrier();
         freed = slot; slot = (slot + SLOT == RING) ? 0u : slot + SLOT;
     }
     for (; c <= last; ++c) {                                    // the last D channels: nothing left to stage
@@ -564,55 +513,34 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             for (int cc = c_begin; cc < c_end; ++cc) out[(int64_t)cc * cs + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
 }
 
-// two 512-thread workgroups per CU (4 waves per SIMD): at most 128 VGPRs
-template <bool BLEND, int MODE>
-#ifndef FI_WAVES
-#define FI_WAVES (8 / FI_PX)                        // waves per SIMD the kernel must fit (4: two 512-thread workgroups per CU)
-#endif
+// two 512-thread workgroups per CU (4 waves per SIMD): at most 128 VGPRs.
+// aligned16 (set by the host): width, strides and base of in1 are multiples of 16 bytes, and two planes lie within 2^31 bytes.
+template <bool BLEND>
 __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     float* __restrict__ out, int channel, int h, int w,
     vfi_strides s1, vfi_strides s2, vfi_strides s3,
-    int tiles_x, int tiles_y, int ntiles, int per_xcd, int ch_per_group, int flags, FiBlend blend) {
+    int tiles_x, int tiles_y, int ntiles, int ch_per_group, int aligned16, FiBlend blend) {
     // ONE LDS array (a second __shared__ object beside an LDS-DMA target makes hipcc drain vmcnt
     // before LDS reads): 16-float header holding the bounding box, then the window ring
     __shared__ float lds[FI_HDR + FI_RING_FLOATS];
     int* box = reinterpret_cast<int*>(lds);
 
-    // ---- block -> tile (XCD-contiguous bands)
+    // ---- block -> tile
     const int bid = blockIdx.x;
     // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and a tile's window rows share
-    // their first and last 128-byte line with the horizontal neighbours' windows.  Default: G = 4 horizontally
+    // their first and last 128-byte line with the horizontal neighbours' windows.  G = 4 horizontally
     // consecutive tiles go to ONE XCD (workgroups b, b + 8, b + 16, b + 24 share an XCD and start together), so
     // three of four shared lines are L2 hits: EA read requests per C=196 launch 39.1 M -> 31.2 M (5.0 -> 4.0 GB),
     // 1-9 % less time depending on the box.  Larger departures from raster order lose more than they save:
-    // XCD-contiguous bands +12 % time, 4x2 / 2x2 tile blocks per XCD -25 % reads but +15-30 % time
-    // (tools/fi_xcd_exp.sh).  The other mappings remain selectable in a development build.
-    int tile = (flags & 2) ? (bid % FI_XCDS) * per_xcd + bid / FI_XCDS : bid;
-    if ((flags >> 2) & 3) {
-        const int G = 1 << ((flags >> 2) & 3);
-        const int xs = bid % FI_XCDS, k = bid / FI_XCDS;
-        tile = ((k / G) * FI_XCDS + xs) * G + (k % G);
-    }
-    int b, tyi, txi;
-    if (flags & 48) {
-        // experiment: GW x GH tiles per XCD (flags bit 4: 4 x 2, bit 5: 2 x 2)
-        const int GW = (flags & 16) ? 4 : 2, GH = 2, GN = GW * GH;
-        const int xs = bid % FI_XCDS, k = bid / FI_XCDS;
-        const int j = (k / GN) * FI_XCDS + xs, m = k % GN;
-        const int gpr = (tiles_x + GW - 1) / GW, gpc = (tiles_y + GH - 1) / GH;
-        b = j / (gpr * gpc);
-        const int jr = j - b * (gpr * gpc);
-        const int gy = jr / gpr, gx = jr - gy * gpr;
-        txi = gx * GW + m % GW;
-        tyi = gy * GH + m / GW;
-        if (txi >= tiles_x || tyi >= tiles_y || b * tiles_x * tiles_y >= ntiles) return;
-    } else {
-        if (tile >= ntiles) return;                         // whole workgroup leaves together
-        b = tile / (tiles_x * tiles_y);
-        const int trem = tile - b * (tiles_x * tiles_y);
-        tyi = trem / tiles_x; txi = trem - tyi * tiles_x;
-    }
+    // XCD-contiguous bands +12 % time, 4x2 / 2x2 tile blocks per XCD -25 % reads but +15-30 % time.
+    constexpr int G = 4;
+    const int xs = bid % FI_XCDS, k = bid / FI_XCDS;
+    const int tile = ((k / G) * FI_XCDS + xs) * G + (k % G);
+    if (tile >= ntiles) return;                             // whole workgroup leaves together
+    const int b = tile / (tiles_x * tiles_y);
+    const int trem = tile - b * (tiles_x * tiles_y);
+    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
     const int c_begin = blockIdx.y * ch_per_group;
     const int c_end = min(channel, c_begin + ch_per_group);
 
@@ -676,24 +604,23 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     }
     __syncthreads();
     const bool any_valid = box[0] != INT_MAX;
-    // MODE 0 (the product): the lean channel loop (the plain one under a blend epilogue), tap reads chosen per tile: a tall or
+    // The lean channel loop (the plain one under a blend epilogue), tap reads chosen per tile: a tall or
     // wide bounding box marks a rough flow field, where the lanes of a wave sit on many window rows and columns and LDS bank
     // conflicts dominate -- there the aligned 8-byte reads win (C=196 on the "quarter" field: 1.77 -> 1.61 ms; all tiles on
     // them: 1.58); on a smooth field they lose 3-10 % to their 16 selects per pixel and channel, and its tiles keep the
-    // 4-byte reads.  Development builds: 1 = the plain loop, 2 = 8-byte reads everywhere, 3 = 4-byte reads everywhere.
+    // 4-byte reads.
     const int raw_bh = any_valid ? box[3] - box[1] + 1 : 0;
     const int raw_bw = any_valid ? box[2] - box[0] + 1 : 0;
-    constexpr bool lean = !BLEND && MODE != 1;
+    constexpr bool lean = !BLEND;
     // (the 8-byte layout's pitch is = 32 mod 64 floats: a window that needs more than 10 x 512 elements with it keeps the
     //  4-byte reads and their tighter pitch -- the two largest ring geometries are compiled for those only)
-    // 16-byte staging (flags bit 28; bit 29, set by the host: width, strides and base of input1 are multiples of 16 bytes):
-    // every column of the window inside the image, rows of the tensor 16-byte aligned; the
+    // 16-byte staging (aligned16): every column of the window inside the image, rows of the tensor 16-byte aligned; the
     // window then starts on a multiple of four columns (which is even: the 8-byte reads' parity rule holds too)
-    const bool can16 = lean && MODE != 1 && (flags & (3 << 28)) == (3 << 28) && any_valid && box[0] >= 0 && box[2] < w;
+    const bool can16 = lean && aligned16 && any_valid && box[0] >= 0 && box[2] < w;
     const int lo = can16 ? (box[0] & ~3) : box[0];
     const int bw64 = any_valid ? box[2] - (lo & ~1) + 1 : 0;
     const bool fits64 = ((((bw64 + 31) >> 6) << 6) + 32) * raw_bh <= 10 * FI_KS * FI_THREADS;
-    const bool use64 = lean && (MODE == 2 || (MODE == 0 && fits64 && (raw_bh >= FI_B64_MIN_BH || raw_bw >= FI_B64_MIN_BW)));
+    const bool use64 = lean && fits64 && (raw_bh >= FI_B64_MIN_BH || raw_bw >= FI_B64_MIN_BW);
     const int bx0 = (use64 && any_valid) ? (lo & ~1) : lo, by0 = box[1];       // 8-byte reads: window columns keep the image's parity
     const int bw = any_valid ? box[2] - bx0 + 1 : 0;
     const int bh = raw_bh;
@@ -735,18 +662,16 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
 
     const FiWindow win{bx0, by0, bw, bh, pitch, h, w, (int)s1.h};
     float* ring = lds + FI_HDR;
-#define FI_RUN(K) if constexpr (lean && MODE == 0) { \
-        if constexpr ((K) <= 10 * FI_KS) { if (use64) fi_run_channels_lean<K, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, FI_ABL(flags)); } \
-        if (!use64) fi_run_channels_lean<K, false>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, FI_ABL(flags)); \
-    } else if constexpr (lean) fi_run_channels_lean<K, MODE == 2>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, FI_ABL(flags)); else \
-                  fi_run_channels<K, BLEND>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, \
-                                     min(((flags >> 8) & 255) ? ((flags >> 8) & 255) : FI_RMAX, FI_RING_FLOATS / ((K) * FI_THREADS)), flags, bl)
-    if constexpr (lean && MODE != 1) {
+#define FI_RUN(K) if constexpr (lean) { \
+        if constexpr ((K) <= 10 * FI_KS) { if (use64) fi_run_channels_lean<K, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); } \
+        if (!use64) fi_run_channels_lean<K, false>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); \
+    } else fi_run_channels<K, BLEND>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, bl)
+    if constexpr (lean) {
         // (units of four floats: two or three per thread cover the windows of smooth fields; larger ones stay on 4-byte staging)
         const int k16 = (n + 4 * FI_THREADS - 1) / (4 * FI_THREADS);
         if (can16 && k16 <= 3) {
-#define FI_RUN16(K) { if (use64) fi_run_channels_lean<K, true, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, FI_ABL(flags)); \
-                      else fi_run_channels_lean<K, false, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, FI_ABL(flags)); }
+#define FI_RUN16(K) { if (use64) fi_run_channels_lean<K, true, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); \
+                      else fi_run_channels_lean<K, false, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); }
             if (k16 <= 1) FI_RUN16(1) else if (k16 == 2) FI_RUN16(2) else FI_RUN16(3)
 #undef FI_RUN16
             return;
@@ -761,41 +686,19 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     else if (kmax <= 8 * FI_KS) FI_RUN(8 * FI_KS);
     else if (kmax <= 10 * FI_KS) FI_RUN(10 * FI_KS);
     else if (kmax <= 12 * FI_KS) FI_RUN(12 * FI_KS);
-#if FI_RING_FLOATS >= 2 * 15 * FI_KS * FI_THREADS
     else FI_RUN(15 * FI_KS);
-#endif
 #undef FI_RUN
 }
 
-// (explicit: with the 16-byte flavours added, hipcc 7.2 silently left the host stubs of the implicitly instantiated modes 0
-//  and 3 of a development build undefined)
-#define FI_INSTANCE(B, M) template __global__ void fi_forward_ori_lds<B, M>(const float* __restrict__, const float* __restrict__, \
-    const float* __restrict__, float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, int, FiBlend)
-FI_INSTANCE(true, 0);
-FI_INSTANCE(false, 0);
-#ifdef VFI_DEV
-FI_INSTANCE(false, 1);
-FI_INSTANCE(false, 2);
-FI_INSTANCE(false, 3);
-#endif
-#undef FI_INSTANCE
+// (explicit: hipcc 7.2 has silently left the host stubs of implicitly instantiated flavours of this kernel undefined)
+template __global__ void fi_forward_ori_lds<true>(const float* __restrict__, const float* __restrict__, const float* __restrict__,
+    float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, FiBlend);
+template __global__ void fi_forward_ori_lds<false>(const float* __restrict__, const float* __restrict__, const float* __restrict__,
+    float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, FiBlend);
 
 }  // namespace vfi
 
 using namespace vfi;
-
-// Kernel flags: bit 0 issue the next DMA before / after the compute phase (plain loop); bit 1 XCD-contiguous bands of tiles;
-// bits 16-17 channel loop (development builds: 1 plain, 2 / 3 lean with 8- / 4-byte tap reads everywhere); bits 20-25 parts of the lean loop
-// switched off (development builds, timing only);
-// bit 28 16-byte staging where a window allows it (bit 29 is set by the host: input1's rows and planes 16-byte aligned);
-// bits 2-3 log2 of the tiles per XCD group (default 2: four horizontally consecutive tiles on one XCD, see the
-// kernel); bits 4-5 two-dimensional groups; bits 8.. ring depth.  g_fi_groups: channel groups, 0 = chosen below.
-#define FI_DEFAULT_FLAGS (8 | (1 << 28))            // four tiles per XCD group; 16-byte staging where a window allows it
-VFI_KNOB(int, g_fi_flags, FI_DEFAULT_FLAGS);
-VFI_KNOB(int, g_fi_groups, 0);
-#ifdef VFI_DEV
-extern "C" void vfi_dev_filterinterp(int flags, int groups) { g_fi_flags = flags; g_fi_groups = groups; }
-#endif
 
 // returns -1 when this path does not apply (caller uses the direct kernel)
 static int forward_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
@@ -806,54 +709,28 @@ static int forward_ori_lds(const float* input1, const float* input2, const float
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
     if (nt > (1 << 28)) return -1;
     const int ntiles = (int)nt;
-    const int per_xcd = (((ntiles + FI_XCDS - 1) / FI_XCDS) + 7) & ~7;         // (a multiple of 8: the tile-group experiments)
+    const int per_xcd = (((ntiles + FI_XCDS - 1) / FI_XCDS) + 7) & ~7;         // (a multiple of 8: whole groups of four tiles)
 
     // split the channel range over blockIdx.y when that shortens the tail: two workgroups per
     // CU run at a time; every extra group re-reads the flow + 16 filter planes (72 B/pixel)
     // next to 8 B/pixel/channel of image traffic
     int best_groups = fi_channel_groups(ntiles, channel, 4.3);
-    if (g_fi_groups > 0) best_groups = g_fi_groups < channel ? g_fi_groups : channel;
     if (blend.out) best_groups = 1;                         // (the blend epilogue keeps a pixel's channels in one workgroup)
     const int ch_per_group = (channel + best_groups - 1) / best_groups;
     const int groups = (channel + ch_per_group - 1) / ch_per_group;
 
-    int grid_x = per_xcd * FI_XCDS;
-    if (g_fi_flags & 48) {
-        const int GW = (g_fi_flags & 16) ? 4 : 2, GH = 2;
-        const int ngroups = ((tiles_x + GW - 1) / GW) * ((tiles_y + GH - 1) / GH) * batch;
-        grid_x = ((ngroups + FI_XCDS - 1) / FI_XCDS) * FI_XCDS * GW * GH;
-    }
-    const dim3 grid((unsigned)grid_x, (unsigned)groups, 1);
+    const dim3 grid((unsigned)(per_xcd * FI_XCDS), (unsigned)groups, 1);
     // (16-byte staging: rows of input1 on 16-byte boundaries; its single-descriptor addressing: two planes within 2^31 bytes)
     const int aligned16 = !(w & 3) && !(s1.h & 3) && !(s1.c & 3) && !(s1.b & 3) && !((uintptr_t)input1 & 15) &&
                           s1.c > 0 && 4 * s1.c + 4 * ((int64_t)(h - 1) * s1.h + w) < 0x7fffffffLL;
-    const int kflags = g_fi_flags | (aligned16 << 29);
     if (blend.out)
-        hipLaunchKernelGGL((fi_forward_ori_lds<true, 0>), grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, per_xcd, ch_per_group, kflags, blend);
-#ifdef VFI_DEV
-#define FI_DEV_MODE(M) hipLaunchKernelGGL((fi_forward_ori_lds<false, M>), grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2, \
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, per_xcd, ch_per_group, kflags, blend)
-    else if (((g_fi_flags >> 16) & 3) == 1) FI_DEV_MODE(1);   // the plain channel loop
-    else if (((g_fi_flags >> 16) & 3) == 2) FI_DEV_MODE(2);   // the lean loop with 8-byte tap reads
-    else if (((g_fi_flags >> 16) & 3) == 3) FI_DEV_MODE(3);   // the lean loop with 4-byte tap reads only
-#undef FI_DEV_MODE
-#endif
+        hipLaunchKernelGGL(fi_forward_ori_lds<true>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
+                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group, aligned16, blend);
     else
-        hipLaunchKernelGGL((fi_forward_ori_lds<false, 0>), grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, per_xcd, ch_per_group, kflags, blend);
+        hipLaunchKernelGGL(fi_forward_ori_lds<false>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
+                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group, aligned16, blend);
     return launch_status();
 }
-
-#ifdef FI_STAMPS
-// reads the accumulators and clears them (synchronises)
-extern "C" int vfi_dev_fi_stamps(unsigned long long* host8) {
-    if (hipDeviceSynchronize() != hipSuccess) return VFI_ERR_LAUNCH;
-    if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(g_fi_stamps), sizeof(unsigned long long) * 8) != hipSuccess) return VFI_ERR_LAUNCH;
-    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_fi_stamps), zero, sizeof(zero)) == hipSuccess ? VFI_OK : VFI_ERR_LAUNCH;
-}
-#endif
 
 extern "C" int vfi_filterinterp_forward_ori_lds(const float* input1, const float* input2, const float* input3,
                                                  float* output, int batch, int channel, int h, int w,

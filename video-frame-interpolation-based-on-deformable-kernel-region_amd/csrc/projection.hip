@@ -51,10 +51,6 @@
 #include "bitwalk.h"
 #include "workspace.h"
 
-#ifndef PROJ_DEV_SKIP
-#define PROJ_DEV_SKIP 0
-#endif
-
 #include <limits.h>
 
 #include <type_traits>
@@ -204,16 +200,9 @@ __device__ __forceinline__ bool pix_target(float fx, float fy, int x, int y, uns
 // K0, K1 and K2 alike, so the flow K0 has just read is in the L2 that K1's workgroups read their source
 // rectangles through, and the counts, flows and bitmaps K1 writes are in the L2 K2 searches them through.  A
 // bijection of [0, n) for every n.
-#ifndef PROJ_BANDS
-#define PROJ_BANDS 1
-#endif
 __device__ __forceinline__ int band_item(int bid, int n) {
-#if PROJ_BANDS
     const int x = bid & 7, k = bid >> 3, base = n >> 3, rem = n & 7;
     return x * base + min(x, rem) + k;
-#else
-    return bid;
-#endif
 }
 
 // min / max over each row of 16 lanes (four DPP row_shr steps); the result is in lane 15 of the row
@@ -407,9 +396,6 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
                 }
             }
         }
-#if PROJ_DEV_SKIP == 6      // (development: K0 = its loads and per-pixel arithmetic only)
-    if (dlmin != 12345) { if (vbits == 0x7fffffff) ws[4] = dlmax + dtmin + dtmax + cbits + mbits; return; }
-#endif
     // a block is four lanes wide
     dlmin = quad_min(dlmin); dlmax = quad_max(dlmax); dtmin = quad_min(dtmin); dtmax = quad_max(dtmax);
     vbits = quad_max(vbits); cbits = quad_max(cbits); mbits = quad_max(mbits); fbits = quad_max(fbits);
@@ -431,9 +417,6 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
         const int bx0 = gxi * 4 * PROJ_TW + k * PROJ_BLK, bx1 = min(bx0 + PROJ_BLK - 1, g.w - 1), by1 = min(y0 + PROJ_BLK - 1, g.h - 1);
         const int dlmin_ = e[0], dlmax_ = e[1], dtmin_ = e[2], dtmax_ = e[3];
         const bool any = dlmin_ != INT_MAX && bx0 < g.w;
-#if PROJ_DEV_SKIP == 5      // (development: K0 without its scatter)
-        if (dlmin_ != 12345) return;
-#endif
         // top-left targets of the block lie in [X0, X1] x [Y0, Y1]; a target (L, T) feeds columns L, L + 1, rows T, T + 1
         const int X0 = max(bx0 + dlmin_, 0), X1 = min(bx1 + dlmax_, g.w - 1);
         const int Y0 = max(y0 + dtmin_, 0), Y1 = min(by1 + dtmax_, g.h - 1);
@@ -503,7 +486,7 @@ template <> struct ProjCountCell<true> { typedef unsigned long long type; };    
 // Workgroup size: every tile costs the same and all start within a microsecond, so what matters is that ALL
 // tiles are resident at once (a 1080p frame has 2232 tiles; 8 workgroups of 256 threads per CU would hold
 // 2048 and leave a second round).  128 threads per tile: 9 workgroups per CU within the LDS.
-// Memory: the kernel is bound by the memory system (in-kernel stamps, tools/proj_stamps.py: the later a
+// Memory: the kernel is bound by the memory system (in-kernel stamps: the later a
 // workgroup's requests are queued, the longer it lives), so the flow is read and count / output are written
 // with 16-byte lanes: a lane owns four consecutive pixels.
 #ifndef PROJ_PULL_THREADS
@@ -601,11 +584,7 @@ __device__ __forceinline__ void pull_add(unsigned long long* accv, typename Proj
         valid = valid && mine == cls;
     }
     const unsigned c = (unsigned)(L - cx), r = (unsigned)(T - cy);
-#if defined(PROJ_STAMPS) && PROJ_DEV_SKIP == 3
-    if (valid && on && c < PROJ_AW && r < PROJ_AH && svx == 12345.0f) {
-#else
     if (valid && on && c < PROJ_AW && r < PROJ_AH) {
-#endif
         // addend * 2^k is exact in float (power-of-two scale)
         const float ax = DEPTH ? d * fx : fx, ay = DEPTH ? d * fy : fy;        // (:75-88; depth :74-91)
         atomicAdd(&accv[r * PROJ_VS + c], pack2(__float2int_rn(ax * svx), __float2int_rn(ay * svy)));
@@ -634,10 +613,6 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);    // (provably wave-uniform: scalar row offsets)
     const int ox0 = txi * PROJ_TW, oy0 = tyi * PROJ_TH;
     const bool fallback = ws[PROJ_WS_FLAG] != 0;
-#ifdef PROJ_STAMPS          // development build only: when and where each workgroup ran (tools/proj_stamps.py)
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_t1 = 0, st_t2 = 0;
-#endif
     if (tile == 0 && tid == 0) {
         ws[PROJ_WS_DIRTY] = fallback ? (int)(unsigned)(plane_floats & 0xffffffffll) : 0;
         ws[PROJ_WS_DIRTY + 1] = fallback ? (int)(plane_floats >> 32) : 0;
@@ -657,9 +632,6 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     for (int i = tid; i < ProjLds<DEPTH>::total / 16; i += PROJ_PULL_THREADS) lds[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
     if (tid < 8) entry[tid] = 0;                            // every thread has read the record: empty for the next call
-#ifdef PROJ_STAMPS
-    const unsigned long long st_ta = __builtin_amdgcn_s_memtime() + (e0 & 0);      // (after the record has arrived)
-#endif
 
     const int ux0 = 32767 - e0, uy0 = 32767 - e1;
     const int uw = e2 - ux0, uh = e2 > 0 ? e3 - uy0 : 0;    // uh == 0: nothing lands here
@@ -750,11 +722,7 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
             }
         } else {
             const int ux0a = ux0 & ~3;                                      // quads start at multiples of four pixels
-#if defined(PROJ_STAMPS) && PROJ_DEV_SKIP == 1
-            const int nq = 0;
-#else
             const int nq = uh > 0 ? (ux0 + uw - 1 - ux0a) / 4 + 1 : 0;      // quads per row
-#endif
             for (int cs = 0; cs < nq; cs += 64) {
                 const int width = min(64, nq - cs), rpi = 64 / width;
                 const int lr = lane / width, lc = lane - lr * width;
@@ -786,9 +754,6 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
                 }
             }
         }
-#ifdef PROJ_STAMPS
-        if (!attempt) st_t1 = __builtin_amdgcn_s_memtime();
-#endif
         __syncthreads();
         if (attempt) break;
         // did every cell stay within the addends its 32-bit halves can hold?
@@ -854,9 +819,6 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
         __syncthreads();
         run_class(std::false_type{}, cls);
     }
-#ifdef PROJ_STAMPS
-    st_t2 = __builtin_amdgcn_s_memtime();
-#endif
 
     // normalise (flowprojection_cuda_kernel.cu:129-134) and write the tile once, 16 bytes per lane; leave the two
     // "count != 0" bitmaps for the hole filler and put the tile on its list if it has holes
@@ -884,11 +846,7 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
             if (DEPTH && inside && c < 0.0f) negs += 1;
         }
         if (nzb) atomicOr(&s_rowbits[yl * 2 + (q >> 3)], nzb << ((q & 7) * 4));
-#if defined(PROJ_STAMPS) && PROJ_DEV_SKIP == 2
-        if (y < g.h && ncls == 12345) {
-#else
         if (y < g.h) {
-#endif
             const int so0 = (oy0 + it * 4 * PROJ_NW + wave * 4) * oh * 4, soc = (oy0 + it * 4 * PROJ_NW + wave * 4) * ch * 4;
             const int vo = (rw * oh + xq) * 4, voc = (rw * ch + xq) * 4;
             if (vec_ok && xq + 3 < g.w) {
@@ -913,17 +871,6 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     if (negs) atomicAdd(&s_misc[2], negs);
     __syncthreads();
     pull_bitmaps<PROJ_PULL_THREADS>(g, ws, bits, s_rowbits, s_misc, b, txi, tyi, ox0, oy0, tile, tid);
-#ifdef PROJ_STAMPS
-    if (tid == 0) {
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(ws + g.off_list + g.ntiles + (g.ntiles & 1)) + (int64_t)tile * 8;
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        st[0] = st_t0; st[1] = st_t1; st[2] = st_t2; st[3] = __builtin_amdgcn_s_memtime();
-        st[4] = st_r0; st[5] = __builtin_amdgcn_s_memrealtime(); st[6] = hwid; st[7] = (unsigned long long)xcc | ((st_ta - st_t0) << 8);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -931,8 +878,8 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
 // called with.  Same tile and same grid of exact integer sums as proj_pull, written for the fewest instructions per
 // pixel, because that is what bounds the kernel: all 2232 tiles of a 1080p frame are resident at once, 4.5 waves per
 // SIMD, and a wave of proj_pull executes ~2000 vector instructions for its ~11 source and 8 output pixels per lane
-// (SQ_INSTS_VALU; the workgroups dispatched first finish first -- age-ordered issue -- which is what the in-kernel
-// stamps show: tools/proj_stamps.py).  Here:
+// (SQ_INSTS_VALU; the workgroups dispatched first finish first -- age-ordered issue -- which is what in-kernel
+// stamps showed).  Here:
 //  * a source pixel is tested ONCE: "valid target" (0 <= x2 <= w - 1) and "target inside this tile's grid" are one
 //    interval per axis, tested on the float's bits (non-negative floats order like their bit patterns: one subtract, one
 //    unsigned compare).  No lane predicates beside it: lanes past the frame or past the strip carry NaN coordinates,
@@ -1005,34 +952,22 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     char* const lbase = reinterpret_cast<char*>(lds);
     unsigned* s_rowbits = reinterpret_cast<unsigned*>(lbase + LY::planes);            // [16][2]
     int* s_misc = reinterpret_cast<int*>(s_rowbits + 2 * PROJ_TH);                    // [0] most addends in a cell, [1] holes, [2] negative counts
-#if PROJ_BANDS
     const int tile = band_item(blockIdx.x, gridDim.x);
     const int per_img = g.tiles_x * g.tiles_y;
     const int b = tile / per_img;
     const int trem = tile - b * per_img;
     const int tyi = trem / g.tiles_x, txi = trem - tyi * g.tiles_x;
-#else
-    const int txi = blockIdx.x, tyi = blockIdx.y, b = blockIdx.z;
-    const int tile = (b * g.tiles_y + tyi) * g.tiles_x + txi;
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ox0 = txi * PROJ_TW, oy0 = tyi * PROJ_TH;
     int* entry = ws + g.off_tile + (int64_t)tile * PROJ_TILE_WORDS;
     // the record and the fallback word through the scalar cache (invalidated at kernel start; K0 wrote them by atomics)
-#ifdef PROJ_STAMPS          // development build only: when and where each workgroup ran (tools/proj_stamps.py)
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long st_t1 = 0, st_t2 = 0;
-#endif
     pl_v8i rec;
     int fb_word;
     asm volatile("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0" : "=&s"(rec), "=&s"(fb_word) : "s"(entry), "s"(ws + PROJ_WS_FLAG) : "memory");
     for (int i = tid; i < LY::total / 16; i += PL_THREADS) lds[i] = make_uint4(0u, 0u, 0u, 0u);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rec), "+s"(fb_word) :: "memory");
     const bool fallback = fb_word != 0;
-#ifdef PROJ_STAMPS
-    const unsigned long long st_ta = __builtin_amdgcn_s_memtime();             // (after the record has arrived)
-#endif
     if (tile == 0 && tid == 0) {
         ws[PROJ_WS_DIRTY] = fallback ? (int)(unsigned)(plane_floats & 0xffffffffll) : 0;
         ws[PROJ_WS_DIRTY + 1] = fallback ? (int)(plane_floats >> 32) : 0;
@@ -1130,11 +1065,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
         constexpr int CH = PL_CH;
         const float svx = -ldexpf(1.0f, kvx), svy = -ldexpf(1.0f, kvy), scn = ldexpf(1.0f, kc);    // exact powers of two (the value addend is MINUS the flow)
         const int ux0a = ux0 & ~3;                                          // quads start at multiples of four pixels
-#if PROJ_DEV_SKIP == 1      // (development: timing of the kernel without its source walk)
-        const int nq = 0;
-#else
         const int nq = uh > 0 ? (ux0 + uw - 1 - ux0a) / 4 + 1 : 0;          // quads per row
-#endif
         for (int cs = 0; cs < nq; cs += 64) {
             // a strip of up to 64 quads; a narrower one packs 64 / width rows into a wave instruction
             const int width = min(64, nq - cs), rpi = 64 / width;
@@ -1155,7 +1086,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                     // (rows of the frame below the rectangle cannot reach the tile, rows below the frame read 0 and sit at
                     //  y > h - 1: both fail the interval test)
                     qx[k] = qy[k] = qd[k] = proj_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-                    if (row0 + k * step < uh && PROJ_DEV_SKIP != 4) {       // (wave-uniform)
+                    if (row0 + k * step < uh) {                             // (wave-uniform)
                         const int yu = uy0 + row0 + k * step;
                         qx[k] = buf_f32x4(pl.f0, vo, yu * src.fh * 4);
                         qy[k] = buf_f32x4(pl.f1, vo, yu * src.fh * 4);
@@ -1179,9 +1110,6 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                                     hit = hit && mine == cls;
                                 }
                             }
-#if PROJ_DEV_SKIP == 3
-                            hit = hit && svx == 12345.0f;
-#endif
                             if (hit) {
                                 const int L = (int)x2, T = (int)y2;
                                 const unsigned a = (unsigned)(__mul24(T, P) + L) * 8u + cell0;
@@ -1220,9 +1148,6 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
             const int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls))) - shift;
             const int kvy = max(-100, min(100, PROJ_ADD_BITS - (efy + ec - PROJ_CLS_BITS * cls))) - shift;
             accumulate(cls, kvx, kvy, kc);
-#ifdef PROJ_STAMPS
-            if (!attempt && !cls) st_t1 = __builtin_amdgcn_s_memtime();
-#endif
             __syncthreads();
 #pragma unroll
             for (int it = 0; it < PL_EPI; ++it) {
@@ -1299,9 +1224,6 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
         }
         if (holes) atomicAdd(&s_misc[1], holes);
         if (negs) atomicAdd(&s_misc[2], negs);
-#ifdef PROJ_STAMPS
-        if (!attempt) st_t2 = __builtin_amdgcn_s_memtime();
-#endif
         __syncthreads();
         const int busiest = s_misc[0];
         if (busiest <= PROJ_ADD_CELL || attempt) break;
@@ -1313,17 +1235,6 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
         __syncthreads();
     }
     pull_bitmaps<PL_THREADS>(g, ws, bits, s_rowbits, s_misc, b, txi, tyi, ox0, oy0, tile, tid);
-#ifdef PROJ_STAMPS
-    if (tid == 0) {
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(ws + g.off_list + g.ntiles + (g.ntiles & 1)) + (int64_t)tile * 8;
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        st[0] = st_t0; st[1] = st_t1; st[2] = st_t2; st[3] = __builtin_amdgcn_s_memtime();
-        st[4] = st_r0; st[5] = __builtin_amdgcn_s_memrealtime(); st[6] = hwid; st[7] = (unsigned long long)xcc | ((st_ta - st_t0) << 8);
-    }
-#endif
 }
 
 // K2: pass 3 (flowprojection_cuda_kernel.cu:175-231).  A cell read here is either a non-hole
@@ -1616,9 +1527,6 @@ static bool proj_geometry(int batch, int h, int w, ProjGeom* g, ProjSizes* z) {
     g->off_tile = PROJ_WS_HDR;
     g->off_list = g->off_tile + PROJ_TILE_WORDS * g->ntiles;
     z->words = (size_t)g->off_list + (size_t)nt;
-#ifdef PROJ_STAMPS
-    z->words += 2 + 16 * (size_t)nt;
-#endif
     z->plane_floats = (size_t)3 * batch * h * w;
     return true;
 }
@@ -1689,13 +1597,10 @@ static int project_forward_list(const float* const* flows, vfi_strides sf, const
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     // 16-byte stores need 16-byte aligned rows
     const int vec_ok = vec_out ? 1 : 0;
-#ifndef PROJ_NO_LEAN
     if (vec_in && vec_ok && g.tiles_y <= 65535 && images <= 65535)
-        hipLaunchKernelGGL((proj_pull_lean<DEPTH>), PROJ_BANDS ? dim3(g.ntiles) : dim3(g.tiles_x, g.tiles_y, images), dim3(PL_THREADS), 0, st, src, dst, g,
+        hipLaunchKernelGGL((proj_pull_lean<DEPTH>), dim3(g.ntiles), dim3(PL_THREADS), 0, st, src, dst, g,
                            (int64_t)s1.b, (int64_t)s1.c, (int)s1.h, (int64_t)sc.b, (int)sc.h, p.words, p.bits, p.planes, (int64_t)z.plane_floats);
-    else
-#endif
-    if (vec_in)
+    else if (vec_in)
         hipLaunchKernelGGL((proj_pull<DEPTH, true>), dim3(g.ntiles), dim3(PROJ_PULL_THREADS), 0, st, src, dst, g,
                            (int64_t)s1.b, (int64_t)s1.c, (int)s1.h, (int64_t)sc.b, (int)sc.h, vec_ok, p.words, p.bits, p.planes, (int64_t)z.plane_floats);
     else
@@ -1749,18 +1654,6 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void flow_upsample4(
 
 using namespace vfi;
 
-#ifdef PROJ_STAMPS
-extern "C" int vfi_dev_projection_stamps(int batch, int h, int w, vfi_stream_t stream, unsigned long long* host_out) {
-    ProjGeom g;
-    ProjSizes z;
-    if (!proj_geometry(batch, h, w, &g, &z)) return VFI_ERR_SHAPE;
-    ProjBuffers p;
-    if (!proj_buffers((hipStream_t)stream, z, &p)) return VFI_ERR_LAUNCH;
-    (void)hipDeviceSynchronize();
-    return hipMemcpy(host_out, p.words + g.off_list + g.ntiles + (g.ntiles & 1), (size_t)g.ntiles * 64, hipMemcpyDeviceToHost) == hipSuccess
-               ? VFI_OK : VFI_ERR_LAUNCH;
-}
-#endif
 
 extern "C" int vfi_projection_reserve(int batch, int h, int w, vfi_stream_t stream) {
     ProjGeom g;

@@ -63,22 +63,13 @@ inline dim3 pixel_grid(int w, int h, int batch) {
     return dim3((unsigned)((w + VFI_TX - 1) / VFI_TX), (unsigned)((h + VFI_TY - 1) / VFI_TY), (unsigned)batch);
 }
 
-// Development knobs: tunables that experiments (tools/) flip at run time exist only in a -DVFI_DEV build of the
-// library (make OUT=../lib_dev EXTRA=-DVFI_DEV); in the product they are compile-time constants and no setter is
-// exported, so no caller or thread can change kernel selection for another.
-#ifdef VFI_DEV
-#define VFI_KNOB(type, name, value) static type name = value
-#else
-#define VFI_KNOB(type, name, value) static constexpr type name = value
-#endif
-
 // compute units of the CURRENT device (cached per device id)
 int device_cu_count();
 // How many channel groups (blockIdx.y) the staged FilterInterpolation kernels split a tile's channel range into.
 // Cost of g groups, in channels: a workgroup pays `prologue` channels' worth before its first channel (flow, filter, bounding
 // box, first window); a launch leaves half a round of its slots (2 workgroups per CU) idle at the end on average; and the
 // more workgroups a slot runs, the better their unequal durations even out (they go to whichever slot frees first).
-// Fitted to launches timed in isolation (tools/fi_isolated.py; fs=4, 1080p, C=196: 1 group 1.12 ms, 2 1.00-1.03, 3 0.99,
+// Fitted to launches timed in isolation (fs=4, 1080p, C=196: 1 group 1.12 ms, 2 1.00-1.03, 3 0.99,
 // 4 1.00, 8 1.08).
 int fi_channel_groups(int ntiles, int channel, double prologue);
 
