@@ -281,6 +281,20 @@ int vfi_correlation_backward(const float* input1, const float* input2, const flo
                              int pad_size, int kernel_size, int max_displacement,
                              int stride1, int stride2,
                              vfi_stream_t stream);
+/* The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541):
+ * all five tensors IEEE half, dense NCHW, stride1 == 1 as for vfi_correlation_backward (same terms, windows and skips).
+ * at::Half arithmetic rounds to half after every operation: each term p = half(gradOutput * value); 32 partials
+ * s_l (l = 0..31, over tc = l, l+32, ...; for k > 1 the window rows outer, columns inner) accumulate IN HALF,
+ * s_l = half(s_l + p); then r = half(r + s_l) in order of l; gradInput = half(r / half(k*k*C)) -- the count itself
+ * rounded to half.  A term whose other-map tap lies in the zero padding is not skipped (it adds half(g * 0)).  Every
+ * element of both gradients is written (the positions the reference never visits as +0), so they need no zero fill;
+ * nothing is allocated: the call can be captured in a graph. */
+int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,
+                                 void* gradinput1, void* gradinput2,
+                                 int batch, int channel, int h, int w,
+                                 int pad_size, int kernel_size, int max_displacement,
+                                 int stride1, int stride2,
+                                 vfi_stream_t stream);
 
 /* ==== glue either side of the ops above: the reference does these with torch
  * built-ins and Python; here each is one launch.  No reference binding exists for them: the

@@ -58,6 +58,7 @@ SIGNATURES = {
     "vfi_correlation_forward_pair": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_forward_f16": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_backward_f16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     # glue either side of the ops
     "vfi_flow_upsample4": [_p, _p, _i, _i, _i, _i, _f, _f, Strides, Strides, _p],
     "vfi_flowprojection_forward_up4": [_p, _p, _p, _i, _i, _i, _f, _f, _i, Strides, Strides, Strides, _p],
@@ -529,6 +530,16 @@ def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_
     if input2.shape != input1.shape or \
             tuple(gradoutput.shape) != (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2):
         raise RuntimeError("correlation_backward: input2 / gradoutput do not match input1's shape and the output dimensions")
+    if input1.dtype == torch.float16:                       # the reference's at::Half instantiation (no conversion)
+        _dev(input1, torch.float16), _dev(input2, torch.float16), _dev(gradoutput, torch.float16)
+        g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
+        with torch.cuda.device(input1.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(input1.device).cuda_stream)
+            err = lib().vfi_correlation_backward_f16(_ptr(input1), _ptr(input2), _ptr(gradoutput), _ptr(g1), _ptr(g2), b, c,
+                                                     h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream)
+        if err != 0:
+            raise RuntimeError("CUDA call failed")
+        return g1, g2
     g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
     with torch.cuda.device(_dev(input1)):
         err = lib().vfi_correlation_backward(_ptr(input1), _ptr(input2), _ptr(gradoutput), _ptr(g1), _ptr(g2), b, c,

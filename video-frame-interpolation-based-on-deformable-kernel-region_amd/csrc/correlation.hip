@@ -871,6 +871,164 @@ __global__ __launch_bounds__(256) void corr_backward_k1(
     }
 }
 
+// The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541).
+// The terms, windows and skips are corr_backward's; the arithmetic is at::Half's, which goes through float and rounds back to
+// half after every operation: p = half(g * v), the 32 partials `__shared__ scalar_t prod_sum[32]` accumulate IN HALF,
+// r = half(r + s_l) for l = 0..31, gin = half(r / nelems_h) with nelems_h = half(k*k*C) (not the exact count above 2048).
+// float32 has 24 >= 2*11 + 2 significand bits, so float-then-round is the correctly rounded half operation: the products and
+// sums here are plain v_mul_f16 / v_add_f16 (never fused: -ffp-contract=off, no fma written), and the one division is done in
+// float on the two widened halves and rounded once.  A term whose other-map tap lies in the zero padding is NOT skipped: it
+// adds half(g * 0), which is NaN when g is inf or NaN.
+__device__ __forceinline__ __half corr_mean_f16(__half r, float nelems_h) {
+    float rf = __half2float(r);
+    asm volatile("" : "+v"(rf));        // (keeps the widening a v_cvt: nothing mixed-precision may be folded into the division)
+    return __float2half_rn(rf / nelems_h);
+}
+
+// any pad / k / md / stride2, stride1 == 1: one thread per gradient element
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward_f16(
+    const __half* __restrict__ other, const __half* __restrict__ gout, __half* __restrict__ gin,
+    int batch, int channel, int h, int w, int oc, int oh, int ow,
+    int pad, int kr, int md, int s2, int dr) {
+    const int64_t total = (int64_t)batch * channel * h * w;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int bx = (int)(gid % w);
+    const int by = (int)((gid / w) % h);
+    const int c = (int)((gid / ((int64_t)w * h)) % channel);
+    const int n = (int)(gid / ((int64_t)w * h * channel));
+    const int dsz = 2 * dr + 1;
+    const int y = by + pad, x = bx + pad;                   // padded coordinates
+    const __half* of = other + ((int64_t)n * channel + c) * h * w;
+    const __half* go = gout + (int64_t)n * oc * oh * ow;
+    const __half zero = __float2half_rn(0.0f);
+    const float nelems_h = __half2float(__float2half_rn((float)((2 * kr + 1) * (2 * kr + 1) * channel)));
+    bool any = SECOND;
+    if constexpr (!SECOND) {
+        const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
+        any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
+    }
+    if (!any) {
+        gin[gid] = zero;        // the binding zero-fills gradInput (correlation_cuda.cc:112-113)
+        return;
+    }
+    __half r = zero;
+    for (int l = 0; l < 32; ++l) {
+        __half s = zero;
+        for (int tc = l; tc < oc; tc += 32) {
+            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
+            int xmin, ymin, xmax, ymax, vy, vx;
+            if constexpr (SECOND) {
+                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
+                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
+                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
+                vy = y - j2 - pad; vx = x - i2 - pad;
+            } else {
+                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
+                vy = y + j2 - pad; vx = x + i2 - pad;
+            }
+            const __half val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? of[(int64_t)vy * w + vx] : zero;
+            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
+            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
+            const __half* g = go + (int64_t)tc * oh * ow;
+            for (int j = ymin; j <= ymax; ++j)
+                for (int i = xmin; i <= xmax; ++i) s = __hadd(s, __hmul(g[(int64_t)j * ow + i], val));
+        }
+        r = __hadd(r, s);
+    }
+    gin[gid] = corr_mean_f16(r, nelems_h);
+}
+
+// PWC-Net's configuration (k == 1, strides 1, pad == md == 4), modelled on corr_backward_k1: a workgroup owns 64x4 pixels and
+// stages the other map's 12x72 window per channel in LDS (double-buffered, zero padded); a lane owns TWO horizontally adjacent
+// pixels, whose 81 gradOutput values are 81 packed-half registers for all channels of the group.  Per channel a term is one
+// v_pk_mul_f16 and one v_pk_add_f16 for both pixels: the rounding is per half, so the bits are corr_backward_f16's.  The
+// partials run in the reference's order (tc = l, l + 32, l + 64, then r += s_l for l = 0..31).  A term the reference skips
+// (gradInput2, displaced position outside the frame) has g = 0 here and meets the window's zero padding: it adds
+// half(0 * 0) = +0, which changes at most the sign of a zero partial -- and r, which starts at +0 and so is never -0,
+// absorbs either zero alike.
+template <bool SECOND>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void corr_backward_k1_f16(
+    const __half* __restrict__ other, const __half* __restrict__ gout, __half* __restrict__ gin,
+    int channel, int h, int w, int groups, int ch_per_group) {
+    constexpr int MD = 4, D = 2 * MD + 1, OC = D * D, TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD, NT = 128;
+    __shared__ __attribute__((aligned(16))) __half win[2][LH][LW];
+    const int tid = threadIdx.x, px = 2 * (tid & 31), py = tid >> 5;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int bx = x0 + px, by = y0 + py;
+    const int n = blockIdx.z / groups, cg = blockIdx.z - n * groups;
+    const int c_begin = cg * ch_per_group, c_end = min(channel, c_begin + ch_per_group);
+    const bool in0 = bx < w && by < h, in1 = bx + 1 < w && by < h;
+    const int64_t plane = (int64_t)h * w;
+    const __half* go = gout + (int64_t)n * OC * plane;
+    const __half zero = __float2half_rn(0.0f);
+    if (c_begin >= c_end) return;
+
+    // the pair's 81 gradOutput values (zero where the reference skips the term, and for a pixel outside the frame).  Buffer
+    // loads through a descriptor that spans the image's gradOutput: one 32-bit offset per load, and an offset out of range
+    // (an element outside the frame) returns the zero.  (Left to itself the compiler issues all 162 loads at once and needs
+    // over 200 registers: the loads go out one displacement row at a time.)
+    const auto gd = __builtin_amdgcn_make_buffer_rsrc((void*)go, 0, (int)(OC * plane * 2), 0x00020000);
+    __half2 g[OC];
+#pragma unroll
+    for (int tc = 0; tc < OC; ++tc) {
+        const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
+        const bool rok = gy >= 0 && gy < h;
+        const bool ok0 = in0 && rok && gx >= 0 && gx < w, ok1 = in1 && rok && gx + 1 >= 0 && gx + 1 < w;
+        const unsigned off = 2u * (unsigned)(tc * (int)plane + gy * w + gx);
+        const unsigned short lo = __builtin_amdgcn_raw_buffer_load_b16(gd, ok0 ? off : 0x80000000u, 0, 0);
+        const unsigned short hi = __builtin_amdgcn_raw_buffer_load_b16(gd, ok1 ? off + 2u : 0x80000000u, 0, 0);
+        g[tc] = __halves2half2(__ushort_as_half(lo), __ushort_as_half(hi));
+        asm volatile("" : "+v"(g[tc]));                              // (packed here, not both halves kept to the end)
+        if (tc % D == D - 1) __builtin_amdgcn_sched_barrier(0);     // one displacement row of loads in flight at a time
+    }
+
+    auto stage = [&](int c, int buf) {
+        const auto od = __builtin_amdgcn_make_buffer_rsrc((void*)(other + ((int64_t)n * channel + c) * plane), 0, (int)(plane * 2), 0x00020000);
+        for (int e = tid; e < LH * LW; e += NT) {
+            const int r = e / LW, col = e - r * LW;
+            const int gy = y0 - MD + r, gx = x0 - MD + col;
+            const bool ok = gy >= 0 && gy < h && gx >= 0 && gx < w;
+            win[buf][r][col] = __ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(od, ok ? 2u * (unsigned)(gy * w + gx) : 0x80000000u, 0, 0));
+        }
+    };
+    stage(c_begin, 0);
+    const float nelems_h = __half2float(__float2half_rn((float)channel));
+    for (int c = c_begin; c < c_end; ++c) {
+        const int buf = (c - c_begin) & 1;
+        __syncthreads();                                    // window c has been written; window c - 1 has been read
+        if (c + 1 < c_end) stage(c + 1, buf ^ 1);
+        // tc in ascending order, the product of tc going straight into partial tc % 32: partial l receives tc = l, l + 32,
+        // l + 64 in that order, and only the 32 partials are live beside g.  (s_l starts at its first term, not at +0 + it:
+        // that changes at most the sign of a zero partial, and r -- which starts at +0 and so is never -0 -- absorbs either
+        // zero alike.)  Window row tj (gradInput1) or 2*MD - tj (gradInput2), columns px .. px + 9 as five aligned pairs; the
+        // pair a displacement column needs is one of them (even offset) or straddles two (odd offset).
+        __half2 s[32];
+#pragma unroll
+        for (int tj = 0; tj < D; ++tj) {
+            const __half2* row = reinterpret_cast<const __half2*>(&win[buf][py + (SECOND ? 2 * MD - tj : tj)][px]);
+            __half2 q[MD + 1];
+#pragma unroll
+            for (int k = 0; k <= MD; ++k) q[k] = row[k];
+#pragma unroll
+            for (int ti = 0; ti < D; ++ti) {
+                const int tc = tj * D + ti, o = SECOND ? 2 * MD - ti : ti;
+                const __half2 v = (o & 1) ? __halves2half2(__high2half(q[o / 2]), __low2half(q[o / 2 + 1])) : q[o / 2];
+                const __half2 prod = __hmul2(g[tc], v);
+                s[tc % 32] = tc < 32 ? prod : __hadd2(s[tc % 32], prod);
+            }
+            __builtin_amdgcn_sched_barrier(0);     // (a row's window reads at a time: g and the 32 partials hold 113 registers)
+        }
+        __half2 r = __halves2half2(zero, zero);
+#pragma unroll
+        for (int l = 0; l < 32; ++l) r = __hadd2(r, s[l]);
+        __half* o = gin + ((int64_t)n * channel + c) * plane + (int64_t)by * w + bx;
+        if (in0) o[0] = corr_mean_f16(__low2half(r), nelems_h);
+        if (in1) o[1] = corr_mean_f16(__high2half(r), nelems_h);
+    }
+}
+
 }  // namespace vfi
 
 using namespace vfi;
@@ -1054,6 +1212,49 @@ extern "C" int vfi_correlation_backward(const float* input1, const float* input2
                        oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     hipLaunchKernelGGL(corr_backward<true>, grid, block, 0, st, input1, gradoutput, gradinput2, batch, channel, h, w,
+                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    return launch_status();
+}
+
+extern "C" int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,
+                                             void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
+                                             int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+                                             vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
+    if (!input1 || !input2 || !gradoutput || !gradinput1 || !gradinput2) return VFI_ERR_SHAPE;
+    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (stride1 != 1 || oh <= 0 || ow <= 0) return VFI_ERR_SHAPE;      // (as vfi_correlation_backward)
+    const int64_t total = (int64_t)batch * channel * h * w;
+    if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const __half* in1 = (const __half*)input1;
+    const __half* in2 = (const __half*)input2;
+    const __half* go = (const __half*)gradoutput;
+    __half* g1 = (__half*)gradinput1;
+    __half* g2 = (__half*)gradinput2;
+    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
+        // PWC-Net's configuration: the tiled kernel, channel groups over blockIdx.z as in vfi_correlation_backward
+        const int tiles = ((w + 63) / 64) * ((h + 3) / 4);
+        int groups = (int)std::min<int64_t>(channel, std::max<int64_t>(1, (2048 + (int64_t)tiles * batch - 1) / ((int64_t)tiles * batch)));
+        const int ch_per_group = (channel + groups - 1) / groups;
+        groups = (channel + ch_per_group - 1) / ch_per_group;
+        // (the kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB)
+        if ((int64_t)batch * groups <= 65535 && (int64_t)81 * h * w * 2 < INT_MAX) {
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
+            hipLaunchKernelGGL(corr_backward_k1_f16<false>, grid, dim3(128), 0, st, in2, go, g1, channel, h, w, groups, ch_per_group);
+            if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
+            hipLaunchKernelGGL(corr_backward_k1_f16<true>, grid, dim3(128), 0, st, in1, go, g2, channel, h, w, groups, ch_per_group);
+            return launch_status();
+        }
+    }
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipLaunchKernelGGL(corr_backward_f16<false>, grid, block, 0, st, in2, go, g1, batch, channel, h, w,
+                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
+    hipLaunchKernelGGL(corr_backward_f16<true>, grid, block, 0, st, in1, go, g2, batch, channel, h, w,
                        oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
     return launch_status();
 }

@@ -497,10 +497,21 @@ int correlation_backward(at::Tensor& input1, at::Tensor& input2, at::Tensor& rIn
     gradInput1.resize_({batch, channel, h, w});
     gradInput2.resize_({batch, channel, h, w});
     at::Tensor a = input1.contiguous(), b = input2.contiguous(), g = gradOutput.contiguous();
-    StreamScope s(a);
-    const int err = vfi_correlation_backward(cptr(a), cptr(b), cptr(g), mptr(gradInput1), mptr(gradInput2), batch,
-                                             channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
-                                             s.stream);
+    StreamScope s(a, /*allow_half=*/true);
+    int err;
+    if (a.scalar_type() == at::kHalf) {         // AT_DISPATCH_FLOATING_TYPES_AND_HALF (correlation_cuda_kernel.cu:495-541)
+        TORCH_CHECK(b.scalar_type() == at::kHalf && g.scalar_type() == at::kHalf && gradInput1.scalar_type() == at::kHalf &&
+                    gradInput2.scalar_type() == at::kHalf && b.is_cuda() && g.is_cuda() && gradInput1.is_cuda() &&
+                    gradInput2.is_cuda(),
+                    "correlation_cuda.backward: half input1 needs half input2, gradOutput, gradInput1 and gradInput2 on the GPU");
+        err = vfi_correlation_backward_f16(a.data_ptr(), b.data_ptr(), g.data_ptr(), gradInput1.data_ptr(),
+                                           gradInput2.data_ptr(), batch, channel, h, w, pad_size, kernel_size,
+                                           max_displacement, stride1, stride2, s.stream);
+    } else {
+        err = vfi_correlation_backward(cptr(a), cptr(b), cptr(g), mptr(gradInput1), mptr(gradInput2), batch,
+                                       channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
+                                       s.stream);
+    }
     TORCH_CHECK(err == VFI_OK, "CUDA call failed");
     return 1;
 }
