@@ -344,6 +344,24 @@ int vfi_pwc_warp_forward(const float* x, const float* flow, float* output,
                          vfi_strides sx, vfi_strides sf, vfi_strides so,
                          vfi_stream_t stream);
 
+/* Backward of PWCDCNet.warp: the gradients torch autograd gives for the reference's warp() in the same
+ * align_corners mode.  The mask is a constant (its two index assignments overwrite every element); the
+ * sample is ATen's bilinear grid_sampler_2d with zero padding, so a corner outside the map counts 0 in
+ * both gradients (a sample on the last column / row gets a one-sided derivative).  With gm = grad_output
+ * x mask: grad_x[c, corner] += gm x weight for the in-bounds corners, summed as 64-bit fixed-point
+ * integers (DESIGN.md "Deterministic image gradients"; fp32 atomics where grad_output holds a NaN / Inf or
+ * magnitudes that could overflow); grad_x is ADDED INTO, the caller zero-fills it, as for
+ * vfi_interpolation_backward.  grad_flow is WRITTEN: per pixel the channel sum of gm x d(sample)/d(ix, iy)
+ * in a fixed order, times grid_sample's un-normalisation ((W-1)/2 aligned, W/2 not) and the reference's
+ * 2 / max(W-1, 1); a pixel with mask 0 gets 0 for finite inputs.  Either gradient may be NULL (not
+ * computed; the other one is bit-identical).  Both are bit-reproducible.  Any batch / channel / row
+ * strides, w stride 1 for every tensor.  May allocate library scratch on its first call per stream. */
+int vfi_pwc_warp_backward(const float* x, const float* flow, const float* grad_output,
+                          float* grad_x, float* grad_flow,
+                          int batch, int channel, int h, int w, int align_corners,
+                          vfi_strides sx, vfi_strides sf, vfi_strides sgo, vfi_strides sgx, vfi_strides sgf,
+                          vfi_stream_t stream);
+
 /* PWCDCNet's warp feeding its correlation layer (PWCNet/PWCNet.py:244-247, 266-267, 282-283, 299-300):
  * output[B,81,h,w] = correlation(input1, warp(input2, flow)) with pad 4, kernel 1, max displacement 4, strides 1 --
  * vfi_pwc_warp_forward followed by vfi_correlation_forward, bit for bit, in one launch and without the warped

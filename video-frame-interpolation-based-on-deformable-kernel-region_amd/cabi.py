@@ -67,6 +67,7 @@ SIGNATURES = {
     "vfi_filterinterp_blend_forward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, Strides, Strides,
                                        Strides, Strides, _p],
     "vfi_pwc_warp_forward": [_p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
+    "vfi_pwc_warp_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_correlation_forward": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, _p],
     "vfi_frame_u8_to_planar": [_p, _p, _i, _i, _i, _i, _i, _i, _i, Strides, _p],
     "vfi_planar_to_frame_u8": [_p, _p, _i, _i, _i, _i, _i, Strides, _p],
@@ -636,6 +637,26 @@ def pwc_warp_forward(x, flow, output, align_corners=True):
     with torch.cuda.device(_dev(x)):
         return _finish(lib().vfi_pwc_warp_forward(_ptr(x), _ptr(flow), _ptr(output), b, c, h, w, int(bool(align_corners)),
                                                   _st(x), _st(flow), _st(output), _stream(x)))
+
+
+def pwc_warp_backward(x, flow, grad_output, grad_x=None, grad_flow=None, align_corners=True):
+    """grad_x (added into: zero-fill it) and / or grad_flow (written) of pwc_warp_forward; None = not computed."""
+    b, c, h, w = x.shape
+    grads = [t for t in (grad_x, grad_flow) if t is not None]
+    if not _nchw_ok(x, flow, grad_output, *grads) or tuple(flow.shape) != (b, 2, h, w) or grad_output.shape != x.shape:
+        return 1
+    if (grad_x is not None and grad_x.shape != x.shape) or (grad_flow is not None and grad_flow.shape != flow.shape):
+        return 1
+    _dev(flow), _dev(grad_output)
+    for t in grads:
+        _dev(t)
+    null = ctypes.c_void_p(0)
+    with torch.cuda.device(_dev(x)):
+        return _finish(lib().vfi_pwc_warp_backward(
+            _ptr(x), _ptr(flow), _ptr(grad_output), _ptr(grad_x) if grad_x is not None else null,
+            _ptr(grad_flow) if grad_flow is not None else null, b, c, h, w, int(bool(align_corners)), _st(x), _st(flow),
+            _st(grad_output), _st(grad_x) if grad_x is not None else _st(x),
+            _st(grad_flow) if grad_flow is not None else _st(flow), _stream(x)))
 
 
 def pwc_warp_correlation_forward(input1, input2, flow, align_corners=True):

@@ -9,6 +9,7 @@
 //     interpolation error (demo_MiddleBury.py:280-318, 350-364, 370-388).
 // (The x4 flow upsample fused into the projection is in projection.hip.)
 #include "filterinterp_dev.h"
+#include "pwc_warp.h"
 
 namespace vfi {
 
@@ -109,8 +110,8 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_blend_only(
 // ------------------------------------------------------------------ PWC-Net warp()
 
 // vgrid = pixel + flow; normalised as PWCNet.py:184-185; grid_sample (bilinear, zeros padding) of x
-// and of a ones tensor; mask = (ones sample >= 0.9999); out = sample * mask.  align_corners selects
-// grid_sample's un-normalisation: 1 = torch <= 1.2 (what the reference was written for: the
+// and of a ones tensor; mask = (ones sample >= 0.9999); out = sample * mask (pwc_warp.h).  align_corners
+// selects grid_sample's un-normalisation: 1 = torch <= 1.2 (what the reference was written for: the
 // normalisation above then round-trips to pixel + flow), 0 = the default of torch >= 1.3.
 #define PWC_CH 8                    // channels per thread: blockIdx.z = batch x channel chunks
 __global__ __launch_bounds__(VFI_TX * VFI_TY) void pwc_warp_forward(
@@ -121,48 +122,18 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void pwc_warp_forward(
     if (x >= w || y >= h) return;
     const int b = blockIdx.z / groups;
     const float* f = flo + (int64_t)b * sf.b + (int64_t)y * sf.h + x;
-    const float vx = (float)x + f[0], vy = (float)y + f[sf.c];
-    const float gx = 2.0f * vx / (float)max(w - 1, 1) - 1.0f;
-    const float gy = 2.0f * vy / (float)max(h - 1, 1) - 1.0f;
-    // ATen grid_sampler_unnormalize
-    const float ix = align_corners ? ((gx + 1.0f) / 2.0f) * (float)(w - 1) : ((gx + 1.0f) * (float)w - 1.0f) / 2.0f;
-    const float iy = align_corners ? ((gy + 1.0f) / 2.0f) * (float)(h - 1) : ((gy + 1.0f) * (float)h - 1.0f) / 2.0f;
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    // corners as ATen orders them: nw, ne, sw, se; weights from the opposite corner
-    const float wnw = (fx0 + 1.0f - ix) * (fy0 + 1.0f - iy), wne = (ix - fx0) * (fy0 + 1.0f - iy);
-    const float wsw = (fx0 + 1.0f - ix) * (iy - fy0), wse = (ix - fx0) * (iy - fy0);
-    // float -> int of a huge or NaN coordinate is undefined in C; such a corner is out of bounds anyway
-    const bool finite = fabsf(ix) < 1.0e9f && fabsf(iy) < 1.0e9f;
-    const int x0 = finite ? (int)fx0 : -2, y0 = finite ? (int)fy0 : -2;
-    const bool inx0 = x0 >= 0 && x0 < w, inx1 = x0 + 1 >= 0 && x0 + 1 < w;
-    const bool iny0 = y0 >= 0 && y0 < h, iny1 = y0 + 1 >= 0 && y0 + 1 < h;
-    float m = 0.0f;
-    if (iny0 && inx0) m += wnw;
-    if (iny0 && inx1) m += wne;
-    if (iny1 && inx0) m += wsw;
-    if (iny1 && inx1) m += wse;
-    const float mask = (m < 0.9999f) ? 0.0f : (m > 0.0f ? 1.0f : m);   // mask[mask<0.9999]=0; mask[mask>0]=1 (NaN stays)
+    const PwcSample s = pwc_sample(f[0], f[sf.c], x, y, h, w, align_corners);
     // A corner outside the map is skipped by ATen; here it is read at a clamped (valid) address and both the value
-    // and its weight are replaced by 0, so v = fma(0, 0, v) = v: the same result from straight-line loads, all of a
-    // chunk's 4 x PWC_CH loads in flight at once.  (With the conditional loads of a per-channel loop a thread walked
+    // and its weight are replaced by 0 (pwc_warped): the same result from straight-line loads, all of a chunk's
+    // 4 x PWC_CH loads in flight at once.  (With the conditional loads of a per-channel loop a thread walked
     // its channels one memory round trip at a time: the 196-channel 18x31 level took longer than the 32-channel
     // 288x496 one.)
-    const int cx0 = clampi(x0, 0, w - 1), cx1 = clampi(x0 + 1, 0, w - 1), cy0 = clampi(y0, 0, h - 1), cy1 = clampi(y0 + 1, 0, h - 1);
-    const int64_t onw = (int64_t)cy0 * sx.h + cx0, one = (int64_t)cy0 * sx.h + cx1;
-    const int64_t osw = (int64_t)cy1 * sx.h + cx0, ose = (int64_t)cy1 * sx.h + cx1;
-    const bool bnw = iny0 && inx0, bne = iny0 && inx1, bsw = iny1 && inx0, bse = iny1 && inx1;
-    const float enw = bnw ? wnw : 0.0f, ene = bne ? wne : 0.0f, esw = bsw ? wsw : 0.0f, ese = bse ? wse : 0.0f;
+    const int64_t onw = (int64_t)s.cy0 * sx.h + s.cx0, one = (int64_t)s.cy0 * sx.h + s.cx1;
+    const int64_t osw = (int64_t)s.cy1 * sx.h + s.cx0, ose = (int64_t)s.cy1 * sx.h + s.cx1;
     const int c0 = (int)(blockIdx.z % groups) * PWC_CH;
     const float* src = xin + (int64_t)b * sx.b + (int64_t)c0 * sx.c;
     float* dst = out + (int64_t)b * so.b + (int64_t)c0 * so.c + (int64_t)y * so.h + x;
-    auto one_channel = [&](float pnw, float pne, float psw, float pse) {
-        float v = 0.0f;                                     // out_acc += value * weight, fused as nvcc fuses ATen's grid_sampler
-        v = fmaf(bnw ? pnw : 0.0f, enw, v);
-        v = fmaf(bne ? pne : 0.0f, ene, v);
-        v = fmaf(bsw ? psw : 0.0f, esw, v);
-        v = fmaf(bse ? pse : 0.0f, ese, v);
-        return v * mask;
-    };
+    auto one_channel = [&](float pnw, float pne, float psw, float pse) { return pwc_warped(s, pnw, pne, psw, pse); };
     if (c0 + PWC_CH <= channel) {
         float q[PWC_CH][4];
 #pragma unroll

@@ -14,7 +14,7 @@
 // lane owns two adjacent pixels; window 12 x 40 = 480 pixels, one per thread: a thread keeps its window pixel's
 // four clamped tap offsets, four weights and mask in registers for all channels and fetches 8 channels x 4 taps
 // per chunk, the next chunk's before the current one is multiplied.
-#include "vfi_common.h"
+#include "pwc_warp.h"
 
 namespace vfi {
 
@@ -46,47 +46,19 @@ __global__ __launch_bounds__(WC_NT) void warp_corr_forward(
     const float* f2 = in2 + (int64_t)b * channel * plane;
     const int wy0 = blockIdx.y * WC_TH - WC_MD, wx0 = blockIdx.x * WC_TW - WC_MD;   // window origin (pad == md: org = 0)
 
-    // ---- this thread's window pixel: the warp's sampling geometry (glue.hip: pwc_warp_forward, statement for statement)
+    // ---- this thread's window pixel: the warp's sampling geometry (pwc_warp.h, as glue.hip: pwc_warp_forward)
     const int wr = tid / WC_LW, wc = tid - wr * WC_LW;
     const int gy = wy0 + wr, gx = wx0 + wc;
     const bool wpix = tid < WC_LH * WC_LW;
     const bool inframe = wpix && gy >= 0 && gy < h && gx >= 0 && gx < w;        // else the correlation's zero padding
     int onw = 0, one = 0, osw = 0, ose = 0;
-    float enw = 0.0f, ene = 0.0f, esw = 0.0f, ese = 0.0f, mask = 0.0f;
-    bool bnw = false, bne = false, bsw = false, bse = false;
+    PwcSample s = {};
     if (inframe) {
         const float* f = flo + (int64_t)b * sf.b + (int64_t)gy * sf.h + gx;
-        const float vx = (float)gx + f[0], vy = (float)gy + f[sf.c];
-        const float nx = 2.0f * vx / (float)max(w - 1, 1) - 1.0f;
-        const float ny = 2.0f * vy / (float)max(h - 1, 1) - 1.0f;
-        const float ix = align_corners ? ((nx + 1.0f) / 2.0f) * (float)(w - 1) : ((nx + 1.0f) * (float)w - 1.0f) / 2.0f;
-        const float iy = align_corners ? ((ny + 1.0f) / 2.0f) * (float)(h - 1) : ((ny + 1.0f) * (float)h - 1.0f) / 2.0f;
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const float wnw = (fx0 + 1.0f - ix) * (fy0 + 1.0f - iy), wne = (ix - fx0) * (fy0 + 1.0f - iy);
-        const float wsw = (fx0 + 1.0f - ix) * (iy - fy0), wse = (ix - fx0) * (iy - fy0);
-        const bool finite = fabsf(ix) < 1.0e9f && fabsf(iy) < 1.0e9f;
-        const int x0 = finite ? (int)fx0 : -2, y0 = finite ? (int)fy0 : -2;
-        const bool inx0 = x0 >= 0 && x0 < w, inx1 = x0 + 1 >= 0 && x0 + 1 < w;
-        const bool iny0 = y0 >= 0 && y0 < h, iny1 = y0 + 1 >= 0 && y0 + 1 < h;
-        float m = 0.0f;
-        if (iny0 && inx0) m += wnw;
-        if (iny0 && inx1) m += wne;
-        if (iny1 && inx0) m += wsw;
-        if (iny1 && inx1) m += wse;
-        mask = (m < 0.9999f) ? 0.0f : (m > 0.0f ? 1.0f : m);
-        const int cx0 = clampi(x0, 0, w - 1), cx1 = clampi(x0 + 1, 0, w - 1), cy0 = clampi(y0, 0, h - 1), cy1 = clampi(y0 + 1, 0, h - 1);
-        onw = cy0 * w + cx0; one = cy0 * w + cx1; osw = cy1 * w + cx0; ose = cy1 * w + cx1;
-        bnw = iny0 && inx0; bne = iny0 && inx1; bsw = iny1 && inx0; bse = iny1 && inx1;
-        enw = bnw ? wnw : 0.0f; ene = bne ? wne : 0.0f; esw = bsw ? wsw : 0.0f; ese = bse ? wse : 0.0f;
+        s = pwc_sample(f[0], f[sf.c], gx, gy, h, w, align_corners);
+        onw = s.cy0 * w + s.cx0; one = s.cy0 * w + s.cx1; osw = s.cy1 * w + s.cx0; ose = s.cy1 * w + s.cx1;
     }
-    auto warped = [&](float pnw, float pne, float psw, float pse) {
-        float v = 0.0f;
-        v = fmaf(bnw ? pnw : 0.0f, enw, v);
-        v = fmaf(bne ? pne : 0.0f, ene, v);
-        v = fmaf(bsw ? psw : 0.0f, esw, v);
-        v = fmaf(bse ? pse : 0.0f, ese, v);
-        return v * mask;
-    };
+    auto warped = [&](float pnw, float pne, float psw, float pse) { return pwc_warped(s, pnw, pne, psw, pse); };
 
     // ---- staging plan of the first map: value e = tid + k * NT of the chunk's [CC][TH][TW] block
     int foff[WC_NF1], fch[WC_NF1];

@@ -1,10 +1,13 @@
 """Host-side mirrors of the glue either side of the hot-path ops, on the fused entry
 points of libvfi_hip.so.  Same names and argument meaning as the reference's static helpers
 (`networks/DAIN_slowmotion.py:204-216, 301-335`, `PWCNet/PWCNet.py:159-199`,
-`demo_MiddleBury.py:280-318, 350-388`); inference only (no autograd)."""
+`demo_MiddleBury.py:280-318, 350-388`).  `warp` and `warp_corr` are differentiable (PWC-Net's glue, trained with
+the flow network: the backward is vfi_pwc_warp_backward, and for `warp_corr` also the correlation backward); the rest
+is inference only (no autograd)."""
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import cabi
 
@@ -135,8 +138,55 @@ def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
     return list(zip(out0, out2))
 
 
+class _Warp(torch.autograd.Function):
+    """`PWCDCNet.warp` with the gradients torch autograd gives for the reference's formula (vfi_pwc_warp_backward)."""
+
+    @staticmethod
+    def forward(ctx, x, flo, align_corners):
+        out = torch.empty_like(x)
+        _check(cabi.pwc_warp_forward(x, flo, out, align_corners), "pwc_warp_forward")
+        ctx.save_for_backward(x, flo)
+        ctx.align_corners = align_corners
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, flo = ctx.saved_tensors
+        if grad_out.stride(3) != 1:                         # (e.g. the expanded gradient of a sum())
+            grad_out = grad_out.contiguous()
+        gx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None          # (added into)
+        gf = torch.empty_like(flo) if ctx.needs_input_grad[1] else None        # (written)
+        if gx is not None or gf is not None:
+            _check(cabi.pwc_warp_backward(x, flo, grad_out, gx, gf, ctx.align_corners), "pwc_warp_backward")
+        return gx, gf, None
+
+
+class _Corr(torch.autograd.Function):
+    """PWC-Net's correlation (pad 4, k 1, md 4, strides 1) on the C ABI, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, c1, c2):
+        ctx.save_for_backward(c1, c2)
+        return cabi.correlation_forward(c1, c2, 4, 1, 4, 1, 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        c1, c2 = ctx.saved_tensors
+        g1, g2 = cabi.correlation_backward(c1, c2, grad_out, 4, 1, 4, 1, 1)
+        return (g1 if ctx.needs_input_grad[0] else None), (g2 if ctx.needs_input_grad[1] else None)
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
 def warp(x, flo, align_corners=True):
-    """`PWCDCNet.warp`."""
+    """`PWCDCNet.warp`.  Differentiable when grad mode is on and x or flo requires grad; otherwise the plain forward
+    launch (no grad_fn)."""
+    if _wants_grad(x, flo):
+        return _Warp.apply(x, flo, bool(align_corners))
     out = torch.empty_like(x)
     _check(cabi.pwc_warp_forward(x, flo, out, align_corners), "pwc_warp_forward")
     return out
@@ -147,7 +197,11 @@ def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
     its LeakyReLU to the result afterwards.  Default: the warp kernel, then the correlation kernel.  one_launch=True:
     vfi_pwc_warp_correlation_forward, which never materialises the warped tensor -- same bits, but measured SLOWER on
     MI355X at PWC-Net's sizes (0.33 vs 0.15 ms for the five levels of a 1080p pair): every tile re-forms the bilinear
-    samples of its 4-pixel halo (3.75 x the taps), which costs more than the 2 x 18 MB round trip it saves."""
+    samples of its 4-pixel halo (3.75 x the taps), which costs more than the 2 x 18 MB round trip it saves.
+    Differentiable when grad mode is on and an input requires grad: then the two-launch path (one_launch is ignored;
+    same bits), whose warped tensor the correlation backward needs."""
+    if _wants_grad(c1, c2, flo):
+        return _Corr.apply(c1, warp(c2, flo, align_corners))
     if one_launch:
         return cabi.pwc_warp_correlation_forward(c1, c2, flo, align_corners)
     return cabi.correlation_forward(c1, warp(c2, flo, align_corners), 4, 1, 4, 1, 1)
