@@ -336,6 +336,34 @@ int vfi_filterinterp_blend_forward(const float* ref0, const float* ref2,
                                    vfi_strides s_ref, vfi_strides s_flow, vfi_strides s_filt, vfi_strides s_out,
                                    vfi_stream_t stream);
 
+/* Backward of vfi_filterinterp_blend_forward (training DAIN through the fused synthesis).
+ * - Per direction d (0: ref0 / flow0 / filt0 / w0, 2: the same with 2) the incoming gradient is
+ *   g_d = grad_blend * w_d + grad_out_d, the product and the sum rounded separately: what torch
+ *   autograd accumulates for out_d when blend = out0 * w0 + out2 * w2 and out_d has another use.
+ *   It is formed in registers, never stored.  A NULL grad_blend / grad_out_d is an absent term; a
+ *   direction with both terms NULL has zero gradients.
+ * - Every requested gradient equals, bit for bit, vfi_filterinterp_backward_ori(ref_d, flow_d,
+ *   filt_d, g_d) run on zero-filled outputs with g_d materialised; the image gradient's fixed-point
+ *   scale comes from a max-scan over g_d formed the same way.  Non-finite g_d or filters scatter
+ *   the image gradient with fp32 atomics as that entry does (same NaN / Inf pattern).
+ * - Any of the six gradient outputs may be NULL and is then not computed (with both grad_ref NULL
+ *   there is no image-gradient work at all).  Requested outputs are written in full: the caller
+ *   does not zero them.  All six NULL: VFI_OK, nothing launched.
+ * - ref0/ref2 and grad_ref0/grad_ref2 use s_ref, flows and their gradients s_flow, filters and
+ *   their gradients s_filt, grad_blend/grad_out0/grad_out2 s_grad.
+ * - Any filter_channels the forward accepts; 16 (fs = 4) is the LDS-staged path.  Both directions
+ *   run in the same launches; results are reproducible bit for bit. */
+int vfi_filterinterp_blend_backward(const float* ref0, const float* ref2,
+                                    const float* flow0, const float* flow2,
+                                    const float* filt0, const float* filt2,
+                                    const float* grad_blend, const float* grad_out0, const float* grad_out2,
+                                    float* grad_ref0, float* grad_ref2,
+                                    float* grad_flow0, float* grad_flow2,
+                                    float* grad_filt0, float* grad_filt2,
+                                    int batch, int channel, int h, int w, int filter_channels, float w0, float w2,
+                                    vfi_strides s_ref, vfi_strides s_flow, vfi_strides s_filt, vfi_strides s_grad,
+                                    vfi_stream_t stream);
+
 /* PWCDCNet.warp (PWCNet/PWCNet.py:159-199): output = grid_sample(x, grid(flow)) * mask, mask = 1
  * where grid_sample(ones, grid) >= 0.9999 else 0; bilinear, zeros padding.  align_corners: 1 = the
  * grid_sample of torch <= 1.2 the reference was written for, 0 = the default of torch >= 1.3. */

@@ -66,6 +66,8 @@ SIGNATURES = {
                                             _p],
     "vfi_filterinterp_blend_forward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, Strides, Strides,
                                        Strides, Strides, _p],
+    "vfi_filterinterp_blend_backward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
+                                        _f, _f, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_forward": [_p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_correlation_forward": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, _p],
@@ -627,6 +629,38 @@ def filterinterp_blend_forward(ref0, ref2, flow0, flow2, filt0, filt2, blend, ou
             _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), _ptr(blend),
             _ptr(out0) if out0 is not None else null, _ptr(out2) if out2 is not None else null, b, c, h, w,
             filt0.size(1), w0, w2, _st(ref0), _st(flow0), _st(filt0), _st(blend), _stream(ref0)))
+
+
+def filterinterp_blend_backward(ref0, ref2, flow0, flow2, filt0, filt2, grad_blend, grad_out0, grad_out2, w0, w2,
+                                grad_ref0=None, grad_ref2=None, grad_flow0=None, grad_flow2=None, grad_filt0=None,
+                                grad_filt2=None):
+    """Backward of filterinterp_blend_forward: direction d's gradient is grad_blend * w_d + grad_out_d (None = an absent term).
+    Gradient outputs that are None are not computed; the others are written in full (no zero fill needed) and share
+    their input's layout.  The incoming gradients share one layout."""
+    dims = _fi_checks(ref0, flow0, filt0, None)
+    if dims is None or not (_same_strides(ref0, ref2) and _same_strides(flow0, flow2) and _same_strides(filt0, filt2)):
+        return 1
+    if not _fi_filter_ok(ref0, filt0):
+        return 1
+    grads = [t for t in (grad_blend, grad_out0, grad_out2) if t is not None]
+    if grads and (grads[0].shape != ref0.shape or grads[0].stride(3) != 1 or
+                  not all(_same_strides(grads[0], t) for t in grads)):
+        return 1
+    if not _addressed_as(ref0, *[t for t in (grad_ref0, grad_ref2) if t is not None]) or \
+            not _addressed_as(flow0, *[t for t in (grad_flow0, grad_flow2) if t is not None]) or \
+            not _addressed_as(filt0, *[t for t in (grad_filt0, grad_filt2) if t is not None]):
+        return 1
+    b, c, h, w = dims
+    outs = (grad_ref0, grad_ref2, grad_flow0, grad_flow2, grad_filt0, grad_filt2)
+    for t in (ref2, flow0, flow2, filt0, filt2, *grads, *[t for t in outs if t is not None]):
+        _dev(t)
+    null = ctypes.c_void_p(0)
+    opt = lambda t: _ptr(t) if t is not None else null      # noqa: E731
+    with torch.cuda.device(_dev(ref0)):
+        return _finish(lib().vfi_filterinterp_blend_backward(
+            _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), opt(grad_blend), opt(grad_out0),
+            opt(grad_out2), *[opt(t) for t in outs], b, c, h, w, filt0.size(1), w0, w2, _st(ref0), _st(flow0), _st(filt0),
+            _st(grads[0]) if grads else _st(ref0), _stream(ref0)))
 
 
 def pwc_warp_forward(x, flow, output, align_corners=True):

@@ -11,6 +11,7 @@
 // The LDS-staged forward for fs == 4 lives in filterinterp_lds.hip and falls
 // back to the kernel here when a tile's tap window does not fit its LDS budget.
 #include "filterinterp_dev.h"
+#include "workspace.h"
 
 #include <limits.h>
 
@@ -79,22 +80,61 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct(
 static_assert(FB_THREADS <= 1024 && FB_THREADS % 64 == 0, "workgroup size");
 static_assert(((FB_WAVES * 256) / FB_THREADS) * (2 + FB_CELLS + FB_CELLS / 2) * 8 <= 160 * 1024, "workgroups per CU x LDS per workgroup exceed the CU's LDS");
 
-__global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
-    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
-    const float* __restrict__ gout, unsigned long long* __restrict__ acc, const int* __restrict__ hdr, float* g1, float* g2, float* g3,
-    int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, const int* __restrict__ tileflag) {
+// Where the two kernels below read their incoming gradient and which outputs they write.  vfi_filterinterp_backward_ori: one
+// tensor (GradPlain), every output requested and zero-filled by the caller.  vfi_filterinterp_blend_backward (BLEND): the two
+// terms of a direction's gradient (GradTerms: g = grad_blend * w + grad_out, formed where the tensor is read), any output
+// may be NULL, and requested outputs are written in full -- zeros where a pixel has no gradient, filter-gradient sums that
+// start from 0 instead of the caller's cells (the same bits: the caller's cells are +0).  WANT_X = false: no image
+// gradient -- no LDS cells, no 64-bit atomics, no fixed-point header.
+
+// one direction of the blend backward (grid z = direction * batch + b)
+struct FiBwdSide {
+    const float* ref;
+    const float* flow;
+    const float* filt;
+    GradTerms g;
+    unsigned long long* acc;                                // this direction's dense fixed-point sums and header
+    const int* hdr;
+    float* gref;
+    float* gflow;
+    float* gfilt;
+};
+struct FiBwdPair { FiBwdSide d[2]; };
+
+// flow / filter gradient of a pixel with none (BLEND: outputs are written in full)
+__device__ __forceinline__ void fi_bwd_zero_px(float* gf, int64_t s2c, float* gfpx, int64_t s3c, int fs2) {
+    if (gf) { gf[0] = 0.0f; gf[s2c] = 0.0f; }
+    if (gfpx) for (int k = 0; k < fs2; ++k) gfpx[(int64_t)k * s3c] = 0.0f;
+}
+
+// one thread per pixel, any filter size; b: the image, zb: blockIdx.z (the flags' plane); sg: the incoming gradient's strides
+template <class G, bool BLEND, bool WANT_X>
+__device__ __forceinline__ void fi_backward_ori_px(
+    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3, G gsrc,
+    unsigned long long* __restrict__ acc, const int* __restrict__ hdr, float* g1, float* g2, float* g3,
+    int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
+    const int* __restrict__ tileflag, int b, int zb, int fc = 0) {
     const int x = blockIdx.x * VFI_TX + threadIdx.x;
     const int y = blockIdx.y * VFI_TY + threadIdx.y;
     if (x >= w || y >= h) return;
-    const int b = blockIdx.z;
     // (after fi_backward_ori4_lds: only the tiles that kernel left alone; VFI_TX x VFI_TY blocks nest in them)
-    if (tileflag && !tileflag[(b * ((h + FB_TH - 1) / FB_TH) + y / FB_TH) * gridDim.x + blockIdx.x]) return;
-    const GradAccCtx gctx = gradacc_ctx(hdr);
+    if (tileflag && !tileflag[(zb * ((h + FB_TH - 1) / FB_TH) + y / FB_TH) * gridDim.x + blockIdx.x]) return;
+    const bool wx = WANT_X && (!BLEND || g1 != nullptr);   // (uniform: this direction's image gradient is wanted)
+    const GradAccCtx gctx = wx ? gradacc_ctx(hdr) : GradAccCtx{1.0f, 1.0f, false};
     const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
     const float fx = flow[0];
     const float fy = flow[s2.c];
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
+    float* gfpx = (!BLEND || g3) ? g3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x : nullptr;
+    if constexpr (BLEND) {
+        float* gf0 = g2 ? g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x : nullptr;
+        if (!gsrc.any() || !fi_valid(fx, fy, x2, y2, w, h)) {
+            fi_bwd_zero_px(gf0, s2.c, gfpx, s3.c, fc);
+            return;
+        }
+        if (gfpx) for (int k = 0; k < fc; ++k) gfpx[(int64_t)k * s3.c] = 0.0f;     // (every filter channel, taps or not)
+    }
     if (!fi_valid(fx, fy, x2, y2, w, h)) return;           // no gradient (:2863-2864)
     const int ix = (int)x2, iy = (int)y2;
     const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
@@ -104,14 +144,13 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
     const float* img = in1 + (int64_t)b * s1.b;
     unsigned long long* gimg = acc + (int64_t)b * channel * h * w;       // dense [b][c][y][x] fixed-point sums
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
-    float* gfpx = g3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
-    const float* gpx = gout + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
+    const auto gpx = gsrc.row((int64_t)b * sg.b + (int64_t)y * sg.h + x);
     float gx = 0.0f, gy = 0.0f;
     for (int c = 0; c < channel; ++c) {
         const float* p = img + (int64_t)c * s1.c;
         unsigned long long* gp = gimg + (int64_t)c * h * w;
         float* gfp = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c;    // (the fp32 scatter of a call with non-finite inputs)
-        const float g = gpx[(int64_t)c * s1.c];
+        const float g = gpx[(int64_t)c * sg.c];
         const float qg[4] = { g * (1.0f - alpha) * (1.0f - beta), g * alpha * (1.0f - beta),
                               g * (1.0f - alpha) * beta,          g * alpha * beta };
         float q[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
@@ -128,8 +167,8 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
                     // image gradient: other pixels hit the same cell -> order-free fixed-point atomic (vfi_common.h).
                     // The filter gradient cell belongs to this thread alone (index is this pixel's own), so a plain
                     // read-modify-write is equivalent to the reference's atomicAdd.
-                    gradacc_add(gp, gfp, (int64_t)clampi(j, 0, h - 1) * w + clampi(i, 0, w - 1), o, qg[quad] * fv, gctx);
-                    gfpx[k] += qg[quad] * pv;
+                    if (wx) gradacc_add(gp, gfp, (int64_t)clampi(j, 0, h - 1) * w + clampi(i, 0, w - 1), o, qg[quad] * fv, gctx);
+                    if (!BLEND || gfpx) gfpx[k] += qg[quad] * pv;
                     acc = fmaf(pv, fv, acc);
                 }
             }
@@ -148,9 +187,19 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
             gy = fmaf(g, temp, gy);
         }
     }
-    float* gf = g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-    gf[0] = gx;
-    gf[s2.c] = gy;
+    if (!BLEND || g2) {
+        float* gf = g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
+        gf[0] = gx;
+        gf[s2.c] = gy;
+    }
+}
+
+__global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
+    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
+    const float* __restrict__ gout, unsigned long long* __restrict__ acc, const int* __restrict__ hdr, float* g1, float* g2, float* g3,
+    int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, const int* __restrict__ tileflag) {
+    fi_backward_ori_px<GradPlain, false, true>(in1, in2, in3, GradPlain{gout}, acc, hdr, g1, g2, g3, channel, h, w, fs, s1, s2, s3,
+                                               s1, tileflag, blockIdx.z, blockIdx.z);
 }
 
 // fs == 4, image values and image gradient through LDS (round 3).  The per-tap kernel above gathers 16 image values per
@@ -164,24 +213,31 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
 // the gradient cells in global memory once per channel and tap).  Every sum keeps the per-tap kernel's order and starting
 // value: its bits.  A call with non-finite inputs (fp32 atomics: vfi_common.h) and a tile whose window does not fit are
 // flagged, and fi_backward_ori, launched after this kernel, does those tiles only.  A tile with a large window takes two
-// channels, or one, per pass.
+// channels, or one, per pass.  Without the image gradient (WANT_X = false) the LDS holds the windows only; the channels per
+// pass stay those of the window budget (at C = 3 one pass covers every channel either way).
 typedef __attribute__((address_space(3))) void* fb_lptr_t;
 
-__global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
-    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
-    const float* __restrict__ gout, unsigned long long* __restrict__ acc, const int* __restrict__ hdr, int* __restrict__ tileflag,
-    float* g2, float* g3, int channel, int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3) {
+template <class G, bool BLEND, bool WANT_X>
+__device__ __forceinline__ void fi_backward_ori4_tile(
+    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3, G gsrc,
+    unsigned long long* __restrict__ acc, const int* __restrict__ hdr, int* __restrict__ tileflag, float* g1,
+    float* g2, float* g3, int channel, int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg, int b) {
     constexpr int fs = 4;
+    constexpr int NCELLS = WANT_X ? FB_CELLS : 0;
+    // channels per pass at most: the blend's instance with the image gradient holds two more 64-bit row pointers per pixel and
+    // spilled to scratch at the launch bound with three (72 B/lane) or two (20 B/lane); with one it needs 108 VGPRs and none.
+    // Every sum runs channel by channel whatever the pass size: the same bits.
+    constexpr int CH = (BLEND && WANT_X) ? 1 : FB_CH;
     // one array: header (bounding box), gradient cells, image windows -- FB_CELLS of each for a pass
-    __shared__ __attribute__((aligned(16))) unsigned long long lds64[2 + FB_CELLS + FB_CELLS / 2];
+    __shared__ __attribute__((aligned(16))) unsigned long long lds64[2 + NCELLS + FB_CELLS / 2];
     int* box = reinterpret_cast<int*>(lds64);
     unsigned long long* cells = lds64 + 2;
-    float* wins = reinterpret_cast<float*>(lds64 + 2 + FB_CELLS);
+    float* wins = reinterpret_cast<float*>(lds64 + 2 + NCELLS);
     const int tid = threadIdx.x;
     const int x = blockIdx.x * FB_TW + (tid & (FB_TW - 1));
     const int y = blockIdx.y * FB_TH + (tid >> 6);
-    const int b = blockIdx.z;
-    const GradAccCtx gctx = gradacc_ctx(hdr);
+    const bool wx = WANT_X && (!BLEND || g1 != nullptr);   // (uniform: this direction's image gradient is wanted)
+    const GradAccCtx gctx = wx ? gradacc_ctx(hdr) : GradAccCtx{1.0f, 1.0f, false};
     const bool inimg = x < w && y < h;
     float fx = 0.0f, fy = 0.0f;
     if (inimg) {
@@ -191,7 +247,12 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
     }
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
-    const bool valid = inimg && fi_valid(fx, fy, x2, y2, w, h);     // an invalid pixel has no gradient (:2863-2864)
+    const bool valid = inimg && gsrc.any() && fi_valid(fx, fy, x2, y2, w, h);     // an invalid pixel has no gradient (:2863-2864)
+    if constexpr (BLEND) {
+        if (inimg && !valid)
+            fi_bwd_zero_px(g2 ? g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x : nullptr, s2.c,
+                           g3 ? g3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x : nullptr, s3.c, 16);
+    }
     const int ix = valid ? (int)x2 : 0, iy = valid ? (int)y2 : 0;
     const int L = ix - 1, T = iy - 1;
     const float alpha = x2 - (float)ix;
@@ -215,11 +276,11 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
     const int bx0 = box[0], by0 = box[1], bw = box[2] - box[0] + 1, bh = box[3] - box[1] + 1;
     const int n = bw * bh;
     const int hs = (int)s1.h;
-    // channels per pass: as many (at most FB_CH) as fit the cells and the window slots -- a slot is the window rounded up to
+    // channels per pass: as many (at most CH) as fit the cells and the window slots -- a slot is the window rounded up to
     // whole DMA instructions, so that a window's last instruction stays inside its slot
     const int slot_floats = (n + FB_THREADS - 1) & ~(FB_THREADS - 1);
-    const int pc = min(FB_CH, FB_CELLS / slot_floats);
-    if (!gradacc_staged_ok(gctx) || pc == 0 || (int64_t)h * hs * 4 > INT_MAX) {     // (workgroup-uniform) left to fi_backward_ori
+    const int pc = min(CH, FB_CELLS / slot_floats);
+    if ((wx && !gradacc_staged_ok(gctx)) || pc == 0 || (int64_t)h * hs * 4 > INT_MAX) {     // (workgroup-uniform) left to fi_backward_ori
         if (tid == 0) tileflag[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = 1;
         return;
     }
@@ -228,10 +289,13 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
     unsigned long long* gimg = acc + (int64_t)b * channel * h * w;       // dense [b][c][y][x] fixed-point sums
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
     float* gfpx = g3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
-    const float* gpx = gout + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
+    const auto gpx = gsrc.row((int64_t)b * sg.b + (int64_t)y * sg.h + x);
     float fv[16], gf16[16];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) { fv[k] = valid ? fpx[(int64_t)k * s3.c] : 0.0f; gf16[k] = valid ? gfpx[(int64_t)k * s3.c] : 0.0f; }
+    for (int k = 0; k < 16; ++k) {
+        fv[k] = valid ? fpx[(int64_t)k * s3.c] : 0.0f;
+        gf16[k] = (valid && !BLEND) ? gfpx[(int64_t)k * s3.c] : 0.0f;
+    }
     int lrow[4];                                            // the window rows' first cells, less the box's first column
 #pragma unroll
     for (int k = 0; k < 4; ++k) lrow[k] = (ro[k] - by0) * bw - bx0;
@@ -254,16 +318,16 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fb_lptr_t)(slot + e0), 4, e < n ? 4u * (unsigned)((by0 + r) * hs + bx0 + col) : 0x80000000u, 0, 0, 0);
             }
         }
-        for (int e = tid; e < n * cn; e += FB_THREADS) cells[e] = 0ull;
-        float gv[FB_CH];
+        if (wx) for (int e = tid; e < n * cn; e += FB_THREADS) cells[e] = 0ull;
+        float gv[CH];
 #pragma unroll
-        for (int cc = 0; cc < FB_CH; ++cc) gv[cc] = (valid && cc < cn) ? gpx[(int64_t)(c0 + cc) * s1.c] : 0.0f;
+        for (int cc = 0; cc < CH; ++cc) gv[cc] = (valid && cc < cn) ? gpx[(int64_t)(c0 + cc) * sg.c] : 0.0f;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (valid) {
-            float qg[FB_CH][4], q[FB_CH][4];
+            float qg[CH][4], q[CH][4];
 #pragma unroll
-            for (int cc = 0; cc < FB_CH; ++cc) {
+            for (int cc = 0; cc < CH; ++cc) {
                 const float g = gv[cc];
                 qg[cc][0] = g * (1.0f - alpha) * (1.0f - beta); qg[cc][1] = g * alpha * (1.0f - beta);
                 qg[cc][2] = g * (1.0f - alpha) * beta;          qg[cc][3] = g * alpha * beta;
@@ -279,17 +343,17 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
                         const int j = (quad >> 1) * 2 + jj, i = (quad & 1) * 2 + ii, k = j * fs + i;
                         const int cell = lrow[j] + co[i];
 #pragma unroll
-                        for (int cc = 0; cc < FB_CH; ++cc) {
+                        for (int cc = 0; cc < CH; ++cc) {
                             if (cc < cn) {                  // (workgroup-uniform)
                                 const float pv = wins[cc * slot_floats + cell];
-                                atomicAdd(&cells[cc * n + cell], (unsigned long long)__float2ll_rn(qg[cc][quad] * fv[k] * gctx.scale));
+                                if (wx) atomicAdd(&cells[cc * n + cell], (unsigned long long)__float2ll_rn(qg[cc][quad] * fv[k] * gctx.scale));
                                 gf16[k] += qg[cc][quad] * pv;
                                 q[cc][quad] = fmaf(pv, fv[k], q[cc][quad]);
                             }
                         }
                     }
 #pragma unroll
-            for (int cc = 0; cc < FB_CH; ++cc) {
+            for (int cc = 0; cc < CH; ++cc) {
                 if (cc < cn) {
                     const float g = gv[cc];
                     {   // flow gradient by quadrant differences (:2965-3102)
@@ -308,23 +372,59 @@ __global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
             }
         }
         __syncthreads();
-        for (int e = tid; e < n * cn; e += FB_THREADS) {
-            const unsigned long long v = cells[e];
-            if (v != 0ull) {
-                const int cc = e / n, r = e - cc * n;
-                const int cy = r / bw, cx = r - cy * bw;
-                atomicAdd(&gimg[(int64_t)(c0 + cc) * h * w + (int64_t)(by0 + cy) * w + bx0 + cx], v);
+        if (wx) {
+            for (int e = tid; e < n * cn; e += FB_THREADS) {
+                const unsigned long long v = cells[e];
+                if (v != 0ull) {
+                    const int cc = e / n, r = e - cc * n;
+                    const int cy = r / bw, cx = r - cy * bw;
+                    atomicAdd(&gimg[(int64_t)(c0 + cc) * h * w + (int64_t)(by0 + cy) * w + bx0 + cx], v);
+                }
             }
+            __syncthreads();                                // (the next pass overwrites windows and cells)
         }
-        __syncthreads();                                    // (the next pass overwrites windows and cells)
     }
     if (valid) {
+        if (!BLEND || g3) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) gfpx[(int64_t)k * s3.c] = gf16[k];
-        float* gf = g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-        gf[0] = gx;
-        gf[s2.c] = gy;
+            for (int k = 0; k < 16; ++k) gfpx[(int64_t)k * s3.c] = gf16[k];
+        }
+        if (!BLEND || g2) {
+            float* gf = g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
+            gf[0] = gx;
+            gf[s2.c] = gy;
+        }
     }
+}
+
+__global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_backward_ori4_lds(
+    const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
+    const float* __restrict__ gout, unsigned long long* __restrict__ acc, const int* __restrict__ hdr, int* __restrict__ tileflag,
+    float* g2, float* g3, int channel, int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3) {
+    fi_backward_ori4_tile<GradPlain, false, true>(in1, in2, in3, GradPlain{gout}, acc, hdr, tileflag, nullptr, g2, g3, channel, h,
+                                                  w, s1, s2, s3, s1, blockIdx.z);
+}
+
+// vfi_filterinterp_blend_backward: both directions in one launch (grid z = direction * batch + b), on the bodies above.
+// Refs and their gradients use s1, flows s2, filters s3, the gradient terms sg.
+template <bool WANT_X>
+__global__ __launch_bounds__(FB_THREADS, FB_WAVES) void fi_blend_backward4_lds(
+    FiBwdPair pr, int* __restrict__ tileflag, int batch, int channel, int h, int w,
+    vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg) {
+    const int dir = (int)blockIdx.z >= batch;
+    const FiBwdSide& d = dir ? pr.d[1] : pr.d[0];
+    fi_backward_ori4_tile<GradTerms, true, WANT_X>(d.ref, d.flow, d.filt, d.g, d.acc, d.hdr, tileflag, d.gref, d.gflow, d.gfilt,
+                                                   channel, h, w, s1, s2, s3, sg, (int)blockIdx.z - dir * batch);
+}
+
+template <bool WANT_X>
+__global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_blend_backward_general(
+    FiBwdPair pr, const int* __restrict__ tileflag, int batch, int channel, int h, int w, int fs, int fc,
+    vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg) {
+    const int dir = (int)blockIdx.z >= batch;
+    const FiBwdSide& d = dir ? pr.d[1] : pr.d[0];
+    fi_backward_ori_px<GradTerms, true, WANT_X>(d.ref, d.flow, d.filt, d.g, d.acc, d.hdr, d.gref, d.gflow, d.gfilt, channel, h, w,
+                                                fs, s1, s2, s3, sg, tileflag, (int)blockIdx.z - dir * batch, blockIdx.z, fc);
 }
 
 // ------------------------------------------------------------------ forward, deformable variants
@@ -723,6 +823,72 @@ extern "C" int vfi_filterinterp_backward_ori(const float* input1, const float* i
                        channel, h, w, fs, s1, s2, s3, fs == 4 ? flags : nullptr);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     return gradacc_finish((hipStream_t)stream, acc, hdr, gradinput1, batch, channel, h, w, s1);
+}
+
+extern "C" int vfi_filterinterp_blend_backward(const float* ref0, const float* ref2, const float* flow0, const float* flow2,
+                                                const float* filt0, const float* filt2, const float* grad_blend,
+                                                const float* grad_out0, const float* grad_out2, float* grad_ref0, float* grad_ref2,
+                                                float* grad_flow0, float* grad_flow2, float* grad_filt0, float* grad_filt2,
+                                                int batch, int channel, int h, int w, int filter_channels, float w0, float w2,
+                                                vfi_strides s_ref, vfi_strides s_flow, vfi_strides s_filt, vfi_strides s_grad,
+                                                vfi_stream_t stream) {
+    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
+    if (!ref0 || !ref2 || !flow0 || !flow2 || !filt0 || !filt2) return VFI_ERR_SHAPE;
+    if (!grad_ref0 && !grad_ref2 && !grad_flow0 && !grad_flow2 && !grad_filt0 && !grad_filt2) return VFI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int fs = fi_filter_size(filter_channels);
+    // the staged kernel for fs == 4 with exactly its 16 filter channels (it writes 16); any other count: per pixel, which
+    // writes every channel of a requested filter gradient
+    const bool staged = fs == 4 && filter_channels == 16;
+    const bool want_x = grad_ref0 || grad_ref2;
+    FiBwdPair pr;
+    pr.d[0] = FiBwdSide{ref0, flow0, filt0, GradTerms{grad_blend, grad_out0, w0}, nullptr, nullptr, grad_ref0, grad_flow0, grad_filt0};
+    pr.d[1] = FiBwdSide{ref2, flow2, filt2, GradTerms{grad_blend, grad_out2, w2}, nullptr, nullptr, grad_ref2, grad_flow2, grad_filt2};
+    // scratch of WS_GRADACC: [header 0][header 1][sums 0][sums 1] when the image gradient is wanted, then one flag word per
+    // 64 x 8 tile of both directions (staged), all zeroed on the stream
+    const int64_t n = (int64_t)batch * channel * h * w;
+    const int ntiles = staged ? ((w + FB_TW - 1) / FB_TW) * ((h + FB_TH - 1) / FB_TH) * 2 * batch : 0;
+    const size_t xbytes = want_x ? 512 + (size_t)n * 16 : 0;
+    const size_t bytes = xbytes + (size_t)ntiles * 4;
+    int* flags = nullptr;
+    if (bytes) {
+        char* p = static_cast<char*>(ws_get(st, WS_GRADACC, bytes, false, nullptr));
+        if (!p) return VFI_ERR_LAUNCH;
+        if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) return VFI_ERR_LAUNCH;
+        if (ntiles) flags = reinterpret_cast<int*>(p + xbytes);
+        if (want_x)
+            for (int d = 0; d < 2; ++d) {
+                pr.d[d].hdr = reinterpret_cast<const int*>(p + 256 * d);
+                pr.d[d].acc = reinterpret_cast<unsigned long long*>(p + 512 + (size_t)n * 8 * d);
+            }
+    }
+    if (want_x)
+        for (int d = 0; d < 2; ++d) {
+            const FiBwdSide& sd = pr.d[d];
+            if (!sd.gref) continue;
+            // the fixed-point scale from the direction's own gradient as the kernels form it, and its filter
+            if (sd.g.any() && gradacc_scan_terms(st, sd.g, batch, channel, h, w, s_grad, sd.filt, filter_channels, s_filt,
+                                                 const_cast<int*>(sd.hdr)) != VFI_OK)
+                return VFI_ERR_LAUNCH;
+            if (gradacc_zero_fp32(st, sd.hdr, sd.gref, batch, channel, h, w, s_ref) != VFI_OK) return VFI_ERR_LAUNCH;
+        }
+    const dim3 tiles((w + FB_TW - 1) / FB_TW, (h + FB_TH - 1) / FB_TH, 2 * batch);
+    const dim3 px = pixel_grid(w, h, 2 * batch), pxb(VFI_TX, VFI_TY, 1);
+    if (staged) {
+        if (want_x) hipLaunchKernelGGL(fi_blend_backward4_lds<true>, tiles, dim3(FB_THREADS), 0, st, pr, flags, batch, channel, h, w,
+                                       s_ref, s_flow, s_filt, s_grad);
+        else hipLaunchKernelGGL(fi_blend_backward4_lds<false>, tiles, dim3(FB_THREADS), 0, st, pr, flags, batch, channel, h, w,
+                                s_ref, s_flow, s_filt, s_grad);
+    }
+    if (want_x) hipLaunchKernelGGL(fi_blend_backward_general<true>, px, pxb, 0, st, pr, flags, batch, channel, h, w, fs,
+                                   filter_channels, s_ref, s_flow, s_filt, s_grad);
+    else hipLaunchKernelGGL(fi_blend_backward_general<false>, px, pxb, 0, st, pr, flags, batch, channel, h, w, fs, filter_channels,
+                            s_ref, s_flow, s_filt, s_grad);
+    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
+    for (int d = 0; d < 2 && want_x; ++d)
+        if (pr.d[d].gref && gradacc_finish_overwrite(st, pr.d[d].acc, pr.d[d].hdr, pr.d[d].gref, batch, channel, h, w, s_ref) != VFI_OK)
+            return VFI_ERR_LAUNCH;
+    return VFI_OK;
 }
 
 extern "C" int vfi_filterinterp_forward_defor_lds(int variant, const float* input1, const float* input2,

@@ -140,6 +140,42 @@ int gradacc_begin(hipStream_t st, const float* gout, int batch, int channel, int
 int gradacc_finish(hipStream_t st, const unsigned long long* acc, const int* hdr, float* g1, int batch, int channel, int h, int w,
                    vfi_strides s1);
 
+// The incoming gradient of one direction of the blend's backward (vfi_filterinterp_blend_backward), formed in registers where
+// it is read: g = gb * wgt + go, the product and the sum rounded separately (torch autograd's accumulation for
+// out * w + <another use of out>).  A NULL term is absent; with both NULL the direction has no gradient.
+// row(o): the gradient from element o on, indexed like a pointer (a plain gradient's row is the pointer itself: GradPlain).
+struct GradTerms {
+    const float* gb;
+    const float* go;
+    float wgt;
+    struct Row {
+        const float* gb;
+        const float* go;
+        float wgt;
+        __device__ __forceinline__ float operator[](int64_t o) const {
+            if (!gb) return go[o];
+            const float v = gb[o] * wgt;
+            return go ? v + go[o] : v;
+        }
+    };
+    __host__ __device__ bool any() const { return gb != nullptr || go != nullptr; }
+    __device__ __forceinline__ Row row(int64_t o) const { return Row{gb ? gb + o : nullptr, go ? go + o : nullptr, wgt}; }
+};
+struct GradPlain {
+    const float* __restrict__ g;
+    __host__ __device__ bool any() const { return true; }
+    __device__ __forceinline__ const float* row(int64_t o) const { return g + o; }
+};
+// The blend backward's scratch on hdr / acc laid out by the caller (one header and one accumulator per direction):
+//   gradacc_scan_terms: gradacc_begin's max-scans of g (formed as above) and of the weights, into a zeroed header
+//   gradacc_zero_fp32:  zero the caller's gradient when the call scatters with fp32 atomics (the caller does not zero it)
+//   gradacc_finish_overwrite: gradacc_finish that WRITES every cell (0 where the sum is 0) instead of adding
+int gradacc_scan_terms(hipStream_t st, GradTerms g, int batch, int channel, int h, int w, vfi_strides sg,
+                       const float* weights, int wchannel, vfi_strides sw, int* hdr);
+int gradacc_zero_fp32(hipStream_t st, const int* hdr, float* g1, int batch, int channel, int h, int w, vfi_strides s1);
+int gradacc_finish_overwrite(hipStream_t st, const unsigned long long* acc, const int* hdr, float* g1, int batch, int channel,
+                             int h, int w, vfi_strides s1);
+
 inline int launch_status() {
     return hipGetLastError() == hipSuccess ? VFI_OK : VFI_ERR_LAUNCH;
 }

@@ -90,7 +90,9 @@ bool ws_get_group(hipStream_t stream, const WsSlot* slots, const size_t* bytes, 
 // ---- deterministic image gradients (vfi_common.h)
 // largest |element| of a [batch, channel, h, w] tensor into hdr[slot] (non-negative floats order like their bits); a NaN or an
 // infinity raises hdr[1]
-__global__ __launch_bounds__(256) void gradacc_max(const float* __restrict__ g, int channel, int h, int w, vfi_strides sg, int64_t n,
+// G: a plain tensor (GradPlain) or the two terms of the blend backward's gradient (GradTerms, formed as its kernels form it)
+template <class G>
+__global__ __launch_bounds__(256) void gradacc_max(G g, int channel, int h, int w, vfi_strides sg, int64_t n,
                                                    int* __restrict__ hdr, int slot, int cells_log2) {
     int m = 0;
     bool bad = false;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256) void gradacc_max(const float* __restrict__ g, 
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
         const int y = row % h, bc = row / h;
         const int c = bc % channel, b = bc / channel;
-        const float* p = g + (int64_t)b * sg.b + (int64_t)c * sg.c + (int64_t)y * sg.h;
+        const auto p = g.row((int64_t)b * sg.b + (int64_t)c * sg.c + (int64_t)y * sg.h);
         for (int x = threadIdx.x; x < w; x += 256) {
             const int bits = __float_as_int(fabsf(p[x]));
             bad = bad || bits >= 0x7f800000;                // infinity or NaN
@@ -124,6 +126,8 @@ __global__ __launch_bounds__(256) void gradacc_max(const float* __restrict__ g, 
     if (blockIdx.x == 0 && threadIdx.x == 0 && slot == 0) hdr[3] = cells_log2;
 }
 
+// OVERWRITE: every cell of g1 is written (the blend backward's caller does not zero its gradient); else added into
+template <bool OVERWRITE>
 __global__ __launch_bounds__(256) void gradacc_convert(const unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
                                                        float* __restrict__ g1, int channel, int h, int w, vfi_strides s1, int64_t n) {
     if (gradacc_fp32(hdr)) return;                          // the call scattered with fp32 atomics: nothing in the scratch
@@ -136,8 +140,22 @@ __global__ __launch_bounds__(256) void gradacc_convert(const unsigned long long*
         float* cells = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c + (int64_t)y * s1.h;
         for (int x = threadIdx.x; x < w; x += 256) {
             const long long sum = (long long)a[x];
-            if (sum != 0) cells[x] += (float)ldexp((double)sum, -k);    // exact integer sum -> float once
+            if constexpr (OVERWRITE) cells[x] = sum != 0 ? (float)ldexp((double)sum, -k) : 0.0f;    // (0 + v: the bits of v)
+            else if (sum != 0) cells[x] += (float)ldexp((double)sum, -k);    // exact integer sum -> float once
         }
+    }
+}
+
+// before an fp32 scatter into a gradient the caller has not zeroed: zero it (nothing to do on the integer path)
+__global__ __launch_bounds__(256) void gradacc_zero_fp32_k(const int* __restrict__ hdr, float* __restrict__ g1, int channel, int h,
+                                                           int w, vfi_strides s1, int64_t n) {
+    if (!gradacc_fp32(hdr)) return;
+    const int rows = (int)(n / w);
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int y = row % h, bc = row / h;
+        const int c = bc % channel, b = bc / channel;
+        float* cells = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c + (int64_t)y * s1.h;
+        for (int x = threadIdx.x; x < w; x += 256) cells[x] = 0.0f;
     }
 }
 
@@ -160,13 +178,43 @@ int gradacc_begin(hipStream_t st, const float* gout, int batch, int channel, int
     while (((int64_t)1 << cells_log2) < (int64_t)h * w * taps) ++cells_log2;
     const int64_t rows = n / w;
     const int blocks = (int)(rows < 2048 ? rows : 2048);
-    hipLaunchKernelGGL(gradacc_max, dim3(blocks), dim3(256), 0, st, gout, channel, h, w, sg, n, *hdr, 0, cells_log2);
+    hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(blocks), dim3(256), 0, st, GradPlain{gout}, channel, h, w, sg, n, *hdr, 0,
+                       cells_log2);
     if (weights) {
         const int64_t nw = (int64_t)batch * wchannel * h * w;
         const int64_t wrows = nw / w;
         const int wblocks = (int)(wrows < 2048 ? wrows : 2048);
-        hipLaunchKernelGGL(gradacc_max, dim3(wblocks), dim3(256), 0, st, weights, wchannel, h, w, sw, nw, *hdr, 2, cells_log2);
+        hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(wblocks), dim3(256), 0, st, GradPlain{weights}, wchannel, h, w, sw, nw,
+                           *hdr, 2, cells_log2);
     }
+    return launch_status();
+}
+
+// gradacc_begin's scans with the gradient formed from its two terms (same header words, same cells_log2 rule)
+int gradacc_scan_terms(hipStream_t st, GradTerms g, int batch, int channel, int h, int w, vfi_strides sg,
+                       const float* weights, int wchannel, vfi_strides sw, int* hdr) {
+    const int64_t n = (int64_t)batch * channel * h * w;
+    const int64_t taps = wchannel > 4 ? wchannel : 4;
+    int cells_log2 = 0;
+    while (((int64_t)1 << cells_log2) < (int64_t)h * w * taps) ++cells_log2;
+    const int64_t rows = n / w;
+    const int blocks = (int)(rows < 2048 ? rows : 2048);
+    hipLaunchKernelGGL(gradacc_max<GradTerms>, dim3(blocks), dim3(256), 0, st, g, channel, h, w, sg, n, hdr, 0, cells_log2);
+    if (weights) {
+        const int64_t nw = (int64_t)batch * wchannel * h * w;
+        const int64_t wrows = nw / w;
+        const int wblocks = (int)(wrows < 2048 ? wrows : 2048);
+        hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(wblocks), dim3(256), 0, st, GradPlain{weights}, wchannel, h, w, sw, nw,
+                           hdr, 2, cells_log2);
+    }
+    return launch_status();
+}
+
+int gradacc_zero_fp32(hipStream_t st, const int* hdr, float* g1, int batch, int channel, int h, int w, vfi_strides s1) {
+    const int64_t n = (int64_t)batch * channel * h * w;
+    const int64_t rows = n / w;
+    const int blocks = (int)(rows < 2048 ? rows : 2048);
+    hipLaunchKernelGGL(gradacc_zero_fp32_k, dim3(blocks), dim3(256), 0, st, hdr, g1, channel, h, w, s1, n);
     return launch_status();
 }
 
@@ -175,7 +223,16 @@ int gradacc_finish(hipStream_t st, const unsigned long long* acc, const int* hdr
     const int64_t n = (int64_t)batch * channel * h * w;
     const int64_t rows = n / w;
     const int blocks = (int)(rows < 8192 ? rows : 8192);
-    hipLaunchKernelGGL(gradacc_convert, dim3(blocks), dim3(256), 0, st, acc, hdr, g1, channel, h, w, s1, n);
+    hipLaunchKernelGGL(gradacc_convert<false>, dim3(blocks), dim3(256), 0, st, acc, hdr, g1, channel, h, w, s1, n);
+    return launch_status();
+}
+
+int gradacc_finish_overwrite(hipStream_t st, const unsigned long long* acc, const int* hdr, float* g1, int batch, int channel,
+                             int h, int w, vfi_strides s1) {
+    const int64_t n = (int64_t)batch * channel * h * w;
+    const int64_t rows = n / w;
+    const int blocks = (int)(rows < 8192 ? rows : 8192);
+    hipLaunchKernelGGL(gradacc_convert<true>, dim3(blocks), dim3(256), 0, st, acc, hdr, g1, channel, h, w, s1, n);
     return launch_status();
 }
 

@@ -2,8 +2,13 @@
 points of libvfi_hip.so.  Same names and argument meaning as the reference's static helpers
 (`networks/DAIN_slowmotion.py:204-216, 301-335`, `PWCNet/PWCNet.py:159-199`,
 `demo_MiddleBury.py:280-318, 350-388`).  `warp` and `warp_corr` are differentiable (PWC-Net's glue, trained with
-the flow network: the backward is vfi_pwc_warp_backward, and for `warp_corr` also the correlation backward); the rest
-is inference only (no autograd)."""
+the flow network: the backward is vfi_pwc_warp_backward, and for `warp_corr` also the correlation backward).
+`FlowProject` / `FlowProject_directions` and `FilterInterpolate` are differentiable too, so DAIN's synthesis loss reaches
+the flow and filter networks (networks/DAIN.py:215-238): the projection's backward is the reference's per-item kernel,
+the blend's is vfi_filterinterp_blend_backward (both directions, the blend weights folded in, no image gradient unless
+a frame requires grad).  Each takes its autograd Function only when grad mode is on and an input requires grad; otherwise
+it is the plain forward launch, with no grad_fn.  The rest (`FlowProject_from_quarter`, `forward_flownets_upsample`,
+`FilterInterpolate_ctx_all`, the frame glue) is inference only."""
 import math
 
 import torch
@@ -75,17 +80,66 @@ def forward_flownets_upsample(flow_q, div_flow, time_offsets):
     return outs
 
 
+def _flow_project_launch(inputs, depth, fillhole):
+    counts = [torch.empty((f.size(0), 1, f.size(2), f.size(3)), device=f.device, dtype=torch.float32) for f in inputs]
+    outs = [torch.empty_strided(f.shape, f.stride(), device=f.device, dtype=torch.float32) for f in inputs]
+    _check(cabi.flowprojection_forward_batch(inputs, counts, outs, int(fillhole), depth), "flowprojection_forward_batch")
+    return counts, outs
+
+
+class _FlowProject(torch.autograd.Function):
+    """The list form of FlowProjectionLayer / DepthFlowProjectionLayer: the forward is the one list call, the backward the
+    reference's per-item kernel into zero-filled gradients (it ignores fillhole, as the reference's does).  A depth tensor
+    shared by several items appears once per item among the inputs, and autograd sums its gradients."""
+
+    @staticmethod
+    def forward(ctx, fillhole, n, *tensors):
+        flows, depths = list(tensors[:n]), (list(tensors[n:]) or None)
+        counts, outs = _flow_project_launch(flows, depths, fillhole)
+        ctx.n, ctx.has_depth = n, depths is not None
+        ctx.save_for_backward(*flows, *counts, *(depths + outs if depths is not None else []))
+        ctx.set_materialize_grads(False)                   # (an unused output gets no backward, as with one module per item)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        n, saved = ctx.n, ctx.saved_tensors
+        flows, counts = saved[:n], saved[n:2 * n]
+        gflows, gdepths = [None] * n, [None] * n
+        for i in range(n):
+            if grads[i] is None:
+                continue
+            f, g = flows[i].contiguous(), grads[i].contiguous()        # (the reference's layers take contiguous tensors)
+            gf = torch.zeros_like(f)
+            if not ctx.has_depth:
+                _check(cabi.flowprojection_backward(f, counts[i], g, gf), "flowprojection_backward")
+            else:
+                d, out = saved[2 * n + i].contiguous(), saved[3 * n + i].contiguous()
+                gd = torch.zeros_like(d)
+                _check(cabi.depthflowprojection_backward(f, d, counts[i], out, g, gf, gd), "depthflowprojection_backward")
+                gdepths[i] = gd if ctx.needs_input_grad[2 + n + i] else None
+            gflows[i] = gf if ctx.needs_input_grad[2 + i] else None
+        return (None, None, *gflows, *(gdepths if ctx.has_depth else []))
+
+
 def FlowProject(inputs, depth=None, fillhole=True):
     """`DAIN.FlowProject` / `DAIN_slowmotion.FlowProject` (networks/DAIN.py:533-539, networks/DAIN_slowmotion.py:301-307):
     inputs = the list of full-resolution flows of `forward_flownets`, depth = the direction's inverse depth (or None);
     returns the list of projected flows.  The reference loops over the list, one module call per flow; here the list is
     ONE call of the library (one launch triple per eight flows), same results bit for bit.  depth may also be a list, one
-    tensor per flow -- which is how both directions go through together: `FlowProject_directions`."""
+    tensor per flow -- which is how both directions go through together: `FlowProject_directions`.
+    Differentiable when grad mode is on and a flow or depth requires grad: the gradients are those of the reference's
+    per-item `FlowProjectionModule` / `DepthFlowProjectionModule` graph, a shared depth getting the sum of its items'.  The
+    reference trains with fillhole=0 (`FlowProjectionModule(input.requires_grad)`, networks/DAIN.py:218); fillhole keeps
+    its meaning in the forward, and the backward ignores it, as the reference's does."""
     inputs = list(inputs)
-    counts = [torch.empty((f.size(0), 1, f.size(2), f.size(3)), device=f.device, dtype=torch.float32) for f in inputs]
-    outs = [torch.empty_strided(f.shape, f.stride(), device=f.device, dtype=torch.float32) for f in inputs]
-    _check(cabi.flowprojection_forward_batch(inputs, counts, outs, int(fillhole), depth), "flowprojection_forward_batch")
-    return outs
+    depths = None if depth is None else (list(depth) if isinstance(depth, (list, tuple)) else [depth] * len(inputs))
+    if _wants_grad(*inputs, *(depths or [])):
+        if depths is not None and len(depths) != len(inputs):
+            _check(1, "flowprojection_forward_batch")
+        return list(_FlowProject.apply(bool(fillhole), len(inputs), *inputs, *(depths or [])))
+    return _flow_project_launch(inputs, depth, fillhole)[1]
 
 
 def FlowProject_directions(cur_offset_outputs, depth_inv=None, fillhole=True):
@@ -115,13 +169,61 @@ def FlowProject_from_quarter(flow_q, div_flow, time_offsets, depth=None, fillhol
     return outs
 
 
-def FilterInterpolate(ref0, ref2, offset, filter, filter_size2, time_offset):
-    """`DAIN.FilterInterpolate`: returns (ref0_offset*(1-t) + ref2_offset*t, ref0_offset, ref2_offset)."""
-    assert filter[0].size(1) == filter_size2
+def _filter_interpolate_launch(ref0, ref2, off0, off2, filt0, filt2, w0, w2):
     blend, out0, out2 = torch.empty_like(ref0), torch.empty_like(ref0), torch.empty_like(ref0)
-    _check(cabi.filterinterp_blend_forward(ref0, ref2, offset[0], offset[1], filter[0], filter[1], blend, out0, out2,
-                                           float(1.0 - time_offset), float(time_offset)), "filterinterp_blend_forward")
+    _check(cabi.filterinterp_blend_forward(ref0, ref2, off0, off2, filt0, filt2, blend, out0, out2, w0, w2),
+           "filterinterp_blend_forward")
     return blend, out0, out2
+
+
+def _grad_layout(grads):
+    """The incoming gradients share one dense layout for the kernel (an expanded gradient of a sum(), or one laid out
+    unlike the others, is made contiguous)."""
+    live = [g for g in grads if g is not None]
+    if not live:
+        return grads
+    ref = live[0]
+    if ref.stride(3) != 1 or 0 in ref.stride() or not all(cabi._same_strides(ref, g) for g in live):
+        return [g.contiguous() if g is not None else None for g in grads]
+    return grads
+
+
+class _FilterInterpolate(torch.autograd.Function):
+    """`DAIN.FilterInterpolate` with the gradients of FilterInterpolationModule on both frames plus torch's blend: one
+    forward launch, one backward call (vfi_filterinterp_blend_backward)."""
+
+    @staticmethod
+    def forward(ctx, ref0, ref2, off0, off2, filt0, filt2, w0, w2):
+        blend, out0, out2 = _filter_interpolate_launch(ref0, ref2, off0, off2, filt0, filt2, w0, w2)
+        ctx.save_for_backward(ref0, ref2, off0, off2, filt0, filt2)
+        ctx.w = (w0, w2)
+        ctx.set_materialize_grads(False)                   # (an unused output is an absent term, not a tensor of zeros)
+        return blend, out0, out2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_blend, g_out0, g_out2):
+        saved = ctx.saved_tensors
+        g_blend, g_out0, g_out2 = _grad_layout([g_blend, g_out0, g_out2])
+        outs = [torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) if need else None
+                for t, need in zip(saved, ctx.needs_input_grad[:6])]
+        if any(o is not None for o in outs):
+            gr0, gr2, gf0, gf2, gk0, gk2 = outs
+            _check(cabi.filterinterp_blend_backward(*saved, g_blend, g_out0, g_out2, ctx.w[0], ctx.w[1], gr0, gr2, gf0, gf2,
+                                                    gk0, gk2), "filterinterp_blend_backward")
+        return (*outs, None, None)
+
+
+def FilterInterpolate(ref0, ref2, offset, filter, filter_size2, time_offset):
+    """`DAIN.FilterInterpolate`: returns (ref0_offset*(1-t) + ref2_offset*t, ref0_offset, ref2_offset).  Differentiable
+    when grad mode is on and a frame, flow or filter requires grad (time_offset is a Python float, with no gradient):
+    the gradients equal those of two `FilterInterpolationModule` calls plus torch's blend, bit for bit.  Otherwise the
+    plain forward launch."""
+    assert filter[0].size(1) == filter_size2
+    w0, w2 = float(1.0 - time_offset), float(time_offset)
+    if _wants_grad(ref0, ref2, *offset, *filter):
+        return _FilterInterpolate.apply(ref0, ref2, offset[0], offset[1], filter[0], filter[1], w0, w2)
+    return _filter_interpolate_launch(ref0, ref2, offset[0], offset[1], filter[0], filter[1], w0, w2)
 
 
 def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
