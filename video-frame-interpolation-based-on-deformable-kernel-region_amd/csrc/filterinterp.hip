@@ -11,6 +11,7 @@
 // The LDS-staged forward for fs == 4 lives in filterinterp_lds.hip and falls
 // back to the kernel here when a tile's tap window does not fit its LDS budget.
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 #include "workspace.h"
 
 #include <limits.h>
@@ -748,17 +749,6 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_defor(
 
 using namespace vfi;
 
-// defined in filterinterp_lds.hip; returns VFI_OK / VFI_ERR_LAUNCH, or -1 when it declines the shape
-extern "C" int vfi_filterinterp_forward_ori_lds_n(const float* input1, const float* input2, const float* input3,
-                                                   float* output, int batch, int channel, int h, int w, int fs,
-                                                   vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                                                   vfi_stream_t stream);
-extern "C" int vfi_filterinterp_forward_ori_lds(const float*, const float*, const float*, float*,
-                                                 int, int, int, int, vfi_strides, vfi_strides, vfi_strides,
-                                                 vfi_stream_t);
-
-static int fi_filter_size(int filter_channels) { return (int)sqrtf((float)filter_channels); }
-
 extern "C" int vfi_filterinterp_forward_ori_direct(const float* input1, const float* input2, const float* input3,
                                                     float* output, int batch, int channel, int h, int w,
                                                     int filter_channels, vfi_strides s1, vfi_strides s2,
@@ -785,13 +775,11 @@ extern "C" int vfi_filterinterp_forward_ori(const float* input1, const float* in
     if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
     const int fs = fi_filter_size(filter_channels);
     if (fs == 4) {
-        const int r = vfi_filterinterp_forward_ori_lds(input1, input2, input3, output, batch, channel, h, w,
-                                                       s1, s2, s3, stream);
-        if (r != -1) return r;
+        const int r = launch_fi_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream);
+        if (r != FI_DECLINED) return r;
     } else if (fs * fs == filter_channels) {
-        const int r = vfi_filterinterp_forward_ori_lds_n(input1, input2, input3, output, batch, channel, h, w, fs,
-                                                         s1, s2, s3, stream);
-        if (r != -1) return r;
+        const int r = launch_fi_ori_lds_n(input1, input2, input3, output, batch, channel, h, w, fs, s1, s2, s3, stream);
+        if (r != FI_DECLINED) return r;
     }
     return vfi_filterinterp_forward_ori_direct(input1, input2, input3, output, batch, channel, h, w,
                                                filter_channels, s1, s2, s3, stream);
@@ -891,12 +879,6 @@ extern "C" int vfi_filterinterp_blend_backward(const float* ref0, const float* r
     return VFI_OK;
 }
 
-extern "C" int vfi_filterinterp_forward_defor_lds(int variant, const float* input1, const float* input2,
-                                                   const float* input3, const float* input4, float* output,
-                                                   int batch, int channel, int h, int w, int filter_size,
-                                                   vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides s4,
-                                                   vfi_stream_t stream);
-
 static int defor_forward(bool allow_staged, int variant, const float* input1, const float* input2,
                          const float* input3, const float* input4, float* output,
                          int batch, int channel, int h, int w, int filter_size,
@@ -908,10 +890,10 @@ static int defor_forward(bool allow_staged, int variant, const float* input1, co
     const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
     hipStream_t st = (hipStream_t)stream;
     if ((filter_size == 4 || filter_size == 6) && allow_staged && variant >= 0 && variant <= 2) {
-        // LDS-staged kernel (filterinterp_defor_lds.hip); -1 = not applicable
-        const int err = vfi_filterinterp_forward_defor_lds(variant, input1, input2, input3, input4, output, batch,
-                                                           channel, h, w, filter_size, s1, s2, s3, s4, stream);
-        if (err >= 0) return err;
+        // the LDS-staged kernel; when it declines the shape, and also when its launch fails, the general kernel below runs
+        const int err = launch_fi_defor_lds(variant, input1, input2, input3, input4, output, batch, channel, h, w, filter_size,
+                                            s1, s2, s3, s4, stream);
+        if (err == VFI_OK) return VFI_OK;
     }
     switch (variant) {
     case VFI_DEFOR_OFFSET:
@@ -954,13 +936,6 @@ extern "C" int vfi_filterinterp_forward_defor_general(int variant, const float* 
                          s4, stream);
 }
 
-// defined in filterinterp_defor_bwd_lds.hip
-extern "C" int vfi_filterinterp_backward_defor_lds(int variant, const float* input1, const float* input2, const float* input3,
-                                                    const float* input4, const float* gradoutput, unsigned long long* acc,
-                                                    const int* hdr, int* flags, float* gradinput2, float* gradinput3,
-                                                    float* gradinput4, int batch, int channel, int h, int w, vfi_strides s1,
-                                                    vfi_strides s2, vfi_strides s3, vfi_strides s4, vfi_stream_t stream);
-
 extern "C" int vfi_filterinterp_backward_defor(int variant, const float* input1, const float* input2,
                                                 const float* input3, const float* input4, const float* gradoutput,
                                                 float* gradinput1, float* gradinput2, float* gradinput3,
@@ -980,29 +955,39 @@ extern "C" int vfi_filterinterp_backward_defor(int variant, const float* input1,
     const int err = gradacc_begin(st, gradoutput, batch, channel, h, w, s1, variant == VFI_DEFOR_NOFILTER ? nullptr : input3,
                                   filter_size * filter_size, s3, &acc, &hdr, (int)(grid.x * grid.y * grid.z), &flags);
     if (err != VFI_OK) return err;
-#define FD_LAUNCH2(V, F, I3, I4, G3, G4, S4) \
-        hipLaunchKernelGGL((fi_backward_defor<V, true, F>), grid, block, 0, st, input1, input2, I3, I4, gradoutput, acc, hdr, flags, \
-                           gradinput1, gradinput2, G3, G4, channel, h, w, filter_size, s1, s2, s3, S4); \
-        hipLaunchKernelGGL((fi_backward_defor<V, false, F>), grid, block, 0, st, input1, input2, I3, I4, gradoutput, acc, hdr, flags, \
-                           gradinput1, gradinput2, G3, G4, channel, h, w, filter_size, s1, s2, s3, S4)
-    // fs == 4: the LDS-staged kernel (filterinterp_defor_bwd_lds.hip), then the per-tap instance for the blocks it flagged
-#define FD_LAUNCH(V, I3, I4, G3, G4, S4) \
-        if (staged4 == 0) hipLaunchKernelGGL((fi_backward_defor<V, false, 4>), grid, block, 0, st, input1, input2, I3, I4, gradoutput, acc, hdr, flags, \
-                                             gradinput1, gradinput2, G3, G4, channel, h, w, filter_size, s1, s2, s3, S4); \
-        else { FD_LAUNCH2(V, 0, I3, I4, G3, G4, S4); }
-    int staged4 = -1;
+    // fs == 4: the LDS-staged kernel, then the per-tap fs == 4 instance for the blocks it flagged.  Otherwise, and when the
+    // staged kernel declines the shape, the STAGED per-tap instance for any filter size, then its !STAGED one for the blocks
+    // that one flagged.
+    bool staged = false;
     if (filter_size == 4) {
-        staged4 = vfi_filterinterp_backward_defor_lds(variant, input1, input2, input3, input4, gradoutput, acc, hdr, flags, gradinput2,
-                                                      gradinput3, gradinput4, batch, channel, h, w, s1, s2, s3, s4, stream);
-        if (staged4 != 0 && staged4 != -1) return VFI_ERR_LAUNCH;
+        const int r = launch_fi_defor_bwd_lds(variant, input1, input2, input3, input4, gradoutput, acc, hdr, flags, gradinput2,
+                                              gradinput3, gradinput4, batch, channel, h, w, s1, s2, s3, s4, stream);
+        if (r != VFI_OK && r != FI_DECLINED) return VFI_ERR_LAUNCH;
+        staged = r == VFI_OK;
     }
+    // (the variant without a filter has no input4: its kernel takes input3 / gradinput3 / s3 in those places)
+    const bool nofilter = variant == VFI_DEFOR_NOFILTER;
+    const float* in4 = nofilter ? input3 : input4;
+    float* g4 = nofilter ? gradinput3 : gradinput4;
+    const vfi_strides t4 = nofilter ? s3 : s4;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, input1, input2, input3, in4, gradoutput, acc, hdr, flags, gradinput1,
+                           gradinput2, gradinput3, g4, channel, h, w, filter_size, s1, s2, s3, t4);
+    };
     switch (variant) {
-    case VFI_DEFOR_OFFSET: FD_LAUNCH(VFI_DEFOR_OFFSET, input3, input4, gradinput3, gradinput4, s4); break;
-    case VFI_DEFOR_REGION: FD_LAUNCH(VFI_DEFOR_REGION, input3, input4, gradinput3, gradinput4, s4); break;
-    default:               FD_LAUNCH(VFI_DEFOR_NOFILTER, input3, input3, gradinput3, gradinput3, s3); break;
+    case VFI_DEFOR_OFFSET:
+        if (staged) launch(fi_backward_defor<VFI_DEFOR_OFFSET, false, 4>);
+        else { launch(fi_backward_defor<VFI_DEFOR_OFFSET, true, 0>); launch(fi_backward_defor<VFI_DEFOR_OFFSET, false, 0>); }
+        break;
+    case VFI_DEFOR_REGION:
+        if (staged) launch(fi_backward_defor<VFI_DEFOR_REGION, false, 4>);
+        else { launch(fi_backward_defor<VFI_DEFOR_REGION, true, 0>); launch(fi_backward_defor<VFI_DEFOR_REGION, false, 0>); }
+        break;
+    default:
+        if (staged) launch(fi_backward_defor<VFI_DEFOR_NOFILTER, false, 4>);
+        else { launch(fi_backward_defor<VFI_DEFOR_NOFILTER, true, 0>); launch(fi_backward_defor<VFI_DEFOR_NOFILTER, false, 0>); }
+        break;
     }
-#undef FD_LAUNCH
-#undef FD_LAUNCH2
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     return gradacc_finish(st, acc, hdr, gradinput1, batch, channel, h, w, s1);
 }

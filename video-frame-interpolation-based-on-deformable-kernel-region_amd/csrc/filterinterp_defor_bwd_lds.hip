@@ -19,6 +19,7 @@
 // A block whose windows do not fit, a block with a non-finite offset, and every block of a call with non-finite
 // gradients or weights raises its flag and returns; fi_backward_defor<V, false, 4>, launched afterwards, does those.
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 #include <limits.h>
 
@@ -300,14 +301,11 @@ __global__ __launch_bounds__(DB_THREADS, 2) void fi_backward_defor_lds(
 
 using namespace vfi;
 
-// internal (filterinterp.hip): launches the staged backward of `variant` for fs == 4; blocks it flags are left to the
-// caller's per-tap launch.  Returns -1 when the shape does not fit its 32-bit plane offsets (nothing launched, no flags).
-extern "C" int vfi_filterinterp_backward_defor_lds(int variant, const float* input1, const float* input2, const float* input3,
-                                                    const float* input4, const float* gradoutput, unsigned long long* acc,
-                                                    const int* hdr, int* flags, float* gradinput2, float* gradinput3,
-                                                    float* gradinput4, int batch, int channel, int h, int w, vfi_strides s1,
-                                                    vfi_strides s2, vfi_strides s3, vfi_strides s4, vfi_stream_t stream) {
-    if ((int64_t)h * s1.h * 4 > INT_MAX) return -1;          // byte offsets inside a plane are 32-bit
+int vfi::launch_fi_defor_bwd_lds(int variant, const float* input1, const float* input2, const float* input3, const float* input4,
+                                 const float* gradoutput, unsigned long long* acc, const int* hdr, int* flags, float* gradinput2,
+                                 float* gradinput3, float* gradinput4, int batch, int channel, int h, int w, vfi_strides s1,
+                                 vfi_strides s2, vfi_strides s3, vfi_strides s4, vfi_stream_t stream) {
+    if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;  // byte offsets inside a plane are 32-bit
     const dim3 grid = pixel_grid(w, h, batch), block(DB_TW, DB_TH, 1);
     static_assert(DB_TW == VFI_TX && DB_TH == VFI_TY, "the per-tap kernel's blocks are this kernel's");
     hipStream_t st = (hipStream_t)stream;

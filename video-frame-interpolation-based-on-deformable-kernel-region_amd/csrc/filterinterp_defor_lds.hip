@@ -21,6 +21,7 @@
 // decided per workgroup; other filter sizes use fi_forward_defor.  fs == 6 keeps 36 taps x (corner index, two fractions,
 // weight) = 144 registers per pixel: one workgroup per CU (at 256 registers the region variant spills inside its pipeline).
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 #include <limits.h>
 
@@ -45,8 +46,6 @@ __device__ __forceinline__ void df_wait_windows(int younger_groups) {
     default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K) : "memory"); break;
     }
 }
-
-struct DfWindow { int bx0, by0, bw, bh, pitch, h, w, hs; };
 
 // One pixel's state for the channel loop.  lb[k]: float index, inside a staged window, of tap k's top-left
 // corner; phy / phx: the fractions of defor_tap; qx / qy bit k: the tap lies right of / below the sampling
@@ -118,7 +117,7 @@ __device__ __forceinline__ float df_value(const DfPixel<FS>& px, F&& fetch) {
 
 template <int VARIANT, int FS, int K>
 __device__ __forceinline__ void df_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
-                                                int c_begin, int c_end, int tid, const DfWindow& win,
+                                                int c_begin, int c_end, int tid, const FiWindow& win,
                                                 const DfPixel<FS>& px, float* __restrict__ ring, int R) {
     static_assert(3 * K <= 63, "vmcnt is a 6-bit counter");
     // staging exactly as fi_run_channels (filterinterp_lds.hip): element e = tid + k * threads of the window,
@@ -312,7 +311,7 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
 #pragma unroll
     for (int k = 0; k < NT; ++k) px.lb[k] = (corner_y(k) - by0) * pitch + (corner_x(k) - bx0);
 
-    const DfWindow win{bx0, by0, bw, bh, pitch, h, w, hs};
+    const FiWindow win{bx0, by0, bw, bh, pitch, h, w, hs};
     float* ring = lds + DF_HDR;
 #define DF_RUN(K) df_run_channels<VARIANT, FS, K>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, \
                                               min(DF_RMAX, DF_RING_FLOATS / ((K) * DF_THREADS)))
@@ -331,35 +330,30 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
 
 using namespace vfi;
 
-// returns -1 when this path does not apply (the caller uses the direct kernels)
-extern "C" int vfi_filterinterp_forward_defor_lds(int variant, const float* input1, const float* input2,
-                                                   const float* input3, const float* input4, float* output,
-                                                   int batch, int channel, int h, int w, int filter_size,
-                                                   vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides s4,
-                                                   vfi_stream_t stream) {
-    if (filter_size != 4 && filter_size != 6) return -1;
-    if (h > 65534 || w > 65534) return -1;                   // (tap corners travel as two 16-bit halves)
+int vfi::launch_fi_defor_lds(int variant, const float* input1, const float* input2, const float* input3, const float* input4,
+                             float* output, int batch, int channel, int h, int w, int filter_size, vfi_strides s1,
+                             vfi_strides s2, vfi_strides s3, vfi_strides s4, vfi_stream_t stream) {
+    if (filter_size != 4 && filter_size != 6) return FI_DECLINED;
+    if (h > 65534 || w > 65534) return FI_DECLINED;          // (tap corners travel as two 16-bit halves)
     const int nt = filter_size * filter_size;
-    if ((int64_t)h * s1.h * 4 > INT_MAX) return -1;          // byte offsets inside a plane are 32-bit
+    if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;  // byte offsets inside a plane are 32-bit
     // the filter / offset tensors of one batch item are addressed through 32-bit buffer offsets (signed descriptor size)
     const int nf = (variant == VFI_DEFOR_NOFILTER) ? 2 * nt : nt;
     const int64_t fb = 4 * ((int64_t)(nf - 1) * s3.c + (int64_t)(h - 1) * s3.h + w);
     const int64_t ob = (variant == VFI_DEFOR_NOFILTER) ? fb : 4 * ((int64_t)(2 * nt - 1) * s4.c + (int64_t)(h - 1) * s4.h + w);
-    if (fb > INT_MAX || ob > INT_MAX || s3.c < 0 || s3.h < 0 || s4.c < 0 || s4.h < 0) return -1;
+    if (fb > INT_MAX || ob > INT_MAX || s3.c < 0 || s3.h < 0 || s4.c < 0 || s4.h < 0) return FI_DECLINED;
     const unsigned filt_bytes = (unsigned)fb, off_bytes = (unsigned)ob;
     const int tiles_x = (w + DF_TW - 1) / DF_TW, tiles_y = (h + DF_TH - 1) / DF_TH;
     const int64_t ntl = (int64_t)tiles_x * tiles_y * batch;
-    if (ntl > INT_MAX) return -1;
+    if (ntl > INT_MAX) return FI_DECLINED;
     const int ntiles = (int)ntl;
     // (a channel of these kernels costs ~4x one of the _ori kernel, the prologue -- flow, offsets, filter: up to 200 B/pixel --
     //  ~3x: about 3 channels' worth)
-    const int best_groups = fi_channel_groups(ntiles, channel, variant == VFI_DEFOR_NOFILTER ? 2.0 : 3.0);
-    const int ch_per_group = (channel + best_groups - 1) / best_groups;
-    const int groups = (channel + ch_per_group - 1) / ch_per_group;
-    const dim3 grid((unsigned)ntiles, (unsigned)groups, 1), block(DF_THREADS, 1, 1);
+    const FiSplit split = fi_channel_split(ntiles, channel, variant == VFI_DEFOR_NOFILTER ? 2.0 : 3.0);
+    const dim3 grid((unsigned)ntiles, (unsigned)split.groups, 1), block(DF_THREADS, 1, 1);
     hipStream_t st = (hipStream_t)stream;
 #define DF_LAUNCH(V, FSZ, IN4, S4, OB) hipLaunchKernelGGL((fi_forward_defor_lds<V, FSZ>), grid, block, 0, st, input1, input2, input3, IN4, \
-                           output, channel, h, w, s1, s2, s3, S4, tiles_x, tiles_y, ntiles, ch_per_group, filt_bytes, OB)
+                           output, channel, h, w, s1, s2, s3, S4, tiles_x, tiles_y, ntiles, split.ch_per_group, filt_bytes, OB)
     switch (variant) {
     case VFI_DEFOR_OFFSET:
         if (filter_size == 4) DF_LAUNCH(VFI_DEFOR_OFFSET, 4, input4, s4, off_bytes); else DF_LAUNCH(VFI_DEFOR_OFFSET, 6, input4, s4, off_bytes);
@@ -371,7 +365,7 @@ extern "C" int vfi_filterinterp_forward_defor_lds(int variant, const float* inpu
         if (filter_size == 4) DF_LAUNCH(VFI_DEFOR_NOFILTER, 4, input3, s3, filt_bytes); else DF_LAUNCH(VFI_DEFOR_NOFILTER, 6, input3, s3, filt_bytes);
         break;
     default:
-        return -1;
+        return FI_DECLINED;
     }
 #undef DF_LAUNCH
     return launch_status();

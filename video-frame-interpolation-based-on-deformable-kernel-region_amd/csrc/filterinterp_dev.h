@@ -41,6 +41,10 @@ __device__ __forceinline__ int fi_pitch_for(int bw) {
     return FI_PITCH_SKEW ? (((max(bw - FI_PITCH_SKEW, 0) + 31) & ~31) + FI_PITCH_SKEW) : ((bw + 31) & ~31);
 }
 
+// A tile's staged window: bw x bh elements from column bx0 / row by0 of an h x w plane with row stride hs, at LDS row
+// pitch `pitch`
+struct FiWindow { int bx0, by0, bw, bh, pitch, h, w, hs; };
+
 // channel loop of one valid pixel gathering straight from global memory.  Row by row, so the
 // register need is 4 taps + 4 sums (the compiler may still batch rows when it has registers
 // to spare); the operation order per quadrant is that of fi4_pixel.

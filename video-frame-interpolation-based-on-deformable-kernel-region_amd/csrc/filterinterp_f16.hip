@@ -97,7 +97,6 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct_f16(
 
 // ------------------------------------------------------------------ LDS-staged kernel, fs == 4
 
-struct F16Window { int bx0, by0, bw, bh, pitch, h, w, hs; };   // bx0 even; bw, pitch in dwords
 struct F16Pixel {
     bool valid, inimg;
     int lbase;              // half index of the window origin inside a staged window (row pitch 2 * pitch)
@@ -125,7 +124,7 @@ __device__ __forceinline__ float f16_hi(unsigned d) { return __half2float(__usho
 // pixel's first rows in flight under the first pixel's arithmetic, range-checked buffer stores.
 template <int K>
 __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img, __half* __restrict__ out, int64_t cs,
-                                                 int c_begin, int c_end, int tid, const F16Window& win,
+                                                 int c_begin, int c_end, int tid, const FiWindow& win,
                                                  const F16Pixel (&px)[F16_PX], unsigned* __restrict__ ring) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     static_assert(F16_PX == 2, "two pixels per thread");
@@ -357,7 +356,7 @@ __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
         return;
     }
 
-    const F16Window win{bx0, by0, bw, bh, pitch, h, w, (int)s1.h};
+    const FiWindow win{bx0, by0, bw, bh, pitch, h, w, (int)s1.h};          // bx0 even; bw, pitch in dwords
     unsigned* ring = lds + F16_HDR;
 #define F16_RUN(K) f16_run_channels<K>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring)
     if (kmax <= 2) F16_RUN(2);
@@ -378,7 +377,7 @@ extern "C" int vfi_filterinterp_forward_ori_f16_direct(const void* input1, const
                                                         vfi_strides s3, vfi_stream_t stream) {
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
     if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
-    const int fs = (int)sqrtf((float)filter_channels);
+    const int fs = fi_filter_size(filter_channels);
     hipLaunchKernelGGL(fi_forward_ori_direct_f16, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, (hipStream_t)stream,
                        (const __half*)input1, input2, input3, (__half*)output, channel, h, w, fs, s1, s2, s3);
     return launch_status();
@@ -391,7 +390,7 @@ extern "C" int vfi_filterinterp_forward_ori_f16(const void* input1, const float*
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
     if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
     // the staged kernel moves dwords: rows, planes and the base address must be 4-byte aligned
-    const bool staged = (int)sqrtf((float)filter_channels) == 4 && filter_channels == 16 && w >= 4 &&
+    const bool staged = filter_channels == 16 && w >= 4 &&
                         ((s1.h | s1.c | s1.b) & 1) == 0 && (reinterpret_cast<uintptr_t>(input1) & 3) == 0 &&
                         (int64_t)h * s1.h * 2 < INT_MAX;
     const int tiles_x = (w + F16_TW - 1) / F16_TW, tiles_y = (h + F16_TH - 1) / F16_TH;
@@ -401,12 +400,10 @@ extern "C" int vfi_filterinterp_forward_ori_f16(const void* input1, const float*
                                                        filter_channels, s1, s2, s3, stream);
     const int ntiles = (int)nt;
     // split the channel range over blockIdx.y when that shortens the tail (as the fp32 kernel)
-    const int best_groups = fi_channel_groups(ntiles, channel, 4.3);
-    const int ch_per_group = (channel + best_groups - 1) / best_groups;
-    const int groups = (channel + ch_per_group - 1) / ch_per_group;
+    const FiSplit split = fi_channel_split(ntiles, channel, 4.3);
     const int grid_x = ((ntiles + 31) / 32) * 32;                   // whole groups of 8 XCDs x 4 tiles
-    hipLaunchKernelGGL(fi_forward_ori_lds_f16, dim3((unsigned)grid_x, (unsigned)groups, 1), dim3(F16_THREADS, 1, 1), 0,
+    hipLaunchKernelGGL(fi_forward_ori_lds_f16, dim3((unsigned)grid_x, (unsigned)split.groups, 1), dim3(F16_THREADS, 1, 1), 0,
                        (hipStream_t)stream, (const __half*)input1, input2, input3, (__half*)output, channel, h, w, s1, s2,
-                       s3, tiles_x, tiles_y, ntiles, ch_per_group);
+                       s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();
 }

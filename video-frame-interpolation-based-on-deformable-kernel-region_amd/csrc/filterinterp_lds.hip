@@ -32,6 +32,7 @@
 // over blockIdx.y shortens the tail when the tile count does not fill the chip
 // evenly.
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 #include <limits.h>
 
@@ -70,7 +71,6 @@ typedef __attribute__((address_space(3))) void* fi_lptr_t;
 __device__ __forceinline__ int wave_min(int v) { return wave_min_i32(v); }
 __device__ __forceinline__ int wave_max(int v) { return wave_max_i32(v); }
 
-struct FiWindow { int bx0, by0, bw, bh, pitch, h, w, hs; };
 struct FiPixel {
     bool valid, inimg;
     float alpha, beta;
@@ -700,51 +700,42 @@ template __global__ void fi_forward_ori_lds<false>(const float* __restrict__, co
 
 using namespace vfi;
 
-// returns -1 when this path does not apply (caller uses the direct kernel)
 static int forward_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
                            int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream, FiBlend blend) {
     // byte offsets inside a plane are 32-bit in the kernel
-    if ((int64_t)h * s1.h * 4 > INT_MAX) return -1;
+    if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;
     const int tiles_x = (w + FI_TW - 1) / FI_TW, tiles_y = (h + FI_TH - 1) / FI_TH;
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
-    if (nt > (1 << 28)) return -1;
+    if (nt > (1 << 28)) return FI_DECLINED;
     const int ntiles = (int)nt;
     const int per_xcd = (((ntiles + FI_XCDS - 1) / FI_XCDS) + 7) & ~7;         // (a multiple of 8: whole groups of four tiles)
 
     // split the channel range over blockIdx.y when that shortens the tail: two workgroups per
     // CU run at a time; every extra group re-reads the flow + 16 filter planes (72 B/pixel)
-    // next to 8 B/pixel/channel of image traffic
-    int best_groups = fi_channel_groups(ntiles, channel, 4.3);
-    if (blend.out) best_groups = 1;                         // (the blend epilogue keeps a pixel's channels in one workgroup)
-    const int ch_per_group = (channel + best_groups - 1) / best_groups;
-    const int groups = (channel + ch_per_group - 1) / ch_per_group;
+    // next to 8 B/pixel/channel of image traffic.  The blend epilogue keeps a pixel's channels in one workgroup.
+    const FiSplit split = blend.out ? FiSplit{channel, 1} : fi_channel_split(ntiles, channel, 4.3);
 
-    const dim3 grid((unsigned)(per_xcd * FI_XCDS), (unsigned)groups, 1);
+    const dim3 grid((unsigned)(per_xcd * FI_XCDS), (unsigned)split.groups, 1);
     // (16-byte staging: rows of input1 on 16-byte boundaries; its single-descriptor addressing: two planes within 2^31 bytes)
     const int aligned16 = !(w & 3) && !(s1.h & 3) && !(s1.c & 3) && !(s1.b & 3) && !((uintptr_t)input1 & 15) &&
                           s1.c > 0 && 4 * s1.c + 4 * ((int64_t)(h - 1) * s1.h + w) < 0x7fffffffLL;
     if (blend.out)
         hipLaunchKernelGGL(fi_forward_ori_lds<true>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group, aligned16, blend);
+                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, aligned16, blend);
     else
         hipLaunchKernelGGL(fi_forward_ori_lds<false>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group, aligned16, blend);
+                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, aligned16, blend);
     return launch_status();
 }
 
-extern "C" int vfi_filterinterp_forward_ori_lds(const float* input1, const float* input2, const float* input3,
-                                                 float* output, int batch, int channel, int h, int w,
-                                                 vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                                                 vfi_stream_t stream) {
+int vfi::launch_fi_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                           int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream) {
     return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream, FiBlend{nullptr, nullptr, 0.0f, 0.0f});
 }
 
-// internal: the second launch of DAIN.FilterInterpolate with the blend as its epilogue -- besides output it writes
-// blend = other * w0 + output * w2; other / blend have input1's strides; channel <= FI_BLEND_MAXC.  -1: not applicable.
-extern "C" int vfi_filterinterp_forward_ori_lds_blend(const float* input1, const float* input2, const float* input3,
-                                                       float* output, const float* other, float* blend, float w0, float w2,
-                                                       int batch, int channel, int h, int w,
-                                                       vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream) {
-    if (channel > FI_BLEND_MAXC || !other || !blend) return -1;
+int vfi::launch_fi_ori_lds_blend(const float* input1, const float* input2, const float* input3, float* output, const float* other,
+                                 float* blend, float w0, float w2, int batch, int channel, int h, int w, vfi_strides s1,
+                                 vfi_strides s2, vfi_strides s3, vfi_stream_t stream) {
+    if (channel > FI_BLEND_MAXC || !other || !blend) return FI_DECLINED;
     return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream, FiBlend{other, blend, w0, w2});
 }

@@ -11,6 +11,7 @@
 // not fit gathers from global memory.  The general direct kernel re-reads the fs*fs filter taps and gathers fs*fs
 // image values from global memory per pixel and channel.
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 #include <limits.h>
 
@@ -35,8 +36,6 @@ __device__ __forceinline__ void fn_wait_windows(int younger_groups) {
     default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K) : "memory"); break;
     }
 }
-
-struct FnWindow { int bx0, by0, bw, bh, pitch, h, w, hs; };
 
 template <int FS>
 struct FnPixel {
@@ -69,7 +68,7 @@ __device__ __forceinline__ float fn_value(const FnPixel<FS>& px, F&& fetch) {
 
 template <int FS, int K>
 __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
-                                                int c_begin, int c_end, int tid, const FnWindow& win,
+                                                int c_begin, int c_end, int tid, const FiWindow& win,
                                                 const FnPixel<FS>& px, float* __restrict__ ring, int R) {
     static_assert(3 * K <= 63, "vmcnt is a 6-bit counter");
     unsigned goff[K];                                       // staging exactly as fi_run_channels (filterinterp_lds.hip)
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
         }
         return;
     }
-    const FnWindow win{bx0, by0, bw, bh, pitch, h, w, hs};
+    const FiWindow win{bx0, by0, bw, bh, pitch, h, w, hs};
     float* ring = lds + FN_HDR;
 #define FN_RUN(K) fn_run_channels<FS, K>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, \
                                          min(FN_RMAX, FN_RING_FLOATS / ((K) * FN_THREADS)))
@@ -219,31 +218,27 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
 
 using namespace vfi;
 
-// returns -1 when this path does not apply (the caller uses the direct kernel)
-extern "C" int vfi_filterinterp_forward_ori_lds_n(const float* input1, const float* input2, const float* input3,
-                                                   float* output, int batch, int channel, int h, int w, int fs,
-                                                   vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                                                   vfi_stream_t stream) {
-    if (!(fs == 2 || fs == 5 || fs == 6)) return -1;
-    if ((int64_t)h * s1.h * 4 > INT_MAX) return -1;          // byte offsets inside a plane are 32-bit
+int vfi::launch_fi_ori_lds_n(const float* input1, const float* input2, const float* input3, float* output, int batch,
+                             int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3,
+                             vfi_stream_t stream) {
+    if (!(fs == 2 || fs == 5 || fs == 6)) return FI_DECLINED;
+    if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;  // byte offsets inside a plane are 32-bit
     const int tiles_x = (w + FN_TW - 1) / FN_TW, tiles_y = (h + FN_TH - 1) / FN_TH;
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
-    if (nt > INT_MAX) return -1;
+    if (nt > INT_MAX) return FI_DECLINED;
     const int ntiles = (int)nt;
     // (the prologue reads flow + fs x fs filter planes: ~4.3 channels' worth at fs = 4)
-    const int best_groups = fi_channel_groups(ntiles, channel, 4.3 * (2 + fs * fs) / 18.0);
-    const int ch_per_group = (channel + best_groups - 1) / best_groups;
-    const int groups = (channel + ch_per_group - 1) / ch_per_group;
-    const dim3 grid((unsigned)ntiles, (unsigned)groups, 1), block(FN_THREADS, 1, 1);
+    const FiSplit split = fi_channel_split(ntiles, channel, 4.3 * (2 + fs * fs) / 18.0);
+    const dim3 grid((unsigned)ntiles, (unsigned)split.groups, 1), block(FN_THREADS, 1, 1);
     hipStream_t st = (hipStream_t)stream;
     if (fs == 2)
         hipLaunchKernelGGL(fi_forward_ori_lds_n<2>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group);
+                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     else if (fs == 5)
         hipLaunchKernelGGL(fi_forward_ori_lds_n<5>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group);
+                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     else
         hipLaunchKernelGGL(fi_forward_ori_lds_n<6>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, ch_per_group);
+                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();
 }

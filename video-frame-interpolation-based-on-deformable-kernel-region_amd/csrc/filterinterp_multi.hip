@@ -568,11 +568,6 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
 
 using namespace vfi;
 
-extern "C" int vfi_filterinterp_forward_ori(const float* input1, const float* input2, const float* input3,
-                                             float* output, int batch, int channel, int h, int w,
-                                             int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                                             vfi_stream_t stream);
-
 extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const float* const* flows, const float* input3,
                                                    float* const* outputs, int nflows, int batch, int channel, int h, int w,
                                                    int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
@@ -611,13 +606,11 @@ extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const flo
     const int ntiles = (int)nt;
     const int per_xcd = (((ntiles + FM_XCDS - 1) / FM_XCDS) + 3) & ~3;          // whole groups of four tiles
     // (one prologue for nflows outputs per channel)
-    const int best_groups = fi_channel_groups(ntiles, channel, 4.3 * (1.0 + 0.3 * (nflows - 1)) / nflows);
-    const int ch_per_group = (channel + best_groups - 1) / best_groups;
-    const int groups = (channel + ch_per_group - 1) / ch_per_group;
+    const FiSplit split = fi_channel_split(ntiles, channel, 4.3 * (1.0 + 0.3 * (nflows - 1)) / nflows);
     FmPtrs ptr;
     for (int t = 0; t < FM_NT; ++t) { ptr.flow[t] = flows[t]; ptr.out[t] = outputs[t]; }
-    const dim3 grid((unsigned)(per_xcd * FM_XCDS), (unsigned)groups, 1), block(FM_THREADS, 1, 1);
+    const dim3 grid((unsigned)(per_xcd * FM_XCDS), (unsigned)split.groups, 1), block(FM_THREADS, 1, 1);
     hipLaunchKernelGGL(fi_forward_ori_multi, grid, block, 0, (hipStream_t)stream, input1, ptr, input3, channel, h, w, s1, s2, s3,
-                       tiles_x, tiles_y, ntiles, ch_per_group);
+                       tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();
 }

@@ -1,0 +1,36 @@
+// filterinterp_paths.h -- the per-path launchers the FilterInterpolation entry points of vfi_hip.h dispatch to.
+//
+// Internal to libvfi_hip.so, with C++ linkage: a definition and a call that disagree on the parameters fail to compile
+// or link instead of passing the wrong arguments.  Each launcher returns VFI_OK or VFI_ERR_LAUNCH, or FI_DECLINED when
+// its kernel does not take the shape; then it has launched nothing and the caller takes the next path.
+#pragma once
+#include "vfi_common.h"
+
+namespace vfi {
+
+constexpr int FI_DECLINED = -1;
+static_assert(FI_DECLINED != VFI_OK && FI_DECLINED != VFI_ERR_SHAPE && FI_DECLINED != VFI_ERR_LAUNCH, "a distinct result");
+
+// filterinterp_lds.hip: _ori forward, fs == 4
+int launch_fi_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                      int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+// filterinterp_lds.hip: the same kernel with the blend of DAIN.FilterInterpolate as its epilogue -- besides output it
+// writes blend = other * w0 + output * w2; other / blend have input1's strides; declines channel > FI_BLEND_MAXC
+int launch_fi_ori_lds_blend(const float* input1, const float* input2, const float* input3, float* output, const float* other,
+                            float* blend, float w0, float w2, int batch, int channel, int h, int w, vfi_strides s1,
+                            vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+// filterinterp_lds_n.hip: _ori forward, fs 2, 5 and 6
+int launch_fi_ori_lds_n(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                        int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+// filterinterp_defor_lds.hip: forward of the deformable variants, fs 4 and 6
+int launch_fi_defor_lds(int variant, const float* input1, const float* input2, const float* input3, const float* input4,
+                        float* output, int batch, int channel, int h, int w, int filter_size, vfi_strides s1, vfi_strides s2,
+                        vfi_strides s3, vfi_strides s4, vfi_stream_t stream);
+// filterinterp_defor_bwd_lds.hip: backward of the deformable variants, fs == 4, into the caller's gradacc scratch (acc,
+// hdr); the blocks it flags are left to the caller's per-tap launch
+int launch_fi_defor_bwd_lds(int variant, const float* input1, const float* input2, const float* input3, const float* input4,
+                            const float* gradoutput, unsigned long long* acc, const int* hdr, int* flags, float* gradinput2,
+                            float* gradinput3, float* gradinput4, int batch, int channel, int h, int w, vfi_strides s1,
+                            vfi_strides s2, vfi_strides s3, vfi_strides s4, vfi_stream_t stream);
+
+}  // namespace vfi

@@ -9,6 +9,7 @@
 //     interpolation error (demo_MiddleBury.py:280-318, 350-364, 370-388).
 // (The x4 flow upsample fused into the projection is in projection.hip.)
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 #include "pwc_warp.h"
 
 namespace vfi {
@@ -300,11 +301,6 @@ __global__ __launch_bounds__(256) void frame_ssim_sums(const unsigned char* __re
 
 using namespace vfi;
 
-extern "C" int vfi_filterinterp_forward_ori_lds_blend(const float* input1, const float* input2, const float* input3,
-                                                       float* output, const float* other, float* blend, float w0, float w2,
-                                                       int batch, int channel, int h, int w,
-                                                       vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
-
 extern "C" int vfi_filterinterp_blend_forward(const float* ref0, const float* ref2, const float* flow0, const float* flow2,
                                                const float* filt0, const float* filt2, float* blend, float* out0,
                                                float* out2, int batch, int channel, int h, int w, int filter_channels,
@@ -312,16 +308,16 @@ extern "C" int vfi_filterinterp_blend_forward(const float* ref0, const float* re
                                                vfi_strides s_filt, vfi_strides s_out, vfi_stream_t stream) {
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
     if (!ref0 || !ref2 || !flow0 || !flow2 || !filt0 || !filt2 || !blend) return VFI_ERR_SHAPE;
-    const int fs = (int)sqrtf((float)filter_channels);
+    const int fs = fi_filter_size(filter_channels);
     if (filter_channels == 16 && out0 && out2 && s_out.b == s_ref.b && s_out.c == s_ref.c && s_out.h == s_ref.h) {
         // the LDS-staged forward per side (faster than the direct gather even at C = 3; it writes with the
         // input's strides), then the blend
         int err = vfi_filterinterp_forward_ori(ref0, flow0, filt0, out0, batch, channel, h, w, 16, s_ref, s_flow, s_filt, stream);
         if (err != VFI_OK) return err;
         // the blend as the second launch's epilogue (3-channel frames); else a launch of its own
-        err = vfi_filterinterp_forward_ori_lds_blend(ref2, flow2, filt2, out2, out0, blend, w0, w2, batch, channel, h, w, s_ref, s_flow,
-                                                     s_filt, stream);
-        if (err != -1) return err;
+        err = launch_fi_ori_lds_blend(ref2, flow2, filt2, out2, out0, blend, w0, w2, batch, channel, h, w, s_ref, s_flow, s_filt,
+                                      stream);
+        if (err != FI_DECLINED) return err;
         err = vfi_filterinterp_forward_ori(ref2, flow2, filt2, out2, batch, channel, h, w, 16, s_ref, s_flow, s_filt, stream);
         if (err != VFI_OK) return err;
         hipLaunchKernelGGL(fi_blend_only, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, (hipStream_t)stream, out0,

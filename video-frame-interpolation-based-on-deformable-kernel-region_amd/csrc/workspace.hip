@@ -247,7 +247,7 @@ int device_cu_count() {
     return cus[dev];
 }
 
-int fi_channel_groups(int ntiles, int channel, double prologue) {
+FiSplit fi_channel_split(int ntiles, int channel, double prologue) {
     const int slots = device_cu_count() * 2;
     int best = 1;
     double best_cost = 0.0;
@@ -256,7 +256,8 @@ int fi_channel_groups(int ntiles, int channel, double prologue) {
         const double cost = (channel + prologue * g) * ((r + 0.5) / r) * (1.0 + 0.25 / r);
         if (g == 1 || cost < best_cost) { best_cost = cost; best = g; }
     }
-    return best;
+    const int ch_per_group = (channel + best - 1) / best;
+    return FiSplit{ch_per_group, (channel + ch_per_group - 1) / ch_per_group};
 }
 
 }  // namespace vfi
