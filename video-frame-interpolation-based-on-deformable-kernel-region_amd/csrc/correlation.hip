@@ -291,8 +291,8 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
     auto fetch = [&](int c0) {
         const int cn = min(CORR_CC_ROWS, channel - c0);
         const int bytes = cn * (int)plane * 4;
-        const auto d2 = __builtin_amdgcn_make_buffer_rsrc((void*)(f2 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
-        const auto d1 = __builtin_amdgcn_make_buffer_rsrc((void*)(f1 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
+        const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, bytes);
+        const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, bytes);
 #pragma unroll
         for (int k = 0; k < NPT; ++k) nv[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(d2, soff[k], 0, 0));
 #pragma unroll
@@ -376,7 +376,6 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
 // registers, 20.7 us at 32 x 288 x 496.)  The tap reads are asm: hipcc
 // drains vmcnt before an LDS read it can see next to an LDS-DMA target (filterinterp_lds.hip), which would wait for the chunk
 // in flight.  Same tile, same lanes, same order of the multiply-adds: the same bits.
-typedef __attribute__((address_space(3))) void* corr_lptr_t;
 #define CORR_QUAD_LDS_FLOATS (2 * (4 * 6 * 18 + 4 * 4 * 16) * 4)          // two buffers of 432 window units + 256 first-map units
 template <int MD>
 __device__ __forceinline__ void corr_quad_body(
@@ -437,17 +436,17 @@ __device__ __forceinline__ void corr_quad_body(
     auto issue = [&](int c0, int buf) {
         const int cn = min(CCQ, channel - c0);
         const int bytes = cn * (int)plane * 4;
-        const auto d2 = __builtin_amdgcn_make_buffer_rsrc((void*)(f2 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
-        const auto d1 = __builtin_amdgcn_make_buffer_rsrc((void*)(f1 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
+        const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, bytes);
+        const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, bytes);
         float* base = lds + buf * BUF;
 #pragma unroll
         for (int k = 0; k < NPT; ++k)
             if (tid + k * NT < NU)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(d2, (corr_lptr_t)(base + (k * NT + wv * 64) * 4), 16, soff[k], 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(d2, (lds_ptr_t)(base + (k * NT + wv * 64) * 4), 16, soff[k], 0, 0, 0);
 #pragma unroll
         for (int k = 0; k < NF1; ++k)
             if (tid + k * NT < FU)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(d1, (corr_lptr_t)(base + NU * 4 + (k * NT + wv * 64) * 4), 16, foff[k], 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(d1, (lds_ptr_t)(base + NU * 4 + (k * NT + wv * 64) * 4), 16, foff[k], 0, 0, 0);
     };
 
     float acc[4][D];
@@ -456,7 +455,7 @@ __device__ __forceinline__ void corr_quad_body(
 #pragma unroll
         for (int ti = 0; ti < D; ++ti) acc[q][ti] = 0.0f;
 
-    const unsigned lds0 = (unsigned)(uintptr_t)(corr_lptr_t)lds;
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     const unsigned a_addr = lds0 + 4u * (unsigned)(NU * 4 + py * TW + px);                 // first map: [c][TH * TW]
     const unsigned t_addr = lds0 + 4u * (unsigned)((py + wv) * LW + px);                   // window: [c][LH][LW]
 #define CORR_CHANNEL_TERMS(c, bo) do { \
@@ -650,8 +649,8 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2_f16(
     auto fetch = [&](int c0) {
         const int cn = min(CORR_CC_ROWS, channel - c0);
         const int bytes = cn * (int)plane * 2;
-        const auto d2 = __builtin_amdgcn_make_buffer_rsrc((void*)(f2 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
-        const auto d1 = __builtin_amdgcn_make_buffer_rsrc((void*)(f1 + (int64_t)c0 * plane), 0, bytes, 0x00020000);
+        const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, bytes);
+        const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, bytes);
 #pragma unroll
         for (int k = 0; k < NPT; ++k) { const v2u_ v = __builtin_amdgcn_raw_buffer_load_b64(d2, soff[k], 0, 0); nv[k] = make_uint2(v.x, v.y); }
 #pragma unroll
@@ -969,7 +968,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void c
     // loads through a descriptor that spans the image's gradOutput: one 32-bit offset per load, and an offset out of range
     // (an element outside the frame) returns the zero.  (Left to itself the compiler issues all 162 loads at once and needs
     // over 200 registers: the loads go out one displacement row at a time.)
-    const auto gd = __builtin_amdgcn_make_buffer_rsrc((void*)go, 0, (int)(OC * plane * 2), 0x00020000);
+    const auto gd = buffer_rsrc(go, (int)(OC * plane * 2));
     __half2 g[OC];
 #pragma unroll
     for (int tc = 0; tc < OC; ++tc) {
@@ -985,7 +984,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void c
     }
 
     auto stage = [&](int c, int buf) {
-        const auto od = __builtin_amdgcn_make_buffer_rsrc((void*)(other + ((int64_t)n * channel + c) * plane), 0, (int)(plane * 2), 0x00020000);
+        const auto od = buffer_rsrc(other + ((int64_t)n * channel + c) * plane, (int)(plane * 2));
         for (int e = tid; e < LH * LW; e += NT) {
             const int r = e / LW, col = e - r * LW;
             const int gy = y0 - MD + r, gx = x0 - MD + col;

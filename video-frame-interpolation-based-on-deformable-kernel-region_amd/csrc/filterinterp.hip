@@ -216,8 +216,6 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
 // flagged, and fi_backward_ori, launched after this kernel, does those tiles only.  A tile with a large window takes two
 // channels, or one, per pass.  Without the image gradient (WANT_X = false) the LDS holds the windows only; the channels per
 // pass stay those of the window budget (at C = 3 one pass covers every channel either way).
-typedef __attribute__((address_space(3))) void* fb_lptr_t;
-
 template <class G, bool BLEND, bool WANT_X>
 __device__ __forceinline__ void fi_backward_ori4_tile(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3, G gsrc,
@@ -309,14 +307,14 @@ __device__ __forceinline__ void fi_backward_ori4_tile(
         // ---- stage the pass's windows (element e of a window = cell e: row-major, bw per row, all inside the image), zero the
         // cells, fetch gradoutput
         for (int cc = 0; cc < cn; ++cc) {
-            const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)(c0 + cc) * s1.c), 0, plane_bytes, 0x00020000);
+            const auto plane = buffer_rsrc(img + (int64_t)(c0 + cc) * s1.c, plane_bytes);
             float* slot = wins + cc * slot_floats + wave_first;
             for (int e0 = 0; e0 < n; e0 += FB_THREADS) {
                 const int e = e0 + tid;
                 const int r = fi_row_of(e, inv_bw);
                 const int col = e - r * bw;
                 // (lanes past the window get an out-of-range offset: they write zeros, inside the window's own slot)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fb_lptr_t)(slot + e0), 4, e < n ? 4u * (unsigned)((by0 + r) * hs + bx0 + col) : 0x80000000u, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(slot + e0), 4, e < n ? 4u * (unsigned)((by0 + r) * hs + bx0 + col) : 0x80000000u, 0, 0, 0);
             }
         }
         if (wx) for (int e = tid; e < n * cn; e += FB_THREADS) cells[e] = 0ull;
@@ -890,10 +888,10 @@ static int defor_forward(bool allow_staged, int variant, const float* input1, co
     const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
     hipStream_t st = (hipStream_t)stream;
     if ((filter_size == 4 || filter_size == 6) && allow_staged && variant >= 0 && variant <= 2) {
-        // the LDS-staged kernel; when it declines the shape, and also when its launch fails, the general kernel below runs
+        // the LDS-staged kernel; when it declines the shape, the general kernel below runs
         const int err = launch_fi_defor_lds(variant, input1, input2, input3, input4, output, batch, channel, h, w, filter_size,
                                             s1, s2, s3, s4, stream);
-        if (err == VFI_OK) return VFI_OK;
+        if (err != FI_DECLINED) return err;
     }
     switch (variant) {
     case VFI_DEFOR_OFFSET:

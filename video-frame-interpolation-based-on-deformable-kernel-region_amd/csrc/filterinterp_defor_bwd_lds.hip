@@ -32,8 +32,6 @@ namespace vfi {
 #define DB_WIN_FLOATS 3840                          // staged window of one plane, at most (15 x 256)
 #define DB_CELLS 4096                               // 64-bit cells of the gradient window, all channels of a pass
 
-typedef __attribute__((address_space(3))) void* db_lptr_t;
-
 template <int VARIANT>
 __global__ __launch_bounds__(DB_THREADS, 2) void fi_backward_defor_lds(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
@@ -174,14 +172,14 @@ __global__ __launch_bounds__(DB_THREADS, 2) void fi_backward_defor_lds(
         // ---- stage the windows of the pass (element e = tid + k * 256 of a window, row-major with `pitch`; pad elements
         // and rows past the last get an out-of-range offset: zero, no memory traffic), zero the cells, fetch gradoutput
         for (int cc = 0; cc < cn; ++cc) {
-            const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)(c0 + cc) * s1.c), 0, plane_bytes, 0x00020000);
+            const auto plane = buffer_rsrc(img + (int64_t)(c0 + cc) * s1.c, plane_bytes);
             float* slot = wins + cc * DB_WIN_FLOATS + wave_first;
             for (int e0 = 0; e0 < n; e0 += DB_THREADS) {
                 const int e = e0 + tid;
                 const int r = fi_row_of(e, inv_pitch);
                 const int col = e - r * pitch;
                 const unsigned off = 4u * (unsigned)(clampi(by0 + r, 0, h - 1) * hs + clampi(bx0 + col, 0, w - 1));
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (db_lptr_t)(slot + e0), 4, (col < bw && r < bh) ? off : 0x80000000u, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(slot + e0), 4, (col < bw && r < bh) ? off : 0x80000000u, 0, 0, 0);
             }
         }
         for (int e = tid; e < ncell * cn; e += DB_THREADS) cells[e] = 0ull;

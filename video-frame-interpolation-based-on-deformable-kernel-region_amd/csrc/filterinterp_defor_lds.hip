@@ -35,18 +35,6 @@ namespace vfi {
 #define DF_RMAX 5
 #define DF_KTOP 15
 
-typedef __attribute__((address_space(3))) void* df_lptr_t;
-
-template <int K>
-__device__ __forceinline__ void df_wait_windows(int younger_groups) {
-    switch (younger_groups) {
-    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory"); break;
-    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K) : "memory"); break;
-    }
-}
-
 // One pixel's state for the channel loop.  lb[k]: float index, inside a staged window, of tap k's top-left
 // corner; phy / phx: the fractions of defor_tap; qx / qy bit k: the tap lies right of / below the sampling
 // position (VARIANT 1, 2).
@@ -135,11 +123,11 @@ __device__ __forceinline__ void df_run_channels(const float* __restrict__ img, f
     constexpr int NP = K * DF_THREADS;
     const int D = R - 1;
     auto issue = [&](int c, int slot) {
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * cs), 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(img + (int64_t)c * cs, plane_bytes);
         float* l = ring + slot * NP + tid;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (df_lptr_t)(l + k * DF_THREADS), 4, goff[k], 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * DF_THREADS), 4, goff[k], 0, 0, 0);
     };
     auto compute = [&](int c, int slot) {
         if (!px.valid) return;
@@ -157,13 +145,13 @@ __device__ __forceinline__ void df_run_channels(const float* __restrict__ img, f
     const int last = c_end - 1;
     for (int j = 0; j < D; ++j)
         if (c_begin + j <= last) issue(c_begin + j, j);
-    df_wait_windows<K>(min(c_begin + D - 1, last) - c_begin);
+    wait_windows<K>(min(c_begin + D - 1, last) - c_begin);
     __builtin_amdgcn_s_barrier();
     int slot = 0;
     for (int c = c_begin; c <= last; ++c) {
         if (c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);      // the slot read last iteration is free
         compute(c, slot);
-        if (c < last) df_wait_windows<K>(min(c + D, last) - (c + 1));
+        if (c < last) wait_windows<K>(min(c + D, last) - (c + 1));
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
@@ -181,14 +169,11 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
     int* box = reinterpret_cast<int*>(lds);
     const int tile = blockIdx.x;
     if (tile >= ntiles) return;
-    const int b = tile / (tiles_x * tiles_y);
-    const int trem = tile - b * (tiles_x * tiles_y);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int c_begin = blockIdx.y * ch_per_group;
-    const int c_end = min(channel, c_begin + ch_per_group);
+    const FiTile tp = fi_tile_at(tile, tiles_x, tiles_y, channel, ch_per_group);
+    const int b = tp.b, c_begin = tp.c_begin, c_end = tp.c_end;
     const int tid = threadIdx.x;
-    const int x = txi * DF_TW + (tid & (DF_TW - 1));
-    const int y = tyi * DF_TH + (tid >> 6);
+    const int x = tp.tx * DF_TW + (tid & (DF_TW - 1));
+    const int y = tp.ty * DF_TH + (tid >> 6);
 
     constexpr int NT = FS * FS;                             // taps
     DfPixel<FS> px;
@@ -222,10 +207,10 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
         // 32 (48) loads first.  Buffer form: a wave-uniform descriptor of this batch item's filter / offset tensor,
         // the channel as scalar offset, the pixel as the one vector offset -- no 64-bit address pair per load
         // (48 of them in flight cost 96 registers and spilled)
-        const auto frs = __builtin_amdgcn_make_buffer_rsrc((void*)(in3 + (int64_t)b * s3.b), 0, (int)filt_bytes, 0x00020000);
+        const auto frs = buffer_rsrc(in3 + (int64_t)b * s3.b, (int)filt_bytes);
         const auto ors = (VARIANT == VFI_DEFOR_NOFILTER)
                              ? frs
-                             : __builtin_amdgcn_make_buffer_rsrc((void*)(in4 + (int64_t)b * s4.b), 0, (int)off_bytes, 0x00020000);
+                             : buffer_rsrc(in4 + (int64_t)b * s4.b, (int)off_bytes);
         const unsigned fvo = 4u * (unsigned)(y * (int)s3.h + x);
         const unsigned ovo = (VARIANT == VFI_DEFOR_NOFILTER) ? fvo : 4u * (unsigned)(y * (int)s4.h + x);
         const unsigned ocs4 = 4u * (unsigned)((VARIANT == VFI_DEFOR_NOFILTER) ? s3.c : s4.c), fcs4 = 4u * (unsigned)s3.c;
@@ -264,19 +249,10 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
     }
 
     // ---- bounding box of every corner of the tile
-    if (tid == 0) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+    if (tid == 0) fi_box_clear(box);
     __syncthreads();
-    {
-        const int x0 = wave_min_i32(bx_lo), y0w = wave_min_i32(by_lo);
-        const int x1 = wave_max_i32(bx_hi), y1 = wave_max_i32(by_hi);
-        if ((tid & 63) == 0 && x0 != INT_MAX) {
-            atomicMin(&box[0], x0); atomicMin(&box[1], y0w);
-            atomicMax(&box[2], x1); atomicMax(&box[3], y1);
-        }
-    }
-    __syncthreads();
+    const bool any_valid = fi_box_fold(box, tid, bx_lo, by_lo, bx_hi, by_hi);
     const int bx0 = box[0], by0 = box[1];
-    const bool any_valid = bx0 != INT_MAX;
     const int bw = any_valid ? box[2] - bx0 + 1 : 0;
     const int bh = any_valid ? box[3] - by0 + 1 : 0;
     const int pitch = (bw + 31) & ~31;
@@ -291,7 +267,7 @@ __global__ __launch_bounds__(DF_THREADS, FS == 4 ? 3 : 1) void fi_forward_defor_
         if (px.valid) {
             const int plane_bytes = 4 * ((h - 1) * hs + w);
             for (int c = c_begin; c < c_end; ++c) {
-                const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * s1.c), 0, plane_bytes, 0x00020000);
+                const auto plane = buffer_rsrc(img + (int64_t)c * s1.c, plane_bytes);
                 dst[(int64_t)c * s1.c + px.pix] = df_value<VARIANT, FS>(px, [&](int k, float (&v)[4]) {
                     int ty = corner_y(k), tx = corner_x(k);
                     asm volatile("" : "+v"(ty), "+v"(tx));  // corner addresses re-derived per channel, not hoisted (registers)

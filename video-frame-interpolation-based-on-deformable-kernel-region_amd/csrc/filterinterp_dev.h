@@ -3,6 +3,10 @@
 #pragma once
 #include "vfi_common.h"
 
+#include <limits.h>
+
+#include <type_traits>
+
 namespace vfi {
 
 // One pixel's 4x4 window, fs == 4: every quadrant is 2x2.  v = the 16 image
@@ -45,40 +49,90 @@ __device__ __forceinline__ int fi_pitch_for(int bw) {
 // pitch `pitch`
 struct FiWindow { int bx0, by0, bw, bh, pitch, h, w, hs; };
 
-// channel loop of one valid pixel gathering straight from global memory.  Row by row, so the
-// register need is 4 taps + 4 sums (the compiler may still batch rows when it has registers
-// to spare); the operation order per quadrant is that of fi4_pixel.
-__device__ __forceinline__ void fi4_channels_direct(const float* __restrict__ img, float* __restrict__ dst,
-                                                    int c0, int c1, int64_t cs, int hs, int h, int w,
-                                                    int L, int T, const float (&f)[16], float alpha, float beta) {
-    // unsigned 32-bit element offsets from a wave-uniform plane pointer: the loads take the
-    // scalar-base + vector-offset form, one VGPR per address
-    unsigned ro[4], co[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ro[k] = (unsigned)(clampi(T + k, 0, h - 1) * hs);
-        co[k] = (unsigned)clampi(L + k, 0, w - 1);
-    }
-    for (int c = c0; c < c1; ++c) {
-        const float* p = img + (int64_t)c * cs;
-        float a0 = p[ro[0] + co[0]], a1 = p[ro[0] + co[1]], a2 = p[ro[0] + co[2]], a3 = p[ro[0] + co[3]];
-        float TL = a0 * f[0];  TL = fmaf(a1, f[1], TL);
-        float TR = a2 * f[2];  TR = fmaf(a3, f[3], TR);
-        a0 = p[ro[1] + co[0]]; a1 = p[ro[1] + co[1]]; a2 = p[ro[1] + co[2]]; a3 = p[ro[1] + co[3]];
-        TL = fmaf(a0, f[4], TL);  TL = fmaf(a1, f[5], TL);
-        TR = fmaf(a2, f[6], TR);  TR = fmaf(a3, f[7], TR);
-        a0 = p[ro[2] + co[0]]; a1 = p[ro[2] + co[1]]; a2 = p[ro[2] + co[2]]; a3 = p[ro[2] + co[3]];
-        float BL = a0 * f[8];   BL = fmaf(a1, f[9], BL);
-        float BR = a2 * f[10];  BR = fmaf(a3, f[11], BR);
-        a0 = p[ro[3] + co[0]]; a1 = p[ro[3] + co[1]]; a2 = p[ro[3] + co[2]]; a3 = p[ro[3] + co[3]];
-        BL = fmaf(a0, f[12], BL);  BL = fmaf(a1, f[13], BL);
-        BR = fmaf(a2, f[14], BR);  BR = fmaf(a3, f[15], BR);
-        dst[(int64_t)c * cs] = blend4(alpha, beta, TL, TR, BL, BR);
+// ---- shared by the LDS-staged kernels
+
+// compile-time loop: the body sees a constant index, so register arrays indexed by it stay in
+// registers (a runtime-indexed array would be demoted to scratch)
+template <int I, int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
     }
 }
 
-// one channel of one valid pixel, fs == 4, from precomputed clamped row / column offsets (the body of
-// fi4_channels_direct's loop)
+// s_waitcnt vmcnt(G*K): everything but the youngest G staged windows (K DMA loads each) has landed, G = younger_groups
+// (at most 3).  The count is clamped to the 6-bit vmcnt field: a smaller count only makes the wait stricter.  The pixel
+// stores of the compute phases sit in the same in-order counter; not counting them only makes the wait stricter too.
+template <int K>
+__device__ __forceinline__ void wait_windows(int younger_groups) {
+    switch (younger_groups) {
+    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K < 63 ? K : 63) : "memory"); break;
+    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K < 63 ? 2 * K : 63) : "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K < 63 ? 3 * K : 63) : "memory"); break;
+    }
+}
+
+// Bounding box of a tile in the 4 header words of its LDS array, box = {x0, y0, x1, y1}:
+//     if (tid == 0) fi_box_clear(box);
+//     __syncthreads();
+//     const bool any_valid = fi_box_fold(box, tid, lo_x, lo_y, hi_x, hi_y);
+// folds the smallest (lo_x, lo_y) and the largest (hi_x, hi_y) over the workgroup's threads into box, one lane per wave, and
+// ends with a barrier.  A thread with nothing to add passes INT_MAX / INT_MIN; false: no thread added anything.  (The
+// thread-0 branch stays in the kernel: moved into a helper, it changes the compiled kernels.)
+__device__ __forceinline__ void fi_box_clear(int* box) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+__device__ __forceinline__ bool fi_box_fold(int* box, int tid, int lo_x, int lo_y, int hi_x, int hi_y) {
+    const int x0 = wave_min_i32(lo_x), y0 = wave_min_i32(lo_y);
+    const int x1 = wave_max_i32(hi_x), y1 = wave_max_i32(hi_y);
+    if ((tid & 63) == 0 && x0 != INT_MAX) {
+        atomicMin(&box[0], x0); atomicMin(&box[1], y0);
+        atomicMax(&box[2], x1); atomicMax(&box[3], y1);
+    }
+    __syncthreads();
+    return box[0] != INT_MAX;
+}
+
+// A tile of a launch over tiles_x x tiles_y tiles per batch item, tile index row-major within an item: batch item b, tile
+// row ty, tile column tx, and the channel range [c_begin, c_end) of this workgroup (blockIdx.y of ch_per_group channels).
+struct FiTile { int b, ty, tx, c_begin, c_end; };
+__device__ __forceinline__ FiTile fi_tile_at(int tile, int tiles_x, int tiles_y, int channel, int ch_per_group) {
+    FiTile t;
+    t.b = tile / (tiles_x * tiles_y);
+    const int trem = tile - t.b * (tiles_x * tiles_y);
+    t.ty = trem / tiles_x;
+    t.tx = trem - t.ty * tiles_x;
+    t.c_begin = blockIdx.y * ch_per_group;
+    t.c_end = min(channel, t.c_begin + ch_per_group);
+    return t;
+}
+
+// XCD-grouped tile order.  Workgroups are dealt round-robin over the FI_XCDS XCDs, each with its own L2, and a tile's
+// window rows share their first and last 128-byte line with the horizontal neighbours' windows.  FI_XCD_RUN horizontally
+// consecutive tiles go to ONE XCD (workgroups b, b + 8, b + 16, b + 24 share an XCD and start together), so three of four
+// shared lines are L2 hits: EA read requests per C=196 launch 39.1 M -> 31.2 M (5.0 -> 4.0 GB), 1-9 % less time depending
+// on the box.  Larger departures from raster order lose more than they save: XCD-contiguous bands +12 % time, 4x2 / 2x2
+// tile blocks per XCD -25 % reads but +15-30 % time.
+// Contract: gridDim.x is a multiple of FI_XCDS x FI_XCD_RUN (fi_xcd_grid); workgroups whose tile is >= ntiles leave.
+#define FI_XCDS 8
+#define FI_XCD_RUN 4
+// device: the tile of workgroup bid = blockIdx.x, computed in type I.  The fp32 kernels compute it as int, the fp16 kernel as
+// unsigned: the same tiles, different instructions (one type for all would change some kernel's code).
+template <typename I>
+__device__ __forceinline__ int fi_xcd_tile(I bid) {
+    const I xs = bid % FI_XCDS, k = bid / FI_XCDS;
+    return ((k / FI_XCD_RUN) * FI_XCDS + xs) * FI_XCD_RUN + (k % FI_XCD_RUN);
+}
+// host: gridDim.x for ntiles tiles, each XCD's share rounded up to a multiple of ROUND
+template <int ROUND = FI_XCD_RUN>
+inline int fi_xcd_grid(int ntiles) {
+    static_assert(ROUND % FI_XCD_RUN == 0, "whole runs of tiles per XCD");
+    return ((ntiles + FI_XCDS - 1) / FI_XCDS + ROUND - 1) / ROUND * ROUND * FI_XCDS;
+}
+
+// one channel of one valid pixel, fs == 4, from precomputed clamped row / column offsets.  Row by row, so the register need
+// is 4 taps + 4 sums (the compiler may still batch rows when it has registers to spare); the operation order per quadrant is
+// that of fi4_pixel.
 __device__ __forceinline__ float fi4_value(const float* __restrict__ p, const unsigned (&ro)[4], const unsigned (&co)[4],
                                            const float (&f)[16], float alpha, float beta) {
     float a0 = p[ro[0] + co[0]], a1 = p[ro[0] + co[1]], a2 = p[ro[0] + co[2]], a3 = p[ro[0] + co[3]];
@@ -94,6 +148,21 @@ __device__ __forceinline__ float fi4_value(const float* __restrict__ p, const un
     BL = fmaf(a0, f[12], BL);  BL = fmaf(a1, f[13], BL);
     BR = fmaf(a2, f[14], BR);  BR = fmaf(a3, f[15], BR);
     return blend4(alpha, beta, TL, TR, BL, BR);
+}
+
+// channel loop of one valid pixel gathering straight from global memory
+__device__ __forceinline__ void fi4_channels_direct(const float* __restrict__ img, float* __restrict__ dst,
+                                                    int c0, int c1, int64_t cs, int hs, int h, int w,
+                                                    int L, int T, const float (&f)[16], float alpha, float beta) {
+    // unsigned 32-bit element offsets from a wave-uniform plane pointer: the loads take the
+    // scalar-base + vector-offset form, one VGPR per address
+    unsigned ro[4], co[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        ro[k] = (unsigned)(clampi(T + k, 0, h - 1) * hs);
+        co[k] = (unsigned)clampi(L + k, 0, w - 1);
+    }
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * cs] = fi4_value(img + (int64_t)c * cs, ro, co, f, alpha, beta);
 }
 
 // quadrant sums for a runtime filter size, rows outer / columns inner per quadrant

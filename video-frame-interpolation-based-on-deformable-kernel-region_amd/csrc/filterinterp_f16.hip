@@ -38,8 +38,6 @@ namespace vfi {
 #define F16_RMAX 5
 #define F16_KTOP 8
 
-typedef __attribute__((address_space(3))) void* f16_lptr_t;
-
 // fp32 -> fp16, round to nearest even, of a value that has first been rounded to fp32.  The empty asm
 // keeps hipcc from folding the conversion into the last FMA (v_fma_mixlo_f16 rounds the exact FMA
 // result to fp16 once; "the fp32 op, then .half()" rounds twice, and ties can fall the other way).
@@ -104,16 +102,6 @@ struct F16Pixel {
     float g[16];            // folded tap weights on the (possibly moved) 4x4 window
 };
 
-template <int K>
-__device__ __forceinline__ void f16_wait_windows(int younger_groups) {
-    switch (younger_groups) {
-    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory"); break;
-    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K) : "memory"); break;
-    }
-}
-
 // the two halves of a packed dword, widened (v_fma_mix_f32 reads them in place)
 __device__ __forceinline__ float f16_lo(unsigned d) { return __half2float(__ushort_as_half((unsigned short)(d & 0xffffu))); }
 __device__ __forceinline__ float f16_hi(unsigned d) { return __half2float(__ushort_as_half((unsigned short)(d >> 16))); }
@@ -148,7 +136,7 @@ __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img,
     }
     const int plane_bytes = (2 * ((win.h - 1) * win.hs + win.w) + 3) & ~3;
     const int wave_first = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
-    const unsigned ring_lds = (unsigned)(uintptr_t)(f16_lptr_t)ring;
+    const unsigned ring_lds = (unsigned)(uintptr_t)(lds_ptr_t)ring;
     const unsigned pitch4 = 4u * (unsigned)win.pitch;
     unsigned lb[F16_PX], sh[F16_PX], soff[F16_PX];
 #pragma unroll
@@ -161,11 +149,11 @@ __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img,
     const __half* pdma = img + (int64_t)c_begin * cs;
     __half* pout = out + (int64_t)c_begin * cs;
     auto issue = [&](int slot) {
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(pdma, plane_bytes);
         unsigned* l = ring + slot * NP + wave_first;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (f16_lptr_t)(l + k * F16_THREADS), 4, goff[k], 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * F16_THREADS), 4, goff[k], 0, 0, 0);
         pdma += cs;
     };
 #define F16_READ2(dst, addr) asm volatile("ds_read2_b32 %0, %1 offset0:0 offset1:1" : "=v"(dst) : "v"(addr))
@@ -192,7 +180,7 @@ __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img,
             acc = fmaf(f16_lo(e1), px[p].g[r * 4 + 2], acc);
             acc = fmaf(f16_hi(e1), px[p].g[r * 4 + 3], acc);
         }
-        const auto oplane = __builtin_amdgcn_make_buffer_rsrc((void*)plane_ptr, 0, plane_bytes, 0x00020000);
+        const auto oplane = buffer_rsrc(plane_ptr, plane_bytes);
         __builtin_amdgcn_raw_buffer_store_b16(__half_as_ushort(f16_store_value(acc)), oplane, soff[p], 0, 0);
     };
     auto compute = [&](int slot, bool first) {
@@ -213,7 +201,7 @@ __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img,
 #undef F16_READ1
     const int n0 = min(D, c_end - c_begin);
     for (int j = 0; j < n0; ++j) issue(j);
-    f16_wait_windows<K>(n0 - 1);                                // the first window has landed ...
+    wait_windows<K>(n0 - 1);                                    // the first window has landed ...
     __builtin_amdgcn_s_barrier();                               // ... in every wave
     int c = c_begin, slot = 0;
     for (; c + D <= last; ++c) {                                // steady state: window c + D exists
@@ -246,20 +234,15 @@ __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
     __shared__ unsigned lds[F16_HDR + F16_RING_DWORDS];
     int* box = reinterpret_cast<int*>(lds);
 
-    // four horizontally consecutive tiles on one XCD (workgroups are dealt round-robin to the 8 XCDs): the 128-byte lines
-    // a window shares with its left and right neighbours are fetched into one L2 (filterinterp_lds.hip)
-    const int xs = blockIdx.x % 8, kx = blockIdx.x / 8;
-    const int tile = ((kx / 4) * 8 + xs) * 4 + (kx % 4);
+    // four horizontally consecutive tiles per XCD (fi_xcd_tile)
+    const int tile = fi_xcd_tile<unsigned>(blockIdx.x);
     if (tile >= ntiles) return;
-    const int b = tile / (tiles_x * tiles_y);
-    const int trem = tile - b * (tiles_x * tiles_y);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int c_begin = blockIdx.y * ch_per_group;
-    const int c_end = min(channel, c_begin + ch_per_group);
+    const FiTile tp = fi_tile_at(tile, tiles_x, tiles_y, channel, ch_per_group);
+    const int b = tp.b, c_begin = tp.c_begin, c_end = tp.c_end;
 
     const int tid = threadIdx.x;
-    const int x = txi * F16_TW + (tid & (F16_TW - 1));
-    const int y0 = tyi * F16_TH + (tid >> 6);
+    const int x = tp.tx * F16_TW + (tid & (F16_TW - 1));
+    const int y0 = tp.ty * F16_TH + (tid >> 6);
 
     F16Pixel px[F16_PX];
     int L[F16_PX], Lc[F16_PX], T[F16_PX];
@@ -291,18 +274,9 @@ __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
         }
     }
 
-    if (tid == 0) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+    if (tid == 0) fi_box_clear(box);
     __syncthreads();
-    {
-        const int x0 = wave_min_i32(bx_lo), y0w = wave_min_i32(by_lo);
-        const int x1 = wave_max_i32(bx_hi), y1 = wave_max_i32(by_hi);
-        if ((tid & 63) == 0 && x0 != INT_MAX) {
-            atomicMin(&box[0], x0); atomicMin(&box[1], y0w);
-            atomicMax(&box[2], x1); atomicMax(&box[3], y1);
-        }
-    }
-    __syncthreads();
-    const bool any_valid = box[0] != INT_MAX;
+    const bool any_valid = fi_box_fold(box, tid, bx_lo, by_lo, bx_hi, by_hi);
     const int bx0 = any_valid ? box[0] & ~1 : 0, by0 = box[1];          // even: dword-aligned rows
     const int bw = any_valid ? (box[2] - bx0 + 2) >> 1 : 0;              // dwords per row
     const int bh = any_valid ? box[3] - by0 + 1 : 0;
@@ -401,8 +375,7 @@ extern "C" int vfi_filterinterp_forward_ori_f16(const void* input1, const float*
     const int ntiles = (int)nt;
     // split the channel range over blockIdx.y when that shortens the tail (as the fp32 kernel)
     const FiSplit split = fi_channel_split(ntiles, channel, 4.3);
-    const int grid_x = ((ntiles + 31) / 32) * 32;                   // whole groups of 8 XCDs x 4 tiles
-    hipLaunchKernelGGL(fi_forward_ori_lds_f16, dim3((unsigned)grid_x, (unsigned)split.groups, 1), dim3(F16_THREADS, 1, 1), 0,
+    hipLaunchKernelGGL(fi_forward_ori_lds_f16, dim3((unsigned)fi_xcd_grid(ntiles), (unsigned)split.groups, 1), dim3(F16_THREADS, 1, 1), 0,
                        (hipStream_t)stream, (const __half*)input1, input2, input3, (__half*)output, channel, h, w, s1, s2,
                        s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();

@@ -28,27 +28,13 @@
 // gathers from global memory instead -- same results, decided per workgroup.
 //
 // Launch: 1-D grid of tiles in row-major order, four consecutive tiles per XCD
-// (see the kernel).  An optional split of the channel range
+// (fi_xcd_tile, filterinterp_dev.h).  An optional split of the channel range
 // over blockIdx.y shortens the tail when the tile count does not fill the chip
 // evenly.
 #include "filterinterp_dev.h"
 #include "filterinterp_paths.h"
 
-#include <limits.h>
-
-#include <type_traits>
-
 namespace vfi {
-
-// compile-time loop: the body sees a constant index, so register arrays indexed by it stay in
-// registers (a runtime-indexed array would be demoted to scratch)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 #define FI_TW 64
 #define FI_TH 16
@@ -62,14 +48,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define FI_WAVES (8 / FI_PX)                        // waves per SIMD the kernel must fit (4: two 512-thread workgroups per CU)
 #define FI_KTOP (15 * FI_KS)                        // staged elements per thread and channel, at most (two ring slots)
 static_assert(2 * FI_KTOP * FI_THREADS <= FI_RING_FLOATS, "the largest window takes two ring slots");
-#define FI_XCDS 8
 #define FI_B64_MIN_BH 34                             // bounding box from which a tile takes the aligned 8-byte tap reads
 #define FI_B64_MIN_BW 92
-
-typedef __attribute__((address_space(3))) void* fi_lptr_t;
-
-__device__ __forceinline__ int wave_min(int v) { return wave_min_i32(v); }
-__device__ __forceinline__ int wave_max(int v) { return wave_max_i32(v); }
+#define FI_B64_PITCH_SKEW 32                        // 8-byte layout: row pitch = a multiple of 64 floats + this (= 32 mod 64)
 
 struct FiPixel {
     bool valid, inimg;
@@ -85,19 +66,6 @@ struct FiPixel {
 // most): the partner value is loaded inside the channel loop, which would cost a deep ring its depth.
 #define FI_BLEND_MAXC 4
 struct FiBlend { const float* other; float* out; float w0, w2; };
-
-// s_waitcnt vmcnt(G*K): everything but the youngest G staged windows (K DMA loads each) has landed.
-// The pixel stores of the compute phases sit in the same in-order counter; not counting them
-// only makes the wait stricter.
-template <int K>
-__device__ __forceinline__ void fi_wait_windows(int younger_groups) {
-    switch (younger_groups) {
-    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K < 63 ? K : 63) : "memory"); break;
-    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K < 63 ? 2 * K : 63) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K < 63 ? 3 * K : 63) : "memory"); break;
-    }
-}
 
 // Channel loop of one workgroup: K staged elements per thread and channel, ring of R slots.
 template <int K, bool BLEND>
@@ -130,14 +98,14 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
     constexpr int NP = K * FI_THREADS;                      // floats per ring slot
     constexpr int D = R - 1;                                // windows in flight
     auto issue = [&](int c, int slot) {
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * cs), 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(img + (int64_t)c * cs, plane_bytes);
         // (the LDS destination is M0 = the wave's first element.  Formed on the scalar unit from a provably uniform wave id it
         //  would save a vector add and a v_readfirstlane per load -- but hipcc then sees the DMA target alias the tap reads
         //  and drains vmcnt before every LDS read: 1.05 -> 1.61 ms.  From tid it does not.)
         float* l = ring + slot * NP + tid;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fi_lptr_t)(l + k * FI_THREADS), 4, goff[k], 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * FI_THREADS), 4, goff[k], 0, 0, 0);
     };
     auto finish = [&](int c, int p, const float (&v)[16], float* o) {
         const float val = fi4_pixel(v, px[p].f, px[p].alpha, px[p].beta);
@@ -174,7 +142,7 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
     const int last = c_end - 1;
     for (int j = 0; j < D; ++j)
         if (c_begin + j <= last) issue(c_begin + j, j);
-    fi_wait_windows<K>(min(c_begin + D - 1, last) - c_begin);      // window of c_begin has landed ...
+    wait_windows<K>(min(c_begin + D - 1, last) - c_begin);         // window of c_begin has landed ...
     __builtin_amdgcn_s_barrier();                                   // ... in every wave
     int slot = 0;
     for (int c = c_begin; c <= last; ++c) {
@@ -182,7 +150,7 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
         // (issuing before the compute phase measured ~5 % faster than after it)
         if (c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);
         compute(c, slot);
-        if (c < last) fi_wait_windows<K>(min(c + D, last) - (c + 1));
+        if (c < last) wait_windows<K>(min(c + D, last) - (c + 1));
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
@@ -230,6 +198,9 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     constexpr int R = (FI_RING_FLOATS / NP) < FI_RMAX ? (FI_RING_FLOATS / NP) : FI_RMAX;
     constexpr int D = R - 1;
     static_assert(D >= 1 && (D - 1) * K <= 63, "ring geometry");
+    // the ds_read_b64 tap reads: the LDS array is 16-byte aligned, and every byte offset added to it is a multiple of 8 (header,
+    // slot stride, row pitch; lbase is rounded down to even)
+    static_assert((FI_HDR * 4) % 8 == 0 && (NP * 4) % 8 == 0 && FI_B64_PITCH_SKEW % 2 == 0, "8-byte tap reads stay 8-byte aligned");
     if (c_begin >= c_end) return;
     const float inv_pitch32 = 1.0f / (float)win.pitch;
     unsigned goff[K];
@@ -244,7 +215,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     }
     const int plane_bytes = 4 * ((win.h - 1) * win.hs + win.w);
     const int wave_first = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
-    const unsigned ring_lds = (unsigned)(uintptr_t)(fi_lptr_t)ring;
+    const unsigned ring_lds = (unsigned)(uintptr_t)(lds_ptr_t)ring;
     const unsigned pitch4 = 4u * (unsigned)win.pitch;
     unsigned lb[FI_PX], soff[FI_PX];
 #pragma unroll
@@ -271,8 +242,8 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     // offset with num_records - soffset: a lane whose offset is 0x80000000 is dropped whatever the plane.  (Host: bit 29
     // promises 4 * cs + plane_bytes < 2^31.)
     constexpr bool ONE = DMA16;
-    auto din = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, 0x7fffffff, 0x00020000);
-    auto dout = __builtin_amdgcn_make_buffer_rsrc((void*)pout, 0, 0x7fffffff, 0x00020000);
+    auto din = buffer_rsrc(pdma, 0x7fffffff);
+    auto dout = buffer_rsrc(pout, 0x7fffffff);
     const int cs4 = (int)(cs * 4);
     const int soff_max = 0x7fffffff - plane_bytes - cs4;      // largest scalar offset whose successor plane is still in range
     int sin = 0, sout = 0;
@@ -280,7 +251,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         if (__builtin_expect(sin > soff_max, 0)) {
             asm volatile("; the input descriptor moves up" ::: "memory");    // (keeps this a branch: as selects it costs ten scalar instructions per channel)
             pdma = (const float*)((const char*)pdma + sin);
-            din = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, 0x7fffffff, 0x00020000);
+            din = buffer_rsrc(pdma, 0x7fffffff);
             sin = 0;
         }
         sin += cs4;
@@ -289,19 +260,19 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         if (__builtin_expect(sout > soff_max, 0)) {
             asm volatile("; the output descriptor moves up" ::: "memory");
             pout = (float*)((char*)pout + sout);
-            dout = __builtin_amdgcn_make_buffer_rsrc((void*)pout, 0, 0x7fffffff, 0x00020000);
+            dout = buffer_rsrc(pout, 0x7fffffff);
             sout = 0;
         }
         sout += cs4;
     };
     constexpr unsigned SLOT = NP * 4, RING = R * SLOT;       // bytes
     auto issue = [&](unsigned slot) {                           // (slots by their byte offset in the ring: one scalar add per step instead of a multiply)
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(pdma, plane_bytes);
         float* l = ring + (slot >> 2) + wave_first * EPT;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            if constexpr (ONE) __builtin_amdgcn_raw_ptr_buffer_load_lds(din, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], sin, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fi_lptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], 0, 0, 0);
+            if constexpr (ONE) __builtin_amdgcn_raw_ptr_buffer_load_lds(din, (lds_ptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], sin, 0, 0);
+            else __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * FI_THREADS * EPT), 4 * EPT, goff[k], 0, 0, 0);
         }
         if constexpr (ONE) { next_in(); return; }
         pdma += cs;
@@ -309,7 +280,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
 #define FI_READ2(dst, addr, o0, o1) asm volatile("ds_read2_b32 %0, %1 offset0:" #o0 " offset1:" #o1 : "=v"(dst) : "v"(addr))
 #define FI_READ64(dst, addr, o) asm volatile("ds_read_b64 %0, %1 offset:" #o : "=v"(dst) : "v"(addr))
     auto compute = [&](unsigned so) {
-        const auto oplane = __builtin_amdgcn_make_buffer_rsrc((void*)pout, 0, plane_bytes, 0x00020000);
+        const auto oplane = buffer_rsrc(pout, plane_bytes);
         // Tap reads of pixel p come in two parts (4-byte reads: rows 0-1, then rows 2-3; 8-byte reads: row 0, then rows 1-3);
         // before pixel p is multiplied, all of its reads and the first part of pixel p + 1's have been issued: two pixels'
         // registers ping-pong, at most 12 (15) LDS reads are outstanding.
@@ -444,7 +415,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         if constexpr (ONE) {
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout - (p ? cs4 : 0), 0);
         } else {
-            const auto oplane = __builtin_amdgcn_make_buffer_rsrc((void*)plane_ptr, 0, plane_bytes, 0x00020000);
+            const auto oplane = buffer_rsrc(plane_ptr, plane_bytes);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), oplane, soff[p], 0, 0);
         }
     };
@@ -468,7 +439,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     //  steady state, out-of-range stores behind the prologue's windows so that the first steps see the same stream, m K + (D - 1)
     //  FI_PX in the last steps -- bit-identical, and measured nothing: 1.056-1.066 against 1.063-1.080 ms.  The simple rule stays.)
     for (int j = 0; j < n0; ++j) issue((unsigned)j * SLOT);
-    fi_wait_windows<K>(n0 - 1);                                 // the first window has landed ...
+    wait_windows<K>(n0 - 1);                                    // the first window has landed ...
     __builtin_amdgcn_s_barrier();                               // ... in every wave
     int c = c_begin;
     unsigned slot = 0, freed = RING - SLOT;                      // the window being read; the slot every wave finished reading before the last barrier
@@ -523,30 +494,17 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     int tiles_x, int tiles_y, int ntiles, int ch_per_group, int aligned16, FiBlend blend) {
     // ONE LDS array (a second __shared__ object beside an LDS-DMA target makes hipcc drain vmcnt
     // before LDS reads): 16-float header holding the bounding box, then the window ring
-    __shared__ float lds[FI_HDR + FI_RING_FLOATS];
-    int* box = reinterpret_cast<int*>(lds);
+    __shared__ __attribute__((aligned(16))) float lds[FI_HDR + FI_RING_FLOATS];
 
-    // ---- block -> tile
-    const int bid = blockIdx.x;
-    // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and a tile's window rows share
-    // their first and last 128-byte line with the horizontal neighbours' windows.  G = 4 horizontally
-    // consecutive tiles go to ONE XCD (workgroups b, b + 8, b + 16, b + 24 share an XCD and start together), so
-    // three of four shared lines are L2 hits: EA read requests per C=196 launch 39.1 M -> 31.2 M (5.0 -> 4.0 GB),
-    // 1-9 % less time depending on the box.  Larger departures from raster order lose more than they save:
-    // XCD-contiguous bands +12 % time, 4x2 / 2x2 tile blocks per XCD -25 % reads but +15-30 % time.
-    constexpr int G = 4;
-    const int xs = bid % FI_XCDS, k = bid / FI_XCDS;
-    const int tile = ((k / G) * FI_XCDS + xs) * G + (k % G);
+    // ---- block -> tile: four horizontally consecutive tiles per XCD (fi_xcd_tile)
+    const int tile = fi_xcd_tile<int>(blockIdx.x);
     if (tile >= ntiles) return;                             // whole workgroup leaves together
-    const int b = tile / (tiles_x * tiles_y);
-    const int trem = tile - b * (tiles_x * tiles_y);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int c_begin = blockIdx.y * ch_per_group;
-    const int c_end = min(channel, c_begin + ch_per_group);
+    const FiTile tp = fi_tile_at(tile, tiles_x, tiles_y, channel, ch_per_group);
+    const int b = tp.b, c_begin = tp.c_begin, c_end = tp.c_end;
 
     const int tid = threadIdx.x;
-    const int x = txi * FI_TW + (tid & (FI_TW - 1));
-    const int y0 = tyi * FI_TH + (tid >> 6);
+    const int x = tp.tx * FI_TW + (tid & (FI_TW - 1));
+    const int y0 = tp.ty * FI_TH + (tid >> 6);
 
     // ---- this thread's pixels: flow, validity, window origin, blend weights.  The 16 filter taps of each pixel are
     // fetched in the same round trip as its flow (they do not depend on it: a pixel the flow then declares invalid
@@ -592,18 +550,10 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     }
 
     // ---- bounding box of every tap of the tile (unclamped window coordinates)
-    if (tid == 0) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+    int* box = reinterpret_cast<int*>(lds);
+    if (tid == 0) fi_box_clear(box);
     __syncthreads();
-    {
-        const int x0 = wave_min(bx_lo), y0w = wave_min(by_lo);
-        const int x1 = wave_max(bx_hi), y1 = wave_max(by_hi);
-        if ((tid & 63) == 0 && x0 != INT_MAX) {
-            atomicMin(&box[0], x0); atomicMin(&box[1], y0w);
-            atomicMax(&box[2], x1); atomicMax(&box[3], y1);
-        }
-    }
-    __syncthreads();
-    const bool any_valid = box[0] != INT_MAX;
+    const bool any_valid = fi_box_fold(box, tid, bx_lo, by_lo, bx_hi, by_hi);
     // The lean channel loop (the plain one under a blend epilogue), tap reads chosen per tile: a tall or
     // wide bounding box marks a rough flow field, where the lanes of a wave sit on many window rows and columns and LDS bank
     // conflicts dominate -- there the aligned 8-byte reads win (C=196 on the "quarter" field: 1.77 -> 1.61 ms; all tiles on
@@ -619,13 +569,13 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     const bool can16 = lean && aligned16 && any_valid && box[0] >= 0 && box[2] < w;
     const int lo = can16 ? (box[0] & ~3) : box[0];
     const int bw64 = any_valid ? box[2] - (lo & ~1) + 1 : 0;
-    const bool fits64 = ((((bw64 + 31) >> 6) << 6) + 32) * raw_bh <= 10 * FI_KS * FI_THREADS;
+    const bool fits64 = ((((bw64 + 31) >> 6) << 6) + FI_B64_PITCH_SKEW) * raw_bh <= 10 * FI_KS * FI_THREADS;
     const bool use64 = lean && fits64 && (raw_bh >= FI_B64_MIN_BH || raw_bw >= FI_B64_MIN_BW);
     const int bx0 = (use64 && any_valid) ? (lo & ~1) : lo, by0 = box[1];       // 8-byte reads: window columns keep the image's parity
     const int bw = any_valid ? box[2] - bx0 + 1 : 0;
     const int bh = raw_bh;
     // LDS row pitch: a multiple of the 32 banks; 8-byte reads see 64 banks: = 32 mod 64
-    const int pitch = use64 ? (((bw + 31) >> 6) << 6) + 32 : fi_pitch_for(bw);
+    const int pitch = use64 ? (((bw + 31) >> 6) << 6) + FI_B64_PITCH_SKEW : fi_pitch_for(bw);
     const int n = pitch * bh;                               // <= (w+33)*(h+2): fits int for any real frame
 
 #pragma unroll
@@ -708,14 +658,14 @@ static int forward_ori_lds(const float* input1, const float* input2, const float
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
     if (nt > (1 << 28)) return FI_DECLINED;
     const int ntiles = (int)nt;
-    const int per_xcd = (((ntiles + FI_XCDS - 1) / FI_XCDS) + 7) & ~7;         // (a multiple of 8: whole groups of four tiles)
 
     // split the channel range over blockIdx.y when that shortens the tail: two workgroups per
     // CU run at a time; every extra group re-reads the flow + 16 filter planes (72 B/pixel)
     // next to 8 B/pixel/channel of image traffic.  The blend epilogue keeps a pixel's channels in one workgroup.
     const FiSplit split = blend.out ? FiSplit{channel, 1} : fi_channel_split(ntiles, channel, 4.3);
 
-    const dim3 grid((unsigned)(per_xcd * FI_XCDS), (unsigned)split.groups, 1);
+    // (each XCD's share rounded up to 8 tiles: whole runs of four)
+    const dim3 grid((unsigned)fi_xcd_grid<8>(ntiles), (unsigned)split.groups, 1);
     // (16-byte staging: rows of input1 on 16-byte boundaries; its single-descriptor addressing: two planes within 2^31 bytes)
     const int aligned16 = !(w & 3) && !(s1.h & 3) && !(s1.c & 3) && !(s1.b & 3) && !((uintptr_t)input1 & 15) &&
                           s1.c > 0 && 4 * s1.c + 4 * ((int64_t)(h - 1) * s1.h + w) < 0x7fffffffLL;

@@ -25,18 +25,6 @@ namespace vfi {
 #define FN_RMAX 5
 #define FN_KTOP 15
 
-typedef __attribute__((address_space(3))) void* fn_lptr_t;
-
-template <int K>
-__device__ __forceinline__ void fn_wait_windows(int younger_groups) {
-    switch (younger_groups) {
-    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory"); break;
-    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K) : "memory"); break;
-    }
-}
-
 template <int FS>
 struct FnPixel {
     bool valid, inimg;
@@ -84,11 +72,11 @@ __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, f
     constexpr int NP = K * FN_THREADS;
     const int D = R - 1;
     auto issue = [&](int c, int slot) {
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * cs), 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(img + (int64_t)c * cs, plane_bytes);
         float* l = ring + slot * NP + tid;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fn_lptr_t)(l + k * FN_THREADS), 4, goff[k], 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * FN_THREADS), 4, goff[k], 0, 0, 0);
     };
     auto compute = [&](int c, int slot) {
         if (!px.valid) return;
@@ -100,13 +88,13 @@ __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, f
     const int last = c_end - 1;
     for (int j = 0; j < D; ++j)
         if (c_begin + j <= last) issue(c_begin + j, j);
-    fn_wait_windows<K>(min(c_begin + D - 1, last) - c_begin);
+    wait_windows<K>(min(c_begin + D - 1, last) - c_begin);
     __builtin_amdgcn_s_barrier();
     int slot = 0;
     for (int c = c_begin; c <= last; ++c) {
         if (c + D <= last) issue(c + D, slot == 0 ? R - 1 : slot - 1);      // the slot read last iteration is free
         compute(c, slot);
-        if (c < last) fn_wait_windows<K>(min(c + D, last) - (c + 1));
+        if (c < last) wait_windows<K>(min(c + D, last) - (c + 1));
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
@@ -124,14 +112,11 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
     int* box = reinterpret_cast<int*>(lds);
     const int tile = blockIdx.x;
     if (tile >= ntiles) return;
-    const int b = tile / (tiles_x * tiles_y);
-    const int trem = tile - b * (tiles_x * tiles_y);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int c_begin = blockIdx.y * ch_per_group;
-    const int c_end = min(channel, c_begin + ch_per_group);
+    const FiTile tp = fi_tile_at(tile, tiles_x, tiles_y, channel, ch_per_group);
+    const int b = tp.b, c_begin = tp.c_begin, c_end = tp.c_end;
     const int tid = threadIdx.x;
-    const int x = txi * FN_TW + (tid & (FN_TW - 1));
-    const int y = tyi * FN_TH + (tid >> 6);
+    const int x = tp.tx * FN_TW + (tid & (FN_TW - 1));
+    const int y = tp.ty * FN_TH + (tid >> 6);
 
     FnPixel<FS> px;
     px.inimg = x < w && y < h;
@@ -150,9 +135,10 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
     px.alpha = x2 - (float)ix;
     px.beta = y2 - (float)iy;
 
-    if (tid == 0) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+    if (tid == 0) fi_box_clear(box);
     __syncthreads();
     {
+        // (fi_box_fold written out: called with these selects as its arguments, it changes how this kernel is scheduled)
         const int x0 = wave_min_i32(px.valid ? L : INT_MAX), y0w = wave_min_i32(px.valid ? T : INT_MAX);
         const int x1 = wave_max_i32(px.valid ? L + FS - 1 : INT_MIN), y1 = wave_max_i32(px.valid ? T + FS - 1 : INT_MIN);
         if ((tid & 63) == 0 && x0 != INT_MAX) {
@@ -186,7 +172,7 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
         if (px.valid) {
             const int plane_bytes = 4 * ((h - 1) * hs + w);
             for (int c = c_begin; c < c_end; ++c) {
-                const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)(img + (int64_t)c * s1.c), 0, plane_bytes, 0x00020000);
+                const auto plane = buffer_rsrc(img + (int64_t)c * s1.c, plane_bytes);
                 dst[(int64_t)c * s1.c + px.pix] = fn_value<FS>(px, [&](int r, int k) {
                     int ty = T, tx = L;
                     asm volatile("" : "+v"(ty), "+v"(tx));  // tap addresses re-derived per channel, not hoisted (registers)

@@ -11,8 +11,9 @@
 // traffic, the same LDS reads and arithmetic.  Semantics per output: filterinterpolation_cuda_kernel.cu:2692-2823,
 // bit for bit the single-flow kernel's (same taps, same order).
 //
-// Tiling, LDS-DMA ring, counted vmcnt and tile -> XCD grouping: exactly filterinterp_lds.hip (see there); a thread
-// owns two pixels, each with two (validity, window address, blend weights) and one set of 16 filter taps.
+// Tiling, LDS-DMA ring, counted vmcnt and tile -> XCD grouping: exactly filterinterp_lds.hip (see there and
+// filterinterp_dev.h); a thread owns two pixels, each with two (validity, window address, blend weights) and one set of
+// 16 filter taps.
 //
 // Round 4: the window is staged as PAIRS.  With two outputs per staged window the launch is bound by its consumer side --
 // LDS tap reads and vector issue (profiles/: three times the single-flow kernel's LDS cycles for one window's staging) --
@@ -24,10 +25,6 @@
 // time), which the two outputs per window pay for.  The four blend weights of an evaluation are formed once per tile
 // (blend4's own products: same bits) instead of once per channel.
 #include "filterinterp_dev.h"
-
-#include <limits.h>
-
-#include <type_traits>
 
 namespace vfi {
 
@@ -41,19 +38,7 @@ namespace vfi {
 #define FM_RMAX 5
 #define FM_KTOP 15                                  // staged dwords per thread and channel, at most
 #define FM_KPAIR 18                                 // ... of a window staged as pairs: classes 3 x 3 ... 3 x 6, 4 x 3, 4 x 4
-#define FM_XCDS 8
 #define FM_NT 2                                     // flows per launch (three flows go as 2 + 1: see the host)
-
-typedef __attribute__((address_space(3))) void* fm_lptr_t;
-
-// compile-time loop: the body sees a constant index (register arrays indexed by it stay in registers)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 struct FmPtrs { const float* flow[FM_NT]; float* out[FM_NT]; };
 
@@ -66,16 +51,6 @@ struct FmPixel {
     float alpha[FM_NT], beta[FM_NT];
     int lbase[FM_NT];       // pair index of the 4x4 window origin of flow t inside the staged window
 };
-
-template <int K>
-__device__ __forceinline__ void fm_wait_windows(int younger_groups) {
-    switch (younger_groups) {
-    case 0:  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K < 63 ? K : 63) : "memory"); break;
-    case 2:  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * K < 63 ? 2 * K : 63) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * K < 63 ? 3 * K : 63) : "memory"); break;
-    }
-}
 
 // Channel loop of one workgroup on a window staged as pairs, written like fi_run_channels_lean (filterinterp_lds.hip): ring
 // geometry a compile-time function of the window class and one constant s_waitcnt in the steady state, running plane pointers,
@@ -115,7 +90,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
         voff[s_] = colp < win.bwp ? 4u * (unsigned)clampi(win.bx0 + colp + 2 * (lane & 1), 0, win.w - 1) : 0x80000000u;
     }
     const int plane_bytes = 4 * ((win.h - 1) * win.hs + win.w);
-    const unsigned ring_lds = (unsigned)(uintptr_t)(fm_lptr_t)ring;
+    const unsigned ring_lds = (unsigned)(uintptr_t)(lds_ptr_t)ring;
     unsigned lb[NE], pix4[FM_PX];
     float W[NE][4];                                          // blend4's weights of an evaluation: (1-a)(1-b), a(1-b), (1-a)b, ab
 #pragma unroll
@@ -147,11 +122,11 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
             const int row = wave + 8 * k;                                       // (scalar)
             const bool live = row < win.bh;
             // (a row past the window: zero records -- every offset out of range)
-            const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, live ? plane_bytes : 0, 0x00020000);
+            const auto plane = buffer_rsrc(pdma, live ? plane_bytes : 0);
             const int soff = live ? 4 * clampi(win.by0 + row, 0, win.h - 1) * win.hs : 0;
 #pragma unroll
             for (int s_ = 0; s_ < S; ++s_)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fm_lptr_t)(l + (8 * k * S + s_) * 64), 4, voff[s_], soff, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + (8 * k * S + s_) * 64), 4, voff[s_], soff, 0, 0);
         }
         pdma += cs;
     };
@@ -172,7 +147,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
             val = fmaf(W[e][1], top.y, val);
             val = fmaf(W[e][2], bot.x, val);
             val = fmaf(W[e][3], bot.y, val);
-            const auto oplane = __builtin_amdgcn_make_buffer_rsrc((void*)(ptr.out[t] + oofs), 0, plane_bytes, 0x00020000);
+            const auto oplane = buffer_rsrc(ptr.out[t] + oofs, plane_bytes);
             // an invalid evaluation's store is dropped by the range check.  (The select is formed here, from a validity mask
             // the compiler keeps in scalar registers: loop-invariant offsets per evaluation instead of per pixel cost registers.)
             unsigned po = pix4[p];
@@ -223,14 +198,14 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
     static_assert(NWAIT <= 63, "vmcnt is six bits");
     const int n0 = min(D, c_end - c_begin);
     {
-        const auto nowhere = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, 0, 0x00020000);      // (zero records: every offset out of range)
+        const auto nowhere = buffer_rsrc(img, 0);      // (zero records: every offset out of range)
         for (int j = 0; j < n0; ++j) {
             issue(j);
 #pragma unroll
             for (int e = 0; e < NE; ++e) __builtin_amdgcn_raw_buffer_store_b32(0u, nowhere, 0x80000000u, 0, 0);
         }
     }
-    fm_wait_windows<K>(n0 - 1);                                 // the first window has landed ...
+    wait_windows<K>(n0 - 1);                                    // the first window has landed ...
     __builtin_amdgcn_s_barrier();                               // ... in every wave
     int c = c_begin, slot = 0;
     for (; c + D <= last; ++c) {                                // steady state: window c + D exists
@@ -296,7 +271,7 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
     }
     const int plane_bytes = 4 * ((win.h - 1) * win.hs + win.w);
     const int wave_first = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
-    const unsigned ring_lds = (unsigned)(uintptr_t)(fm_lptr_t)ring;
+    const unsigned ring_lds = (unsigned)(uintptr_t)(lds_ptr_t)ring;
     const unsigned pitch4 = 4u * (unsigned)win.pitch;
     unsigned lb[NE], pix4[FM_PX];
 #pragma unroll
@@ -319,11 +294,11 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
     const float* pdma = img + (int64_t)c_begin * cs;
     int64_t oofs = boff + (int64_t)c_begin * cs;            // element offset of the output plane inside every output tensor
     auto issue = [&](int slot) {
-        const auto plane = __builtin_amdgcn_make_buffer_rsrc((void*)pdma, 0, plane_bytes, 0x00020000);
+        const auto plane = buffer_rsrc(pdma, plane_bytes);
         float* l = ring + slot * NP + wave_first;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (fm_lptr_t)(l + k * FM_THREADS), 4, goff[k], 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(plane, (lds_ptr_t)(l + k * FM_THREADS), 4, goff[k], 0, 0, 0);
         pdma += cs;
     };
 #define FM_READ2(dst, addr, o0, o1) asm volatile("ds_read2_b32 %0, %1 offset0:" #o0 " offset1:" #o1 : "=v"(dst) : "v"(addr))
@@ -360,7 +335,7 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
             float al = px[p].alpha[t], be = px[p].beta[t];
             asm volatile("" : "+v"(al), "+v"(be));
             const float val = blend4(al, be, top.x, top.y, bot.x, bot.y);
-            const auto oplane = __builtin_amdgcn_make_buffer_rsrc((void*)(ptr.out[t] + oofs), 0, plane_bytes, 0x00020000);
+            const auto oplane = buffer_rsrc(ptr.out[t] + oofs, plane_bytes);
             unsigned po = pix4[p];                          // (an invalid evaluation's store is dropped by the range check)
             asm volatile("" : "+v"(po));
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), oplane, px[p].valid[t] ? po : 0x80000000u, 0, 0);
@@ -379,14 +354,14 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
     static_assert(NWAIT <= 63, "vmcnt is six bits");
     const int n0 = min(D, c_end - c_begin);
     {
-        const auto nowhere = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, 0, 0x00020000);
+        const auto nowhere = buffer_rsrc(img, 0);
         for (int j = 0; j < n0; ++j) {
             issue(j);
 #pragma unroll
             for (int e = 0; e < NE; ++e) __builtin_amdgcn_raw_buffer_store_b32(0u, nowhere, 0x80000000u, 0, 0);
         }
     }
-    fm_wait_windows<K>(n0 - 1);                                 // the first window has landed ...
+    wait_windows<K>(n0 - 1);                                    // the first window has landed ...
     __builtin_amdgcn_s_barrier();                               // ... in every wave
     int c = c_begin, slot = 0;
     for (; c + D <= last; ++c) {                                // steady state: window c + D exists
@@ -426,20 +401,15 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
     __shared__ __attribute__((aligned(16))) float lds[FM_HDR + FM_RING_FLOATS];
     int* box = reinterpret_cast<int*>(lds);
 
-    // four horizontally consecutive tiles per XCD (filterinterp_lds.hip)
-    const int bid = blockIdx.x;
-    const int xs = bid % FM_XCDS, kk = bid / FM_XCDS;
-    const int tile = ((kk / 4) * FM_XCDS + xs) * 4 + (kk % 4);
+    // four horizontally consecutive tiles per XCD (fi_xcd_tile)
+    const int tile = fi_xcd_tile<int>(blockIdx.x);
     if (tile >= ntiles) return;
-    const int b = tile / (tiles_x * tiles_y);
-    const int trem = tile - b * (tiles_x * tiles_y);
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int c_begin = blockIdx.y * ch_per_group;
-    const int c_end = min(channel, c_begin + ch_per_group);
+    const FiTile tp = fi_tile_at(tile, tiles_x, tiles_y, channel, ch_per_group);
+    const int b = tp.b, c_begin = tp.c_begin, c_end = tp.c_end;
 
     const int tid = threadIdx.x;
-    const int x = txi * FM_TW + (tid & (FM_TW - 1));
-    const int y0 = tyi * FM_TH + (tid >> 6);
+    const int x = tp.tx * FM_TW + (tid & (FM_TW - 1));
+    const int y0 = tp.ty * FM_TH + (tid >> 6);
 
     const int flow_bytes = ((int)s2.c + (h - 1) * (int)s2.h + w) * 4;           // (the host checked that these fit 31 bits)
     const int filt_bytes = (15 * (int)s3.c + (h - 1) * (int)s3.h + w) * 4;
@@ -461,11 +431,11 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
             const int fo = (y * (int)s2.h + x) * 4, ko = (y * (int)s3.h + x) * 4;
 #pragma unroll
             for (int t = 0; t < FM_NT; ++t) {
-                const auto fr = __builtin_amdgcn_make_buffer_rsrc((void*)(ptr.flow[t] + (int64_t)b * s2.b), 0, flow_bytes, 0x00020000);
+                const auto fr = buffer_rsrc(ptr.flow[t] + (int64_t)b * s2.b, flow_bytes);
                 fxv[p][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(fr, fo, 0, 0));
                 fyv[p][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(fr, fo, (int)s2.c * 4, 0));
             }
-            const auto kr = __builtin_amdgcn_make_buffer_rsrc((void*)(in3 + (int64_t)b * s3.b), 0, filt_bytes, 0x00020000);
+            const auto kr = buffer_rsrc(in3 + (int64_t)b * s3.b, filt_bytes);
 #pragma unroll
             for (int k = 0; k < 16; ++k) px[p].f[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(kr, ko, k * (int)s3.c * 4, 0));
         }
@@ -492,19 +462,10 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
     }
 
     // ---- bounding box of every tap of the tile, all flows
-    if (tid == 0) { box[0] = INT_MAX; box[1] = INT_MAX; box[2] = INT_MIN; box[3] = INT_MIN; }
+    if (tid == 0) fi_box_clear(box);
     __syncthreads();
-    {
-        const int x0 = wave_min_i32(bx_lo), y0w = wave_min_i32(by_lo);
-        const int x1 = wave_max_i32(bx_hi), y1 = wave_max_i32(by_hi);
-        if ((tid & 63) == 0 && x0 != INT_MAX) {
-            atomicMin(&box[0], x0); atomicMin(&box[1], y0w);
-            atomicMax(&box[2], x1); atomicMax(&box[3], y1);
-        }
-    }
-    __syncthreads();
+    const bool any_valid = fi_box_fold(box, tid, bx_lo, by_lo, bx_hi, by_hi);
     const int bx0 = box[0], by0 = box[1];
-    const bool any_valid = bx0 != INT_MAX;
     const int bw = any_valid ? box[2] - bx0 + 1 : 0;
     const int bh = any_valid ? box[3] - by0 + 1 : 0;
     // the slot holds pairs (column c, column c + 2): bw - 2 of them per row, pitch a multiple of 32 pairs; a window too large
@@ -604,12 +565,11 @@ extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const flo
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
     if (nt > (1 << 28)) return VFI_ERR_SHAPE;
     const int ntiles = (int)nt;
-    const int per_xcd = (((ntiles + FM_XCDS - 1) / FM_XCDS) + 3) & ~3;          // whole groups of four tiles
     // (one prologue for nflows outputs per channel)
     const FiSplit split = fi_channel_split(ntiles, channel, 4.3 * (1.0 + 0.3 * (nflows - 1)) / nflows);
     FmPtrs ptr;
     for (int t = 0; t < FM_NT; ++t) { ptr.flow[t] = flows[t]; ptr.out[t] = outputs[t]; }
-    const dim3 grid((unsigned)(per_xcd * FM_XCDS), (unsigned)split.groups, 1), block(FM_THREADS, 1, 1);
+    const dim3 grid((unsigned)fi_xcd_grid(ntiles), (unsigned)split.groups, 1), block(FM_THREADS, 1, 1);
     hipLaunchKernelGGL(fi_forward_ori_multi, grid, block, 0, (hipStream_t)stream, input1, ptr, input3, channel, h, w, s1, s2, s3,
                        tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();

@@ -162,11 +162,11 @@ __device__ __forceinline__ ProjPlanes proj_planes(const ProjSrc& s, int b, int h
     const ProjImage im = proj_image(b, s.per);
     const float* f0 = s.flow[im.item] + (int64_t)im.bi * s.fb;
     ProjPlanes p;
-    p.f0 = __builtin_amdgcn_make_buffer_rsrc((void*)f0, 0, ((h - 1) * s.fh + w) * 4, 0x00020000);
-    p.f1 = __builtin_amdgcn_make_buffer_rsrc((void*)(f0 + s.fc), 0, ((h - 1) * s.fh + w) * 4, 0x00020000);
+    p.f0 = buffer_rsrc(f0, ((h - 1) * s.fh + w) * 4);
+    p.f1 = buffer_rsrc(f0 + s.fc, ((h - 1) * s.fh + w) * 4);
     p.d = p.f0;
     if constexpr (DEPTH)
-        p.d = __builtin_amdgcn_make_buffer_rsrc((void*)(s.depth[im.item] + (int64_t)im.bi * s.db), 0, ((h - 1) * s.dh + w) * 4, 0x00020000);
+        p.d = buffer_rsrc(s.depth[im.item] + (int64_t)im.bi * s.db, ((h - 1) * s.dh + w) * 4);
     return p;
 }
 __device__ __forceinline__ float buf_f32(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
@@ -826,9 +826,9 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     const ProjImage im = proj_image(b, src.per);
     float* const out = dst.out[im.item] + (int64_t)im.bi * ob;
     float* const count = dst.count[im.item] + (int64_t)im.bi * cb;
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, ((g.h - 1) * oh + g.w) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro1 = __builtin_amdgcn_make_buffer_rsrc((void*)(out + oc), 0, ((g.h - 1) * oh + g.w) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rcn = __builtin_amdgcn_make_buffer_rsrc((void*)count, 0, ((g.h - 1) * ch + g.w) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro0 = buffer_rsrc(out, ((g.h - 1) * oh + g.w) * 4);
+    const __amdgpu_buffer_rsrc_t ro1 = buffer_rsrc(out + oc, ((g.h - 1) * oh + g.w) * 4);
+    const __amdgpu_buffer_rsrc_t rcn = buffer_rsrc(count, ((g.h - 1) * ch + g.w) * 4);
 #pragma unroll
     for (int it = 0; it < PROJ_EPI_ITERS; ++it) {
         const int yl = it * 4 * PROJ_NW + wave * 4 + rw, y = oy0 + yl;
@@ -1011,9 +1011,9 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     const ProjImage im = proj_image(b, src.per);
     float* const out = dst.out[im.item] + (int64_t)im.bi * ob;
     float* const count = dst.count[im.item] + (int64_t)im.bi * cb;
-    const __amdgpu_buffer_rsrc_t ro0 = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, ((g.h - 1) * oh + g.w) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro1 = __builtin_amdgcn_make_buffer_rsrc((void*)(out + oc), 0, ((g.h - 1) * oh + g.w) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rcn = __builtin_amdgcn_make_buffer_rsrc((void*)count, 0, ((g.h - 1) * ch + g.w) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro0 = buffer_rsrc(out, ((g.h - 1) * oh + g.w) * 4);
+    const __amdgpu_buffer_rsrc_t ro1 = buffer_rsrc(out + oc, ((g.h - 1) * oh + g.w) * 4);
+    const __amdgpu_buffer_rsrc_t rcn = buffer_rsrc(count, ((g.h - 1) * ch + g.w) * 4);
 
     // the 2x2 sums of one pass for the lane's four cells: lo / hi halves of the value cells; count cells: clo = weight sum
     // (depth), chi = addends

@@ -59,6 +59,15 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 }
 #undef VFI_DPP_STEP
 
+// Word 3 of a raw buffer descriptor: DATA_FORMAT (bits 15-18) = 32 bits, no swizzle, no index stride.  Offsets at or past
+// num_records bytes load 0 and drop stores without touching memory.
+constexpr int BUF_RAW_FLAGS = 0x00020000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, BUF_RAW_FLAGS);
+}
+// LDS destination of an LDS-DMA load (__builtin_amdgcn_raw_ptr_buffer_load_lds)
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
 inline dim3 pixel_grid(int w, int h, int batch) {
     return dim3((unsigned)((w + VFI_TX - 1) / VFI_TX), (unsigned)((h + VFI_TY - 1) / VFI_TY), (unsigned)batch);
 }
