@@ -2,6 +2,7 @@
 """bench.py -- throughput of the frame-synthesis hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (starts its own N ranks when N > 1)
+    python bench.py --gpus N --steps K --warmup W --full     (and every side measurement after the headline)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workloads
@@ -26,7 +27,14 @@ work) are outside this repo's scope and are NOT part of a step -- `value` is hot
 All inputs are synthetic (vfidkr_amd/synthetic.py), float32, resident in HBM before timing.  Ranks share nothing:
 the only communication is the timing join (barrier, MAX of wall time, SUM of frames) over gloo.
 
-Every native call goes through the C ABI of libvfi_hip.so (ctypes, vfidkr_amd/cabi.py).  The JSON line also carries
+Every native call goes through the C ABI of libvfi_hip.so (ctypes, vfidkr_amd/cabi.py).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line: the headline and what the
+timed region itself recorded (`roofline`, `dump_outputs`).  Whatever takes runs of its own -- every other block below, and
+`fp16_storage`, `correlation`, `shared_window`, `two_streams`, `parity`, vimeo64's `four_branches` -- is measured with
+--full only (where --no-extras and --no-cpu-baseline leave parts of it out).
+
+The JSON line also carries
   roofline          dominant kernel (FilterInterpolation, C=196): algorithmic bytes per launch (1640 B/pixel,
                     SURVEY 8d) / mean launch time from HIP events on the launch stream INSIDE the timed region
                     (each launch streams 3.6 GB: nothing of it is cache resident), vs 8 TB/s.  `traffic` = HBM
@@ -76,8 +84,11 @@ def parse(argv=None):
                     help="synthetic flow field of the timed step (vfidkr_amd/synthetic.py); 'quarter' = SURVEY 8d to the letter")
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (no gate / quarter / fp16 measurements)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every side measurement as well: value_spread, the gate / quarter / fp16 / schedule "
+                         "blocks, the CPU baseline and parity (slowmo1080), four_branches (vimeo64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / parity")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no gate / quarter / fp16 / schedule measurements")
     ap.add_argument("--direct", action="store_true", help="force the direct-gather FilterInterpolation kernel")
     ap.add_argument("--storage", choices=("f32", "f16"), default="f32",
                     help="slowmo1080: f16 = BASELINE.json configs[2], frames / context / correlation features and their "
@@ -309,7 +320,7 @@ def run_vimeo64(args, torch, cabi, runner, S, dev, rank, world):
             outs.update({"b%02d_warp_d0" % j: p.out[0], "b%02d_warp_d1" % j: p.out[1], "b%02d_proj_d1" % j: p.proj,
                          "b%02d_count_d1" % j: p.count})
         extra["dump_outputs"] = dump_outputs(args.dump_outputs, outs)
-    if args.streams == 1 and not args.no_extras:
+    if args.full and args.streams == 1 and not args.no_extras:
         # the same step with its independent batches dealt over four parallel branches of the graph (a schedule change, not
         # kernel work: reported beside the one-branch headline, which stays comparable from round to round)
         _, run4 = make_runner(4)
@@ -457,6 +468,8 @@ def run_slowmo(args, torch, cabi, runner, S, dev, rank, world):
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
+    if not args.full:
+        return out              # a plain run: the headline and what its timed region recorded, nothing measured after it
     # five more repetitions of the timed region (every rank takes part: the region ends in a barrier): box-to-box and
     # run-to-run spread is of the order of a kernel improvement
     reps = [elapsed] + [runner.timed_region(lambda i: run_step(i), args.steps, dev) for _ in range(4)]

@@ -64,6 +64,14 @@ def test_best_schedule_block_is_the_median_of_the_repetitions():
     assert blk["vs_value"] == round((3 / 5.5e-3) / 400.0, 3)
 
 
+def test_side_measurements_wait_for_full():
+    """A plain run times the headline alone; --full adds the side measurements, --no-extras / --no-cpu-baseline trim them."""
+    import bench
+    plain, full = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]), bench.parse(["--full", "--no-extras"])
+    assert not plain.full and not plain.no_extras and not plain.no_cpu_baseline
+    assert full.full and full.no_extras and not full.no_cpu_baseline
+
+
 def test_dump_outputs_budget_and_fixed_sample(tmp_path):
     """bench.py --dump-outputs: float32 files, whole arrays where they fit their share of the budget, a seeded sample of the
     rest, never more than the budget in all, and the same files from the same inputs."""
