@@ -127,6 +127,14 @@ def flowproj_fwd(flow, fillhole=1):
     return out, count
 
 
+def proj_fillhole(count, out):
+    """The projections' pass 3 alone (hole filling) on a copy of out, given count."""
+    count, out = _f32(count).copy(), _f32(out).copy()
+    B, _, H, W = out.shape
+    _check(lib().vfi_oracle_proj_fillhole(_p(count), _p(out), B, H, W), "proj_fillhole")
+    return out
+
+
 def flowproj_bwd(flow, count, gout):
     flow, count, gout = _f32(flow), _f32(count), _f32(gout)
     B, _, H, W = flow.shape

@@ -510,6 +510,13 @@ static int project(const float* flow, const float* depth, float* count, float* o
     return 0;
 }
 
+/* pass 3 alone, in place on (count, out): lets a test fill the holes of a projection computed elsewhere */
+int vfi_oracle_proj_fillhole(float* count, float* out, int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 1;
+    fillhole_pass(count, out, B, H, W);
+    return 0;
+}
+
 int vfi_oracle_flowproj_fwd(const float* flow, float* count, float* out,
                             int B, int H, int W, int fillhole) {
     return project(flow, NULL, count, out, B, H, W, fillhole);

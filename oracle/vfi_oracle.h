@@ -58,6 +58,7 @@ int vfi_oracle_filterinterp_defor_bwd(int variant, const float* img, const float
                                       int B, int C, int H, int W, int fs, int fmad);
 
 /* A3  flowprojection_cuda_kernel.cu:29-235 ; count/out must arrive zero-filled */
+int vfi_oracle_proj_fillhole(float* count, float* out, int B, int H, int W);
 int vfi_oracle_flowproj_fwd(const float* flow, float* count, float* out,
                             int B, int H, int W, int fillhole);
 /* A3b flowprojection_cuda_kernel.cu:237-301 */

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Soak: FlowProjection / DepthFlowProjection (pull kernels, fallback included) against the CPU oracle on many random
-frames.  Dyadic inputs (multiples of 1/8, weights multiples of 1/16): every sum is exact in any order, so count and flow
-must equal the oracle's bit for bit; non-dyadic inputs: within 1e-4 and identical from run to run.
+frames.  Dyadic inputs (multiples of 1/8, weights multiples of 1/16): every sum is exact in any order while it fits
+fp32, so count and flow must equal the oracle's bit for bit -- or, where a converging field's sums outgrow fp32 and the
+oracle's own sum rounds, the host mirror's (tests/proj_tiles.py) exact restatement; non-dyadic inputs: within 1e-4 and
+identical from run to run.
     python tests/soak_projection.py [cases] [seed]        (not collected by pytest; the oracle is the checker, so it lives under tests/)
     --lib <path> picks a development build of the library
 """
@@ -19,6 +21,7 @@ if "--lib" in sys.argv:         # a development build of the library (tools/mkva
     del sys.argv[_i:_i + 2]
 from vfidkr_amd import cabi  # noqa: E402
 from oracle import cpu_oracle as oracle  # noqa: E402  (test infrastructure: the checker)
+from tests import proj_tiles as pt  # noqa: E402
 oracle.build()
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
@@ -40,7 +43,8 @@ for it in range(cases):
     elif kind == "wild":
         flow = rng.uniform(-W / 2, W / 2, (B, 2, H, W))
     elif kind == "converge":                            # everything lands near one point: busy cells (the rescaling pass)
-        flow = np.stack([(W // 2 - xs) * 0.9, (H // 2 - ys) * 0.9])[None].repeat(B, 0)
+        k = rng.choice([0.9, 0.95, 0.99])               # 0.95 / 0.99: hundreds to thousands per top-left grid cell
+        flow = np.stack([(W // 2 - xs) * k, (H // 2 - ys) * k])[None].repeat(B, 0)
     else:
         flow = np.zeros((B, 2, H, W))
     dyadic = rng.random() < 0.7
@@ -63,6 +67,13 @@ for it in range(cases):
             c, o = count.cpu().numpy(), out.cpu().numpy()
             if dyadic:
                 good = np.array_equal(c, rc) and np.array_equal(o, r)
+                if not good and kind != "wild":
+                    # a cell of thousands of addends (converging fields) outgrows fp32: the oracle's sequential sum rounds,
+                    # the kernels' fixed-point sum does not -- the host mirror restates it bit for bit
+                    pr, pc = pt.mirror(flow, wgt if depth else None, "lean").predict()
+                    if fh:
+                        pr = oracle.proj_fillhole(pc, pr)
+                    good = np.array_equal(c, pc) and np.array_equal(o, pr)
             else:
                 g1 = bool(np.all(np.abs(c - rc) <= 1e-4 * np.maximum(1.0, np.abs(rc))))
                 # fixed-point sums per weight class leave a cell's flow within 2^(e - 19) of the exact sum, 2^e

@@ -1,0 +1,172 @@
+"""CPU checks of tests/proj_tiles.py, the host mirror of the projection kernels' per-tile decisions: its constants and
+dispatch chain are the sources', hand-worked records and regimes hold, the fields it builds send every label through a
+tile, every contributor lies in its tile's rectangle, and its FlowProjection restatement equals the oracle bit for bit on
+dyadic fields and stays within the stated bound on random ones (the GPU file is tests/test_gpu_proj_tiles.py)."""
+import re
+
+import numpy as np
+import pytest
+
+from tests import proj_tiles as pt
+from tests.fi_windows import source
+
+f32 = np.float32
+
+
+def test_constants_match_the_source():
+    text = source(pt.SOURCE)
+    for name, value in (("PROJ_TW", pt.TW), ("PROJ_TH", pt.TH), ("PROJ_BLK", pt.BLK), ("PROJ_ADD_BITS", pt.ADD_BITS),
+                        ("PROJ_ADD_CELL", pt.ADD_CELL), ("PROJ_CLS_BITS", pt.CLS_BITS), ("PROJ_BLOCK_CAP", pt.BLOCK_CAP),
+                        ("PROJ_NMAX", pt.NMAX), ("PROJ_INV_BITS", pt.INV_BITS)):
+        m = re.search(r"^\s*#define\s+%s\s+(\S+)" % name, text, flags=re.M)
+        assert m and int(m.group(1), 0) == value, name
+    # the constants the mirror states itself
+    assert text.count("min(4, max(0, emax - emin) / PROJ_CLS_BITS + 1)") == 2
+    assert text.count("max(-100, min(100, PROJ_ADD_BITS - (") == 6
+    assert text.count("(32 - __clz(nmax - 1)) - 5") == 1 and text.count("(32 - __clz(busiest - 1)) - 5") == 1
+    assert 2 ** 5 == pt.ADD_CELL
+
+
+def test_dispatch_chain_matches_project_forward_list():
+    text = " ".join(source(pt.SOURCE).split())
+    body = text[text.index("static int project_forward_list("):text.index("static int project_forward_items(")]
+    assert "bool vec_in = sf.b % 4 == 0 && sf.c % 4 == 0 && sf.h % 4 == 0 && (!DEPTH || (s2.b % 4 == 0 && s2.h % 4 == 0));" in body
+    assert "bool vec_out = s1.b % 4 == 0 && s1.c % 4 == 0 && s1.h % 4 == 0 && sc.b % 4 == 0 && sc.h % 4 == 0;" in body
+    assert "vec_in = vec_in && (uintptr_t)flows[k] % 16 == 0 && (!DEPTH || (uintptr_t)depths[k] % 16 == 0);" in body
+    assert "vec_out = vec_out && (uintptr_t)outs[k] % 16 == 0 && (uintptr_t)counts[k] % 16 == 0;" in body
+    launches = re.findall(r"(if \(vec_in[^)]*\)|else if \(vec_in\)|else) hipLaunchKernelGGL\(\(?(\w+)(<[^>]*>)?", body)
+    assert "if (vec_in) { const int groups_x = (g.tiles_x + 3) / 4; hipLaunchKernelGGL((proj_scan4<DEPTH>)" in body
+    assert "} else { hipLaunchKernelGGL((proj_scan<DEPTH>)" in body
+    assert launches == [("if (vec_in && vec_ok && g.tiles_y <= 65535 && images <= 65535)", "proj_pull_lean", "<DEPTH>"),
+                        ("else if (vec_in)", "proj_pull", "<DEPTH, true>"), ("else", "proj_pull", "<DEPTH, false>")]
+    # the bindings pass the flow's strides for the outputs
+    assert "project_forward<false>(input1, s1, nullptr, count, output, batch, h, w, fillhole, s1, s1, sc," in text
+    # the mirror's statement of the same chain
+    D = pt.dispatch
+    assert D(False, (2 * 64 * 80, 64 * 80, 80), (64 * 80, 80)) == ("scan4", "lean")
+    assert D(False, (2 * 64 * 80, 64 * 80, 80), (64 * 80, 80), ptr_mod16=(0, 0, 4, 0)) == ("scan4", "pull_vec")
+    assert D(False, (2 * 64 * 81, 64 * 81, 81), (64 * 80, 80)) == ("scan", "pull_scalar")
+    assert D(True, (2 * 64 * 80, 64 * 80, 80), (64 * 80, 80), (64 * 81, 81)) == ("scan", "pull_scalar")
+    assert D(False, (2 * 64 * 80, 64 * 80, 80), (64 * 80, 80), images=65536) == ("scan4", "pull_vec")
+
+
+def test_k1_scale_and_retry_statements_match_the_sources():
+    text = " ".join(source(pt.SOURCE).split())
+    # proj_pull: per class, retried once; proj_pull_lean: one shift for all classes, bias scaled with it
+    assert "kvx -= shift; kvy -= shift; kc -= shift;" in text
+    assert "const int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls))) - shift;" in text
+    assert "const int bias_bits = max(PROJ_ADD_BITS - shift, 0);" in text
+    assert "const int Y = (int)(vlo[j] - ((unsigned)n << bias_bits));" in text
+    assert "PL_BIAS" not in text
+
+
+def test_hand_worked_records():
+    h, w = 64, 256
+    # a constant shift of (+3, +2): every block reaches its own tiles and the ones 3 px right / 2 px down
+    flow = np.zeros((1, 2, h, w), f32)
+    flow[0, 0], flow[0, 1] = 3.0, 2.0
+    rec, wild = pt.records(flow, None, h, w)
+    assert not wild
+    ux0, uy0, uw, uh = pt.rectangle(rec[0])
+    # tile (1, 1): L in [63, 127], T in [15, 31] -> x in [60, 124], y in [13, 29]
+    assert (ux0[1, 1], uy0[1, 1], uw[1, 1], uh[1, 1]) == (60, 13, 65, 17)
+    assert (ux0[0, 0], uy0[0, 0], uw[0, 0], uh[0, 0]) == (0, 0, 61, 14)
+    assert rec[0, 0, 0, 4] == np.float32(3.0).view(np.int32) and rec[0, 0, 0, 7] == np.float32(2.0).view(np.int32)
+    # one block scattered over 65 tiles: the fallback
+    flow = np.zeros((1, 2, 16 * 13, 64 * 5), f32)
+    ys, xs = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+    flow[0, 0, :16, :16] = (xs % 5) * 64 - xs
+    flow[0, 1, :16, :16] = (ys % 13) * 16 - ys
+    assert pt.records(flow, None, 16 * 13, 64 * 5)[1]
+    flow[0, 1, :16, :16] = (ys % 12) * 16 - ys                  # 5 x 12 = 60 tiles: no fallback
+    assert not pt.records(flow, None, 16 * 13, 64 * 5)[1]
+
+
+def test_hand_worked_regimes():
+    h, w = 32, 128
+    flow = np.full((1, 2, h, w), 0.5, f32)
+    depth = np.full((1, 1, h, w), 0.75, f32)
+    depth[0, 0, 20, 70] = 0.75 * 2.0 ** -7                    # a weight 7 binary orders down: two classes
+    m = pt.mirror(flow, depth, "lean")
+    lab = m.labels()
+    assert "classes_2" in lab[(0, 1, 1)] and "plain" not in lab[(0, 1, 1)]
+    assert lab[(0, 0, 0)] == {"plain"}
+    kvx, kvy, kc, shift = pt.scales(flow, depth, "lean")
+    # max |fx| = 0.5 -> |fx| < 2^0; max weight 0.75 -> 2^0: kvx = 25 - 0 + 6 cls, kc = 25 + 6 cls
+    assert list(kvx[0, 1, 1, :2]) == [25, 31] and list(kc[0, 1, 1, :2]) == [25, 31] and not shift.any()
+    # 40 sources on one top-left cell (15, 50) beside the still field's own four per cell: 44 > 32 addends, once more
+    # 1 bit coarser, in both tiles whose grids hold row 15
+    flow2 = np.zeros((1, 2, h, w), f32)
+    flow2[0, 0, 10, :40] = 50 - np.arange(40, dtype=f32)
+    flow2[0, 1, 10, :40] = 5
+    m = pt.mirror(flow2, None, "lean")
+    assert list(m.busy[:, 0]) == [44, 6, 44, 9] and list(m.shift[:, 0]) == [1, 0, 1, 0]
+    assert "retry_1" in m.labels()[(0, 0, 0)] and "retry_1" in m.labels()[(0, 1, 0)]
+    out, cnt = m.predict()
+    assert cnt[0, 0, 15, 50] == 44 and cnt[0, 0, 16, 51] == 44
+
+
+@pytest.mark.parametrize("kind", ["flow", "depth"])
+@pytest.mark.parametrize("k1", ["lean", "pull_vec"])
+@pytest.mark.parametrize("dyadic", [False, True])
+def test_fields_cover_every_label(kind, k1, dyadic):
+    flow, depth = pt.build_field(kind, np.random.default_rng(5), 1, dyadic=dyadic)
+    m = pt.mirror(flow, depth, k1)
+    assert not m.fallback
+    assert pt.covered(m.labels()) >= set(pt.all_regimes(kind)), set(pt.all_regimes(kind)) - pt.covered(m.labels())
+    assert m.contributors_inside().all()
+    # the converging sites reach the shifts they were placed for
+    for n, ty, tx in pt.SITES:
+        assert m.grid_max.reshape(m.tyn, m.txn)[ty, tx] >= n
+
+
+def test_contributors_inside_rectangles_on_random_fields():
+    rng = np.random.default_rng(11)
+    for (h, w, amp) in ((40, 130, 3.0), (70, 200, 20.0), (33, 64, 0.5)):
+        flow = rng.uniform(-amp, amp, (2, 2, h, w)).astype(f32)
+        m = pt.mirror(flow, None, "lean")
+        assert not m.fallback and m.contributors_inside().all()
+
+
+@pytest.mark.parametrize("k1", ["lean", "pull_vec"])
+def test_predict_flowprojection_equals_oracle_on_dyadic_fields(oracle, k1):
+    flow, _ = pt.build_field("flow", np.random.default_rng(2), 2, dyadic=True)
+    out, cnt = pt.predict_flowprojection(flow, k1)
+    ref, rcount = oracle.flowproj_fwd(flow, 0)
+    assert np.array_equal(cnt, rcount) and np.array_equal(out, ref)
+
+
+@pytest.mark.parametrize("k1", ["lean", "pull_vec"])
+def test_predict_depthflowprojection_equals_oracle_on_dyadic_fields(oracle, k1):
+    flow, depth = pt.build_field("depth", np.random.default_rng(3), 1, dyadic=True)
+    out, cnt = pt.predict_depthflowprojection(flow, depth, k1)
+    ref, rcount = oracle.depthflowproj_fwd(flow, depth, 0)
+    assert np.array_equal(cnt, rcount) and np.array_equal(out, ref)
+
+
+def test_predict_flowprojection_within_bound_on_random_fields():
+    flow, _ = pt.build_field("flow", np.random.default_rng(4), 1)
+    m = pt.mirror(flow, None, "lean")
+    out, cnt = m.predict()
+    err, bound = flow_errors(m, flow, out)
+    assert np.all(err <= bound), (err - bound).max()
+
+
+def flow_errors(m, flow, out):
+    """|out - (-sum fx / n)| and its bound 2^-(kx+1) + 2^-23 |want| per cell (float64 sums of the fp32 addends)."""
+    B, _, h, w = flow.shape
+    sums = np.zeros((B, 2, h * w))
+    n = np.zeros((B, h * w))
+    for b in range(B):
+        valid, L, T = pt.targets(flow[b, 0], flow[b, 1], h, w)
+        R, Bm = np.minimum(L + 1, w - 1), np.minimum(T + 1, h - 1)
+        for ty, tx in ((T, L), (T, R), (Bm, L), (Bm, R)):
+            idx = (ty * w + tx)[valid]
+            for c in range(2):
+                np.add.at(sums[b, c], idx, -flow[b, c][valid].astype(np.float64))
+            np.add.at(n[b], idx, 1)
+    n = n.reshape(B, 1, h, w)
+    want = np.where(n > 0, sums.reshape(B, 2, h, w) / np.maximum(n, 1), 0)
+    kx = np.stack([m.tile_plane(m.kvx[:, 0]), m.tile_plane(m.kvy[:, 0])], 1)
+    bound = np.exp2(-(kx + 1.0)) + 2.0 ** -23 * np.abs(want)
+    return np.abs(out.astype(np.float64) - want), bound

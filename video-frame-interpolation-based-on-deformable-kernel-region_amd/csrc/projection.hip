@@ -886,8 +886,8 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
 //    and an in-frame pixel outside the rectangle cannot reach the tile (K0's rectangle holds every pixel that can);
 //  * grid cell address = (T * pitch + L) * 8 + one uniform constant; the count plane has the value plane's 8-byte
 //    pitch, so its address is the same register + an immediate;
-//  * the y half of a value addend is biased by 2^25 (non-negative: the 64-bit add never borrows from the x half; the
-//    epilogue subtracts count * 2^25), which saves the sign fix-up per pixel and the packed-half recovery per cell;
+//  * the y half of a value addend is biased by 2^(25 - shift) (non-negative: the 64-bit add never borrows from the x half;
+//    the epilogue subtracts count * 2^(25 - shift)), which saves the sign fix-up per pixel and the packed-half recovery per cell;
 //  * the 2x2 sums of a lane's four cells share their five column sums; the frame's last row / column (R == L, B == T:
 //    the reference adds twice) is fixed up in the tiles that touch them only;
 //  * FlowProjection divides by an integer count <= 32 times a power of two: the reciprocal is rcp + one Newton step
@@ -913,7 +913,6 @@ template <bool DEPTH> struct PlLds {
     static constexpr int total = planes + PROJ_TH * 8 + 16;                    // + row bitmaps + four counters
 };
 static_assert(PlLds<false>::total <= 17920, "nine workgroups per CU");
-#define PL_BIAS (1 << PROJ_ADD_BITS)
 #ifndef PL_THREADS
 #define PL_THREADS 128
 #endif
@@ -1061,7 +1060,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     };
 
     // one weight class into the grid: every source pixel of the rectangle, once, at its top-left target
-    auto accumulate = [&](int cls, int kvx, int kvy, int kc) {
+    auto accumulate = [&](int cls, int kvx, int kvy, int kc, unsigned bias) {
         constexpr int CH = PL_CH;
         const float svx = -ldexpf(1.0f, kvx), svy = -ldexpf(1.0f, kvy), scn = ldexpf(1.0f, kc);    // exact powers of two (the value addend is MINUS the flow)
         const int ux0a = ux0 & ~3;                                          // quads start at multiples of four pixels
@@ -1114,10 +1113,10 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                                 const int L = (int)x2, T = (int)y2;
                                 const unsigned a = (unsigned)(__mul24(T, P) + L) * 8u + cell0;
                                 const float ax = DEPTH ? d * fx : fx, ay = DEPTH ? d * fy : fy;  // (:75-88; depth :74-91)
-                                const unsigned X = (unsigned)__float2int_rn(ax * svx), Y = (unsigned)(__float2int_rn(ay * svy) + PL_BIAS);
+                                const unsigned X = (unsigned)__float2int_rn(ax * svx), Y = (unsigned)__float2int_rn(ay * svy) + bias;
                                 __hip_atomic_fetch_add((pl_lds64_t)a, ((unsigned long long)X << 32) | Y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                 if constexpr (DEPTH) {
-                                    const unsigned Wc = (unsigned)(__float2int_rn(d * scn) + PL_BIAS);
+                                    const unsigned Wc = (unsigned)__float2int_rn(d * scn) + bias;
                                     __hip_atomic_fetch_add((pl_lds64_t)(a + (cellc - cell0)), (1ull << 32) | Wc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                 } else {
                                     const unsigned ac = (unsigned)(__mul24(T, PC) + L) * 4u + cellc;
@@ -1134,6 +1133,12 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
 
     int shift = 0;                                          // coarser scale of the second try
     for (int attempt = 0;; ++attempt) {
+        // The bias shrinks with the addends: a pass keeps at most 2^(shift + 5) addends per cell, each biased below
+        // 2^(26 - shift), so no low half reaches 2^31 and none carries into the high half.  (A bias of 2^25 on the second
+        // pass carried from 128 addends per grid cell on: x sums off by units of 2^-kvx, and with depth the addend count,
+        // hence the weight and y sums, off by the carries.)  Past shift 25 every addend rounds to 0: bias 1.
+        const int bias_bits = max(PROJ_ADD_BITS - shift, 0);
+        const unsigned bias = 1u << bias_bits;
         float resx[PL_EPI][4], resy[PL_EPI][4], resc[PL_EPI][4];
         int nres[PL_EPI][4];
         int nmax = 0;
@@ -1147,7 +1152,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
             const int kc = max(-100, min(100, PROJ_ADD_BITS - (ec - PROJ_CLS_BITS * cls))) - shift;
             const int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls))) - shift;
             const int kvy = max(-100, min(100, PROJ_ADD_BITS - (efy + ec - PROJ_CLS_BITS * cls))) - shift;
-            accumulate(cls, kvx, kvy, kc);
+            accumulate(cls, kvx, kvy, kc, bias);
             __syncthreads();
 #pragma unroll
             for (int it = 0; it < PL_EPI; ++it) {
@@ -1158,11 +1163,11 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                 for (int j = 0; j < 4; ++j) {
                     const int n = chi[j];                       // addends of the cell (cells outside the frame: none)
                     nmax = max(nmax, n);
-                    const int Y = (int)(vlo[j] - ((unsigned)n << PROJ_ADD_BITS));
+                    const int Y = (int)(vlo[j] - ((unsigned)n << bias_bits));
                     // exact integer sums -> float once per class (a power-of-two scale: exact)
                     const float px_ = ldexpf((float)vhi[j], -kvx), py_ = ldexpf((float)Y, -kvy);
                     float pc_;
-                    if constexpr (DEPTH) pc_ = ldexpf((float)(int)(clo[j] - ((unsigned)n << PROJ_ADD_BITS)), -kc);
+                    if constexpr (DEPTH) pc_ = ldexpf((float)(int)(clo[j] - ((unsigned)n << bias_bits)), -kc);
                     else pc_ = 0.0f;
                     if (cls == 0) { resx[it][j] = px_; resy[it][j] = py_; resc[it][j] = pc_; nres[it][j] = n; }
                     else { resx[it][j] += px_; resy[it][j] += py_; resc[it][j] += pc_; nres[it][j] += n; }
@@ -1229,7 +1234,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
         if (busiest <= PROJ_ADD_CELL || attempt) break;
         // a cell took more addends than fit beside it: everything once more, with addends small enough for the busiest cell
         // (this thread's stores are overwritten in program order)
-        shift = (32 - __clz(busiest - 1)) - 5;                  // ceil(log2(busiest)) - log2(32)
+        shift = __builtin_amdgcn_readfirstlane((32 - __clz(busiest - 1)) - 5);    // ceil(log2(busiest)) - log2(32)
         __syncthreads();                                        // every thread has read the counter
         for (int i = tid; i < LY::total / 16; i += PL_THREADS) lds[i] = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
