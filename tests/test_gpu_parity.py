@@ -302,6 +302,9 @@ def test_deformable_backward_staged_and_flagged_blocks(torch_mod, cabi, oracle, 
     assert err == 0
     r1, r2, r3, r4 = oracle.filterinterp_defor_bwd(variant, img, flow, filt, off, gout, fmad=1)
     assert np.abs(cpu(g1) - (s1 + r1)).max() <= GRAD_TOL * max(1.0, np.abs(r1).max())
+    if fs == 4:     # ... and bit for bit the exact integer sums (tests/bwd_tiles.py), added into s1
+        from tests import bwd_tiles
+        assert np.array_equal(cpu(g1), bwd_tiles.predict_image_grad("defor", flow, gout, s1, filt, off, variant)[0])
     assert np.array_equal(cpu(g2), r2)
     assert np.array_equal(cpu(go), r4)
     if variant != 2:
@@ -666,6 +669,8 @@ def test_filterinterp_backward_staged_and_flagged_tiles(torch_mod, cabi, oracle)
     assert cabi.filterinterp_backward_ori(gpu(torch, img), gpu(torch, flow), gpu(torch, filt), gpu(torch, gout), g1, g2, g3) == 0
     r1, r2, r3 = oracle.filterinterp_ori_bwd(img, flow, filt, gout, fmad=1)
     assert np.abs(cpu(g1) - (s1 + r1)).max() <= GRAD_TOL * max(1.0, np.abs(r1).max())
+    from tests import bwd_tiles     # ... and bit for bit the exact integer sums, added into s1
+    assert np.array_equal(cpu(g1), bwd_tiles.predict_image_grad("ori", flow, gout, s1, filt)[0])
     assert np.array_equal(cpu(g2), r2)
     # filter gradient: the kernel sums the channels in order starting from the cell's value, as the reference's += does
     want3 = s3.copy()
@@ -782,6 +787,8 @@ def test_interpolation_backward_staged_and_flagged_tiles(torch_mod, cabi, oracle
     assert cabi.interpolation_backward(gpu(torch, img), gpu(torch, flow), gpu(torch, gout), g1, g2) == 0
     r1, r2 = oracle.interp_bwd(img, flow, gout, fmad=1)
     assert np.abs(cpu(g1) - (s1 + r1)).max() <= GRAD_TOL * max(1.0, np.abs(r1).max())
+    from tests import bwd_tiles     # ... and bit for bit the exact integer sums, added into s1
+    assert np.array_equal(cpu(g1), bwd_tiles.predict_image_grad("interp", flow, gout, s1)[0])
     assert np.array_equal(cpu(g2), r2)
     h1 = gpu(torch, s1)
     assert cabi.interpolation_backward(gpu(torch, img), gpu(torch, flow), gpu(torch, gout), h1, torch.zeros_like(g2)) == 0
