@@ -323,6 +323,49 @@ int vfi_depthflowprojection_forward_up4(const float* flow_q, const float* input2
                                         vfi_strides sq, vfi_strides s2, vfi_strides sc, vfi_strides so,
                                         vfi_stream_t stream);
 
+/* ---- training through the quarter-resolution flow: the backwards of the three entry points above, each for a LIST
+ * of 1 <= nitems <= 8 time offsets of ONE quarter-resolution tensor (the gradients of all of them land on it).
+ * Table arguments (`[]` below) are HOST arrays of nitems device pointers, mul1 a HOST array of nitems floats; items
+ * share shape and strides.  grad_q is WRITTEN, every element once: no zero fill, no accumulation, no atomics, so the
+ * results are reproducible bit for bit.  Nothing is allocated: the calls can be captured in a graph (the tables travel
+ * by value in the kernel arguments).  Null pointers, nitems outside 1..8, sizes or strides beyond 32-bit in-plane
+ * offsets: VFI_ERR_SHAPE before any launch.
+ *
+ * vfi_flow_upsample4_backward: grad_q[B,C,hq,wq] = sum_i m_i * U^T grad_full[i], U the x4 bilinear upsample of
+ * vfi_flow_upsample4, m_i = mul0 * mul1[i] (one fp32 product).  A quarter pixel q of an axis collects from the
+ * full-resolution pixels d = 4q-2 .. 4q+5 cut to the image, with weight (i0 == q ? l0 : 0) + (i1 == q ? l1 : 0) of d's
+ * two taps.  Per item: rows ascending, inside a row columns ascending, r = fmaf(wx, G, r), then s = fmaf(wy, r, s);
+ * items in order, acc = fmaf(m_i, s_i, acc) (csrc/flow_up4.h: up4_adjoint).  grad_full[i]: [B,C,4hq,4wq], strides sg. */
+int vfi_flow_upsample4_backward(const float* const* grad_full, const float* mul1, int nitems,
+                                float* grad_q,
+                                int batch, int channels, int hq, int wq, float mul0,
+                                vfi_strides sg, vfi_strides sq,
+                                vfi_stream_t stream);
+/* Backward of vfi_flowprojection_forward_up4 for item i = (mul0, mul1[i]): counts[i] [B,1,4hq,4wq] is what that
+ * forward wrote, gradoutputs[i] [B,2,4hq,4wq] the gradient of its output.  grad_q [B,2,hq,wq] equals, bit for bit,
+ * vfi_flow_upsample4 -> vfi_flowprojection_backward into a zero-filled gradient (per item) ->
+ * vfi_flow_upsample4_backward; the full-resolution flow and its gradient exist per tile in LDS only.  fillhole plays
+ * no part, as in vfi_flowprojection_backward.  sq: flow_q, sc: counts, so: gradoutputs, sgq: grad_q. */
+int vfi_flowprojection_backward_up4(const float* flow_q, const float* const* counts,
+                                    const float* const* gradoutputs, const float* mul1, int nitems,
+                                    float* grad_q,
+                                    int batch, int hq, int wq, float mul0,
+                                    vfi_strides sq, vfi_strides sc, vfi_strides so, vfi_strides sgq,
+                                    vfi_stream_t stream);
+/* The same for vfi_depthflowprojection_forward_up4: depths[i] (items may share one) and the forward's outputs[i] are
+ * needed as in vfi_depthflowprojection_backward.  grad_depths (the table, or any entry) may be NULL = not wanted;
+ * a given grad_depths[i] [B,1,4hq,4wq] is WRITTEN in full with item i's depth gradient, equal bit for bit to what
+ * vfi_depthflowprojection_backward adds into zeros (a caller whose items share a depth sums them).  s2: depths and
+ * grad_depths, so: outputs and gradoutputs. */
+int vfi_depthflowprojection_backward_up4(const float* flow_q, const float* const* depths,
+                                         const float* const* counts, const float* const* outputs,
+                                         const float* const* gradoutputs, const float* mul1, int nitems,
+                                         float* grad_q, float* const* grad_depths,
+                                         int batch, int hq, int wq, float mul0,
+                                         vfi_strides sq, vfi_strides s2, vfi_strides sc, vfi_strides so,
+                                         vfi_strides sgq,
+                                         vfi_stream_t stream);
+
 /* FilterInterpolate (networks/DAIN_slowmotion.py:324-335, DAIN.py:560-573): out0 = A1(ref0, flow0,
  * filt0), out2 = A1(ref2, flow2, filt2), blend = out0 * w0 + out2 * w2 (products rounded
  * separately, as torch's three elementwise ops).  out0 / out2 may be NULL.  ref0/ref2, flow0/flow2

@@ -64,6 +64,10 @@ SIGNATURES = {
     "vfi_flowprojection_forward_up4": [_p, _p, _p, _i, _i, _i, _f, _f, _i, Strides, Strides, Strides, _p],
     "vfi_depthflowprojection_forward_up4": [_p, _p, _p, _p, _i, _i, _i, _f, _f, _i, Strides, Strides, Strides, Strides,
                                             _p],
+    "vfi_flow_upsample4_backward": [_p, _p, _i, _p, _i, _i, _i, _i, _f, Strides, Strides, _p],
+    "vfi_flowprojection_backward_up4": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _f, Strides, Strides, Strides, Strides, _p],
+    "vfi_depthflowprojection_backward_up4": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, Strides, Strides, Strides,
+                                             Strides, Strides, _p],
     "vfi_filterinterp_blend_forward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, Strides, Strides,
                                        Strides, Strides, _p],
     "vfi_filterinterp_blend_backward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
@@ -594,6 +598,68 @@ def depthflowprojection_forward_up4(flow_q, input2, count, output, mul0, mul1, f
         return _finish(lib().vfi_depthflowprojection_forward_up4(
             _ptr(flow_q), _ptr(input2), _ptr(count), _ptr(output), b, hq, wq, mul0, mul1, int(fillhole), _st(flow_q),
             _st(input2), _st(count), _st(output), _stream(flow_q)))
+
+
+def _ptr_table(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def flow_upsample4_backward(grads_full, mul0, mul1, grad_q):
+    """grad_q = sum_i (mul0 * mul1[i]) U^T grads_full[i] (1..8 items of one shape and layout); grad_q is written."""
+    n = len(grads_full)
+    if n == 0 or len(mul1) != n or not _nchw_ok(grad_q, *grads_full):
+        return 1
+    b, c, hq, wq = grad_q.shape
+    g0 = grads_full[0]
+    if tuple(g0.shape) != (b, c, 4 * hq, 4 * wq) or not _addressed_as(g0, *grads_full):
+        return 1
+    for g in grads_full:
+        _dev(g)
+    with torch.cuda.device(_dev(grad_q)):
+        return _finish(lib().vfi_flow_upsample4_backward(_ptr_table(grads_full), (_f * n)(*mul1), n, _ptr(grad_q), b, c, hq, wq,
+                                                         mul0, _st(g0), _st(grad_q), _stream(grad_q)))
+
+
+def flowprojection_backward_up4(flow_q, counts, gradoutputs, mul0, mul1, grad_q, depths=None, outputs=None, grad_depths=None):
+    """The backward of [depth]flowprojection_forward_up4 for the items (mul0, mul1[i]) of one flow_q.  depths (one tensor
+    per item, or one shared by all) and outputs select the depth form; grad_depths: None, or one tensor or None per item."""
+    n = len(counts)
+    if n == 0 or len(gradoutputs) != n or len(mul1) != n:
+        return 1
+    b, c, hq, wq = flow_q.shape
+    full = (b, 1, 4 * hq, 4 * wq)
+    if c != 2 or tuple(grad_q.shape) != tuple(flow_q.shape) or not _nchw_ok(flow_q, grad_q, *counts, *gradoutputs):
+        return 1
+    c0, g0 = counts[0], gradoutputs[0]
+    if tuple(c0.shape) != full or tuple(g0.shape) != (b, 2, 4 * hq, 4 * wq):
+        return 1
+    if not _addressed_as(c0, *counts) or not _addressed_as(g0, *gradoutputs):
+        return 1
+    mul = (_f * n)(*mul1)
+    if depths is None:
+        for t in (grad_q, *counts, *gradoutputs):
+            _dev(t)
+        with torch.cuda.device(_dev(flow_q)):
+            return _finish(lib().vfi_flowprojection_backward_up4(
+                _ptr(flow_q), _ptr_table(counts), _ptr_table(gradoutputs), mul, n, _ptr(grad_q), b, hq, wq, mul0, _st(flow_q),
+                _st(c0), _st(g0), _st(grad_q), _stream(flow_q)))
+    if not isinstance(depths, (list, tuple)):
+        depths = [depths] * n
+    if outputs is None or len(depths) != n or len(outputs) != n or (grad_depths is not None and len(grad_depths) != n):
+        return 1
+    d0 = depths[0]
+    if tuple(d0.shape) != full or not _addressed_as(d0, *depths) or not _addressed_as(g0, *outputs):
+        return 1
+    wanted = [t for t in (grad_depths or []) if t is not None]
+    if not _addressed_as(d0, *wanted):
+        return 1
+    for t in (grad_q, *counts, *gradoutputs, *depths, *outputs, *wanted):
+        _dev(t)
+    with torch.cuda.device(_dev(flow_q)):
+        return _finish(lib().vfi_depthflowprojection_backward_up4(
+            _ptr(flow_q), _ptr_table(depths), _ptr_table(counts), _ptr_table(outputs), _ptr_table(gradoutputs), mul, n,
+            _ptr(grad_q), None if grad_depths is None else _ptr_table(grad_depths), b, hq, wq, mul0, _st(flow_q), _st(d0),
+            _st(c0), _st(g0), _st(grad_q), _stream(flow_q)))
 
 
 def _same_strides(a, b):

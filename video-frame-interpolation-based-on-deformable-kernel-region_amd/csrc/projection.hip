@@ -50,6 +50,7 @@
 #include "vfi_common.h"
 #include "bitwalk.h"
 #include "workspace.h"
+#include "flow_up4.h"
 
 #include <limits.h>
 
@@ -122,32 +123,7 @@ __device__ __forceinline__ ProjImage proj_image(int b, int per) {
     return ProjImage{it, b - it * per};
 }
 
-// torch's upsample_bilinear2d, align_corners=False, scale factor 4 (ATen UpSampleBilinear2d):
-// source index 0.25 * (dst + 0.5) - 0.5 clamped at 0, second tap one further unless at the edge
-struct UpTap { int i0, i1; float l0, l1; };
-__device__ __forceinline__ UpTap up4_tap(int dst, int in_size) {
-    float src = 0.25f * ((float)dst + 0.5f) - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    UpTap t;
-    t.i0 = (int)src;
-    t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
-    t.l1 = src - (float)t.i0;
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
-// one channel of the upsampled (m0 * plane) * m1 from its four taps; fused as nvcc fuses ATen's expression
-__device__ __forceinline__ float up4_blend(float q00, float q01, float q10, float q11, const UpTap& ty, const UpTap& tx,
-                                           float m0, float m1) {
-    const float p00 = (m0 * q00) * m1, p01 = (m0 * q01) * m1, p10 = (m0 * q10) * m1, p11 = (m0 * q11) * m1;
-    const float t0 = fmaf(tx.l1, p01, tx.l0 * p00);
-    const float t1 = fmaf(tx.l1, p11, tx.l0 * p10);
-    return fmaf(ty.l1, t1, ty.l0 * t0);
-}
-__device__ __forceinline__ float up4_sample(const float* __restrict__ plane, int64_t hs, const UpTap& ty, const UpTap& tx,
-                                            float m0, float m1) {
-    return up4_blend(plane[(int64_t)ty.i0 * hs + tx.i0], plane[(int64_t)ty.i0 * hs + tx.i1],
-                     plane[(int64_t)ty.i1 * hs + tx.i0], plane[(int64_t)ty.i1 * hs + tx.i1], ty, tx, m0, m1);
-}
+// (up4_tap / up4_blend / up4_sample, torch's x4 bilinear upsample of the quarter-resolution flow: flow_up4.h)
 
 // A source pixel's raw values: pix_load only issues loads, so that a caller can have the loads of many pixels in flight
 // before it works on the first.

@@ -7,8 +7,10 @@ the flow network: the backward is vfi_pwc_warp_backward, and for `warp_corr` als
 the flow and filter networks (networks/DAIN.py:215-238): the projection's backward is the reference's per-item kernel,
 the blend's is vfi_filterinterp_blend_backward (both directions, the blend weights folded in, no image gradient unless
 a frame requires grad).  Each takes its autograd Function only when grad mode is on and an input requires grad; otherwise
-it is the plain forward launch, with no grad_fn.  The rest (`FlowProject_from_quarter`, `forward_flownets_upsample`,
-`FilterInterpolate_ctx_all`, the frame glue) is inference only."""
+it is the plain forward launch, with no grad_fn.  `forward_flownets_upsample` and `FlowProject_from_quarter` are
+differentiable in the same way, so the loss reaches the quarter-resolution flow of the flow network: one backward call of
+the library for all time offsets (vfi_flow_upsample4_backward, vfi_[depth]flowprojection_backward_up4).  The rest
+(`FilterInterpolate_ctx_all`, the frame glue) is inference only."""
 import math
 
 import torch
@@ -69,8 +71,10 @@ class DirectionStreams:
             self._forked = False
 
 
-def forward_flownets_upsample(flow_q, div_flow, time_offsets):
-    """`forward_flownets` after the flow network: [div_flow * flow * t upsampled x4 for t in time_offsets]."""
+UP4_ITEMS = 8       # items per backward call of the library (PROJ_NMAX)
+
+
+def _flow_upsample_launch(flow_q, div_flow, time_offsets):
     b, c, hq, wq = flow_q.shape
     outs = []
     for t in time_offsets:
@@ -78,6 +82,51 @@ def forward_flownets_upsample(flow_q, div_flow, time_offsets):
         _check(cabi.flow_upsample4(flow_q, out, float(div_flow), float(t)), "flow_upsample4")
         outs.append(out)
     return outs
+
+
+def _add_in_order(parts):
+    total = parts[0]
+    for p in parts[1:]:
+        total = total + p
+    return total
+
+
+class _FlowUpsample(torch.autograd.Function):
+    """`forward_flownets`' upsample for the whole list of time offsets; the backward is ONE vfi_flow_upsample4_backward call
+    over the outputs that received a gradient (per eight of them: the partial sums are added in group order)."""
+
+    @staticmethod
+    def forward(ctx, flow_q, div_flow, time_offsets):
+        ctx.div_flow, ctx.time_offsets = div_flow, time_offsets
+        ctx.q_shape = tuple(flow_q.shape)
+        ctx.set_materialize_grads(False)                   # (an unused output is an absent item, not a tensor of zeros)
+        return tuple(_flow_upsample_launch(flow_q, div_flow, time_offsets))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        live = [i for i, g in enumerate(grads) if g is not None]
+        if not live:
+            return None, None, None
+        gs = _grad_layout([grads[i] for i in live])
+        parts = []
+        for k in range(0, len(live), UP4_ITEMS):
+            gq = torch.empty(ctx.q_shape, device=gs[0].device, dtype=torch.float32)
+            _check(cabi.flow_upsample4_backward(gs[k:k + UP4_ITEMS], ctx.div_flow,
+                                                [ctx.time_offsets[i] for i in live[k:k + UP4_ITEMS]], gq), "flow_upsample4_backward")
+            parts.append(gq)
+        return _add_in_order(parts), None, None
+
+
+def forward_flownets_upsample(flow_q, div_flow, time_offsets):
+    """`forward_flownets` after the flow network: [div_flow * flow * t upsampled x4 for t in time_offsets].
+    Differentiable when grad mode is on and flow_q requires grad (div_flow and the time offsets are Python floats, with
+    no gradient): flow_q's gradient is the adjoint of the upsample applied to every output's gradient, summed over the
+    time offsets in list order inside one kernel -- reproducible bit for bit, where torch's `upsample_bilinear2d_backward`
+    adds with atomics.  Otherwise the plain forward launches, with no grad_fn."""
+    if _wants_grad(flow_q):
+        return list(_FlowUpsample.apply(flow_q, float(div_flow), tuple(float(t) for t in time_offsets)))
+    return _flow_upsample_launch(flow_q, div_flow, time_offsets)
 
 
 def _flow_project_launch(inputs, depth, fillhole):
@@ -152,11 +201,9 @@ def FlowProject_directions(cur_offset_outputs, depth_inv=None, fillhole=True):
     return [outs[:n0], outs[n0:]]
 
 
-def FlowProject_from_quarter(flow_q, div_flow, time_offsets, depth=None, fillhole=True):
-    """`forward_flownets` + `FlowProject` (inference: fillhole) in one call per time offset: the full-resolution flow lives in
-    a scratch tensor of the library, not in a tensor of the caller."""
+def _from_quarter_launch(flow_q, div_flow, time_offsets, depth, fillhole):
     b, _, hq, wq = flow_q.shape
-    outs = []
+    counts, outs = [], []
     for t in time_offsets:
         count = torch.empty((b, 1, 4 * hq, 4 * wq), device=flow_q.device, dtype=torch.float32)
         out = torch.empty((b, 2, 4 * hq, 4 * wq), device=flow_q.device, dtype=torch.float32)
@@ -165,8 +212,64 @@ def FlowProject_from_quarter(flow_q, div_flow, time_offsets, depth=None, fillhol
         else:
             err = cabi.depthflowprojection_forward_up4(flow_q, depth, count, out, float(div_flow), float(t), int(fillhole))
         _check(err, "flowprojection_forward_up4")
+        counts.append(count)
         outs.append(out)
-    return outs
+    return counts, outs
+
+
+class _FlowProjectFromQuarter(torch.autograd.Function):
+    """`forward_flownets` + `FlowProject` on the quarter-resolution flow: the forward is the *_forward_up4 call per time
+    offset, the backward ONE *_backward_up4 call (per eight time offsets) that never materialises the full-resolution
+    flow or its gradient.  It ignores fillhole, as `_FlowProject`'s and the reference's do."""
+
+    @staticmethod
+    def forward(ctx, div_flow, time_offsets, fillhole, flow_q, depth):
+        counts, outs = _from_quarter_launch(flow_q, div_flow, time_offsets, depth, fillhole)
+        ctx.div_flow, ctx.time_offsets, ctx.has_depth = div_flow, time_offsets, depth is not None
+        ctx.save_for_backward(flow_q, *counts, *([depth] + outs if depth is not None else []))
+        ctx.set_materialize_grads(False)                   # (an unused output is an absent item, not a tensor of zeros)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        n, saved = len(ctx.time_offsets), ctx.saved_tensors
+        flow_q, counts = saved[0], saved[1:1 + n]
+        live = [i for i, g in enumerate(grads) if g is not None]
+        if not live:
+            return None, None, None, None, None
+        gs = _grad_layout([grads[i] for i in live])
+        depth = saved[1 + n] if ctx.has_depth else None
+        if ctx.has_depth and not cabi._same_strides(gs[0], saved[2 + n]):      # (the depth form addresses gout like out)
+            gs = [g.contiguous() for g in gs]
+        want_depth = ctx.has_depth and ctx.needs_input_grad[4]
+        q_parts, d_parts = [], []
+        for k in range(0, len(live), UP4_ITEMS):
+            idx = live[k:k + UP4_ITEMS]
+            gq = torch.empty_like(flow_q)
+            gds = [torch.empty_like(depth) for _ in idx] if want_depth else None
+            _check(cabi.flowprojection_backward_up4(
+                flow_q, [counts[i] for i in idx], gs[k:k + UP4_ITEMS], ctx.div_flow, [ctx.time_offsets[i] for i in idx], gq,
+                depth, [saved[2 + n + i] for i in idx] if ctx.has_depth else None, gds), "flowprojection_backward_up4")
+            q_parts.append(gq)
+            d_parts += gds or []
+        return (None, None, None, _add_in_order(q_parts) if ctx.needs_input_grad[3] else None,
+                _add_in_order(d_parts) if want_depth else None)
+
+
+def FlowProject_from_quarter(flow_q, div_flow, time_offsets, depth=None, fillhole=True):
+    """`forward_flownets` + `FlowProject` in one call per time offset: the full-resolution flow lives in a scratch tensor of
+    the library, not in a tensor of the caller.  depth: the direction's inverse depth, shared by the time offsets, or None.
+    Differentiable when grad mode is on and flow_q or depth requires grad: flow_q's gradient is that of
+    `FlowProject(forward_flownets_upsample(flow_q, ...), depth)` bit for bit, from one fused call of the library for the
+    whole list (vfi_[depth]flowprojection_backward_up4: neither the full-resolution flow nor its gradient is stored), and
+    depth gets the sum of the time offsets' depth gradients, added in list order.  Reproducible bit for bit.  The
+    reference trains with fillhole=0 (networks/DAIN.py:218); fillhole keeps its meaning in the forward, and the backward
+    ignores it, as the reference's does.  Otherwise (inference) the plain forward launches, with no grad_fn."""
+    if _wants_grad(flow_q, *([] if depth is None else [depth])):
+        return list(_FlowProjectFromQuarter.apply(float(div_flow), tuple(float(t) for t in time_offsets), bool(fillhole),
+                                                  flow_q, depth))
+    return _from_quarter_launch(flow_q, div_flow, time_offsets, depth, fillhole)[1]
 
 
 def _filter_interpolate_launch(ref0, ref2, off0, off2, filt0, filt2, w0, w2):
