@@ -462,6 +462,71 @@ int vfi_frame_error_sums(const unsigned char* a, const unsigned char* b, int64_t
 int vfi_frame_ssim_sums(const unsigned char* a, const unsigned char* b, int batch, int h, int w,
                         long long* sums, vfi_stream_t stream);
 
+/* ==== training losses (loss_function.py: part_loss as train.py calls it) ========================================
+ * The Charbonnier pixel loss of nd tensors, the gradient-adaptive total variation of a flow pair and the pair's
+ * motion-symmetry loss, forward in one launch plus a small finish launch, backward in one launch.
+ *
+ *   x_i      = diffs[i]                       (target == NULL)
+ *            = diffs[i] - target              (target given: diffs[i] is the network output; one fp32 rounding)
+ *   e2       = (float)(epsilon * epsilon)     (the product in double)
+ *   l_ib     = mean over [cd,h,w] of sqrt(x_i^2 + e2) of sample b          -> sample_means[i * batch + b]
+ *   pixel_i  = mean over [batch,cd,h,w] of sqrt(x_i^2 + e2)                (neg_psnr == 0)
+ *            = mean_b( -log(1 / l_ib) / 100 )                              (neg_psnr != 0)
+ *   tv(f, I) = mean over b, y < h-1, x < w-1 of  w (T_0 + T_1),
+ *              T_c = sqrt((f_c(y,x) - f_c(y+1,x))^2 + (f_c(y,x) - f_c(y,x+1))^2 + e2),
+ *              w   = exp(-sum over the ci channels of (|I(y,x) - I(y+1,x)| + |I(y,x) - I(y,x+1)|))
+ *   offset   = tv(flow0, img0) + tv(flow1, img1)                           (two fp32 means, one fp32 add)
+ *   sym      = mean over [batch,2,h,w] of sqrt((flow0 + flow1)^2 + e2)
+ *   values   = [pixel_0 .. pixel_{nd-1}, offset, sym]                      (nd + 2 floats on the device)
+ *
+ * Every term is formed in fp32, one rounding per operation (no contraction), and summed in double: per lane, then
+ * per wave, then per workgroup; the workgroups' partial sums go to a per-stream scratch buffer of the library and the
+ * finish launch adds them in a fixed order.  No floating-point atomics: results are reproducible bit for bit, and the
+ * same for a strided view as for its dense copy (rows are read 16 bytes at a time where base, strides and w allow,
+ * element by element otherwise; both give every lane the same elements in the same order).
+ *
+ * diffs: HOST array of 1 <= nd <= 8 device pointers, [batch,cd,h,w] each with strides sd; target (may be NULL) shares
+ * sd.  flow0 / flow1: [batch,2,h,w], strides sf, both given or both NULL (then values[nd] = values[nd+1] = 0 and the
+ * images are not read).  img0 / img1: [batch,ci,h,w], strides si, required with flows.  With flows h >= 2 and w >= 2
+ * (the total variation's mean would be over nothing).  Null required pointers, nd outside 1..8, non-positive sizes:
+ * VFI_ERR_SHAPE before any launch.  May allocate library scratch on its first call per stream. */
+int vfi_part_loss_forward(const float* const* diffs, int nd, const float* target,
+                          const float* flow0, const float* flow1,
+                          const float* img0, const float* img1,
+                          int batch, int cd, int ci, int h, int w,
+                          double epsilon, int neg_psnr,
+                          float* values, float* sample_means,
+                          vfi_strides sd, vfi_strides sf, vfi_strides si,
+                          vfi_stream_t stream);
+
+/* Gradients of sum_j grad_values[j] * values[j] in ONE launch; grad_values is a DEVICE vector of nd + 2 floats (nothing
+ * synchronises with the host).  loss_mask: bit j set = loss j takes part; a loss whose bit is clear is an absent term
+ * (not a multiplication by zero).  grad_diffs: HOST array of nd device pointers, entries (or the table) may be NULL =
+ * not wanted; grad_flow0 / grad_flow1 may be NULL.  Requested outputs are WRITTEN in full (zeros where every loss that
+ * reaches them is masked out); nothing else is touched -- with only pixel bits set and the flow gradients NULL the
+ * launch is one elementwise pass per requested diff and reads neither flows nor images.
+ *   grad_diffs[i] = c * (x / sqrt(x^2 + e2)),  c = grad_values[i] / (float)(batch cd h w), or with neg_psnr
+ *                   c_b = ((grad_values[i] / (float)(100 batch)) / sample_means[i * batch + b]) / (float)(cd h w);
+ *                   with target it is the gradient of diffs[i], the network output (target gets none).
+ *   grad_flow_s[c](y,x), terms added in this order into 0:
+ *        + (k w(y,x))   * ((dy + dx) / T_c(y,x))                  own cell,        y < h-1 and x < w-1
+ *        - (k w(y-1,x)) * (dy / T_c)  of the cell (y-1,x)         y >= 1 and x < w-1
+ *        - (k w(y,x-1)) * (dx / T_c)  of the cell (y,x-1)         x >= 1 and y < h-1
+ *        + ks * (u / sqrt(u^2 + e2)),  u = flow0 + flow1          symmetry
+ *     k = grad_values[nd] / (float)(batch (h-1) (w-1)), ks = grad_values[nd+1] / (float)(batch 2 h w); divide and sqrt
+ *     correctly rounded.  Images and target are data: no gradient.
+ * sample_means: what the forward wrote (read with neg_psnr only).  sgd: strides of every grad_diffs[i], sgf: of the
+ * flow gradients.  Nothing is allocated: the call can be captured in a graph. */
+int vfi_part_loss_backward(const float* const* diffs, int nd, const float* target,
+                           const float* flow0, const float* flow1,
+                           const float* img0, const float* img1,
+                           int batch, int cd, int ci, int h, int w,
+                           double epsilon, int neg_psnr,
+                           const float* grad_values, const float* sample_means, unsigned int loss_mask,
+                           float* const* grad_diffs, float* grad_flow0, float* grad_flow1,
+                           vfi_strides sd, vfi_strides sf, vfi_strides si, vfi_strides sgd, vfi_strides sgf,
+                           vfi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,11 @@ SIGNATURES = {
     "vfi_planar_to_frame_u8": [_p, _p, _i, _i, _i, _i, _i, Strides, _p],
     "vfi_frame_error_sums": [_p, _p, ctypes.c_int64, _p, _p],
     "vfi_frame_ssim_sums": [_p, _p, _i, _i, _i, _p, _p],
+    # training losses
+    "vfi_part_loss_forward": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, ctypes.c_double, _i, _p, _p, Strides, Strides,
+                              Strides, _p],
+    "vfi_part_loss_backward": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, ctypes.c_double, _i, _p, _p, ctypes.c_uint, _p, _p,
+                               _p, Strides, Strides, Strides, Strides, Strides, _p],
 }
 # internal entry points used by the bench / tests to time one code path in isolation
 INTERNAL_SIGNATURES = {
@@ -821,3 +826,94 @@ def frame_ssim_sums(a, b, sums):
     with torch.cuda.device(_dev(a, torch.uint8)):
         stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         return _finish(lib().vfi_frame_ssim_sums(_ptr(a), _ptr(b), a.size(0), a.size(1), a.size(2), _ptr(sums), stream))
+
+
+# ---------------------------------------------------------------- training losses (loss_function.py: part_loss)
+
+PART_LOSS_ITEMS = 8     # diffs per call of the library (LOSS_NMAX)
+
+
+def _part_loss_checks(diffs, target, flow0, flow1, img0, img1):
+    """(b, cd, ci, h, w) when the tensors of a part_loss call fit together, else None"""
+    n = len(diffs)
+    if n == 0 or n > PART_LOSS_ITEMS or (flow0 is None) != (flow1 is None):
+        return None
+    d0 = diffs[0]
+    if not _nchw_ok(*diffs) or not _addressed_as(d0, *diffs) or (target is not None and not _addressed_as(d0, target)):
+        return None
+    b, cd, h, w = d0.shape
+    ci = 0
+    if flow0 is not None:
+        if img0 is None or img1 is None or not _nchw_ok(flow0, flow1, img0, img1):
+            return None
+        ci = img0.size(1)
+        if tuple(flow0.shape) != (b, 2, h, w) or tuple(img0.shape) != (b, ci, h, w):
+            return None
+        if not _addressed_as(flow0, flow1) or not _addressed_as(img0, img1):
+            return None
+    return b, cd, ci, h, w
+
+
+def _part_loss_on_device(*tensors):
+    for t in tensors:
+        if t is not None:
+            _dev(t)
+
+
+def _opt(t):
+    return ctypes.c_void_p(0) if t is None else _ptr(t)
+
+
+def _opt_st(t, like=None):
+    return _st(t) if t is not None else (_st(like) if like is not None else Strides(0, 0, 0))
+
+
+def part_loss_forward(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr, values, sample_means):
+    """values[nd + 2] = the pixel losses of diffs (of diffs[i] - target with a target), the offset loss and the symmetry loss of
+    the flow pair (zeros when flow0 / flow1 are None); sample_means[nd * B] = the per-sample Charbonnier means."""
+    dims = _part_loss_checks(diffs, target, flow0, flow1, img0, img1)
+    if dims is None:
+        return 1
+    b, cd, ci, h, w = dims
+    n = len(diffs)
+    if values.numel() != n + 2 or sample_means.numel() != n * b or not values.is_contiguous() or not sample_means.is_contiguous():
+        return 1
+    _part_loss_on_device(*diffs, target, flow0, flow1, *((img0, img1) if flow0 is not None else ()), values, sample_means)
+    with torch.cuda.device(_dev(diffs[0])):
+        return _finish(lib().vfi_part_loss_forward(
+            _ptr_table(diffs), n, _opt(target), _opt(flow0), _opt(flow1), _opt(img0 if flow0 is not None else None),
+            _opt(img1 if flow0 is not None else None), b, cd, ci, h, w, float(epsilon), int(bool(neg_psnr)), _ptr(values),
+            _ptr(sample_means), _st(diffs[0]), _opt_st(flow0), _opt_st(img0 if flow0 is not None else None), _stream(diffs[0])))
+
+
+def part_loss_backward(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr, grad_values, sample_means, loss_mask,
+                       grad_diffs=None, grad_flow0=None, grad_flow1=None):
+    """The gradients of sum_j grad_values[j] * values[j] over the losses whose bit of loss_mask is set, into the tensors that
+    are given: grad_diffs (None, or one tensor or None per diff; they share one layout), grad_flow0 / grad_flow1.  Given
+    tensors are written in full."""
+    dims = _part_loss_checks(diffs, target, flow0, flow1, img0, img1)
+    if dims is None:
+        return 1
+    b, cd, ci, h, w = dims
+    n = len(diffs)
+    if grad_values.numel() != n + 2 or not grad_values.is_contiguous():
+        return 1
+    if neg_psnr and (sample_means is None or sample_means.numel() != n * b or not sample_means.is_contiguous()):
+        return 1
+    gds = [t for t in (grad_diffs or []) if t is not None]
+    gfs = [t for t in (grad_flow0, grad_flow1) if t is not None]
+    if (grad_diffs is not None and len(grad_diffs) != n) or (gfs and flow0 is None):
+        return 1
+    if not _nchw_ok(*gds, *gfs) or any(t.shape != diffs[0].shape for t in gds) or any(t.shape != flow0.shape for t in gfs):
+        return 1
+    if (gds and not _addressed_as(gds[0], *gds)) or (gfs and not _addressed_as(gfs[0], *gfs)):
+        return 1
+    _part_loss_on_device(*diffs, target, flow0, flow1, *((img0, img1) if flow0 is not None else ()), grad_values, sample_means,
+                         *gds, *gfs)
+    with torch.cuda.device(_dev(diffs[0])):
+        return _finish(lib().vfi_part_loss_backward(
+            _ptr_table(diffs), n, _opt(target), _opt(flow0), _opt(flow1), _opt(img0 if flow0 is not None else None),
+            _opt(img1 if flow0 is not None else None), b, cd, ci, h, w, float(epsilon), int(bool(neg_psnr)), _ptr(grad_values),
+            _opt(sample_means), int(loss_mask), None if grad_diffs is None else _ptr_table(grad_diffs), _opt(grad_flow0),
+            _opt(grad_flow1), _st(diffs[0]), _opt_st(flow0), _opt_st(img0 if flow0 is not None else None),
+            _opt_st(gds[0] if gds else None, diffs[0]), _opt_st(gfs[0] if gfs else None, flow0), _stream(diffs[0])))

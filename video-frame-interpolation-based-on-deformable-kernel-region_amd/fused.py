@@ -418,6 +418,127 @@ def corr_pair(c1_a, c2_a, c1_b, c2_b):
     return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
 
 
+class _PartLoss(torch.autograd.Function):
+    """The losses of one `part_loss` call as ONE tensor of nd + 2 values (vfi_part_loss_forward); the backward is ONE launch
+    (vfi_part_loss_backward) over the dense gradient vector autograd hands back.  `used` is the host-side set of loss
+    indices whose element received a gradient in this backward pass (filled by the hooks `part_loss` puts on the elements
+    it hands out): a loss outside it is an absent term, so `pixel_loss[1].backward()` is one elementwise pass over one
+    tensor.  Nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, epsilon, neg_psnr, used, target, flow0, flow1, img0, img1, *diffs):
+        values, means = _part_loss_launch(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr)
+        ctx.epsilon, ctx.neg_psnr, ctx.used, ctx.nd = epsilon, neg_psnr, used, len(diffs)
+        ctx.has_target, ctx.has_flows = target is not None, flow0 is not None
+        ctx.save_for_backward(means, *diffs, *([target] if target is not None else []),
+                              *([flow0, flow1, img0, img1] if flow0 is not None else []))
+        return values
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_values):
+        nd, saved = ctx.nd, ctx.saved_tensors
+        means, diffs = saved[0], list(saved[1:1 + nd])
+        rest = list(saved[1 + nd:])
+        target = rest.pop(0) if ctx.has_target else None
+        flow0, flow1, img0, img1 = rest if ctx.has_flows else (None, None, None, None)
+        used = sorted(ctx.used) if ctx.used else list(range(nd + 2))      # (no hook ran: values was used whole)
+        ctx.used.clear()
+        mask = sum(1 << j for j in used)
+        gds = [torch.empty_like(d) if ctx.needs_input_grad[8 + i] and (mask >> i) & 1 else None for i, d in enumerate(diffs)]
+        flow_terms = ctx.has_flows and (mask >> nd) & 3
+        gf0 = torch.empty_like(flow0) if flow_terms and ctx.needs_input_grad[4] else None
+        gf1 = torch.empty_like(flow1) if flow_terms and ctx.needs_input_grad[5] else None
+        if any(g is not None for g in (*gds, gf0, gf1)):
+            gv = grad_values.to(torch.float32).contiguous()
+            _check(cabi.part_loss_backward(diffs, target, flow0, flow1, img0, img1, ctx.epsilon, ctx.neg_psnr, gv, means, mask,
+                                           gds, gf0, gf1), "part_loss_backward")
+        return (None, None, None, None, gf0, gf1, None, None, *gds)
+
+
+def _part_loss_launch(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr):
+    d0 = diffs[0]
+    values = torch.empty(len(diffs) + 2, device=d0.device, dtype=torch.float32)
+    means = torch.empty(len(diffs) * d0.size(0), device=d0.device, dtype=torch.float32)
+    _check(cabi.part_loss_forward(list(diffs), target, flow0, flow1, img0, img1, epsilon, neg_psnr, values, means),
+           "part_loss_forward")
+    return values, means
+
+
+def _part_loss_call(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr):
+    """values[nd + 2] of one library call, with the autograd Function when something can train"""
+    diffs = list(diffs)
+    d0 = diffs[0]
+    if d0.dim() == 4 and not all(cabi._same_strides(d, d0) and d.stride(3) == 1 for d in diffs):
+        diffs = [d.contiguous() for d in diffs]
+    if target is not None and not cabi._same_strides(target, diffs[0]):     # (the library addresses target like the diffs)
+        diffs, target = [d.contiguous() for d in diffs], target.contiguous()
+    if flow0 is not None and not cabi._same_strides(flow0, flow1):
+        flow0, flow1 = flow0.contiguous(), flow1.contiguous()
+    if flow0 is not None and not cabi._same_strides(img0, img1):
+        img0, img1 = img0.contiguous(), img1.contiguous()
+    trainable = [t for t in (*diffs, flow0, flow1) if t is not None]
+    if not _wants_grad(*trainable):
+        return _part_loss_launch(diffs, target, flow0, flow1, img0, img1, epsilon, neg_psnr)[0], None
+    used = set()
+    return _PartLoss.apply(epsilon, neg_psnr, used, target, flow0, flow1, img0, img1, *diffs), used
+
+
+def _hand_out(values, used, indices):
+    """the elements of `values` as 0-dim tensors; each notes on the host that its loss received a gradient"""
+    out = []
+    for j in indices:
+        v = values[j]
+        if used is not None and v.requires_grad:
+            v.register_hook(lambda g, j=j: used.add(j))
+        out.append(v)
+    return out
+
+
+def part_loss(diffs, offsets, occlusions, images, epsilon, use_negPSNR=False, target=None):
+    """`loss_function.part_loss` as `train.py` calls it: returns (pixel_loss, offset_loss, sym_loss), lists of 0-dim tensors.
+      pixel_loss[i]  the Charbonnier loss of diffs[i] (the negative-PSNR form with use_negPSNR); with `target` the entries of
+                     diffs are the network's outputs and diffs[i] - target is formed inside the kernel, never stored;
+      offset_loss[k] the gradient-adaptive total variation of offsets[k] = [flow0, flow1] against images = [I0, I1]; one
+                     zero when offsets[0][0] is None, as in the reference;
+      sym_loss[k]    the motion-symmetry loss of offsets[k] (none when offsets[0][0] is None: the reference cannot form it).
+    occlusions is accepted and ignored, as in the reference.  The diffs and the first flow pair are one call of the library
+    (one forward launch plus a small finish launch); further pairs are calls of their own.  Differentiable when grad mode
+    is on and a diff or flow requires grad: the backward is one launch that computes only what the losses actually used
+    ask for, reproducible bit for bit.  Otherwise the plain forward, with no grad_fn.  Images and target are data: one
+    that requires grad is refused, not given a silent zero gradient."""
+    diffs = list(diffs)
+    if not diffs:
+        raise RuntimeError("part_loss: no diffs")
+    pairs = [] if offsets[0][0] is None else [(o[0], o[1]) for o in offsets]
+    for t in (*(images if pairs else ()), *([target] if target is not None else [])):
+        if t.requires_grad:
+            raise RuntimeError("part_loss: images and target are data; a tensor among them requires grad")
+    epsilon, neg = float(epsilon), bool(use_negPSNR)
+    nd = len(diffs)
+    pixel_loss, offset_loss, sym_loss = [], [], []
+    for k in range(0, nd, cabi.PART_LOSS_ITEMS):
+        chunk = diffs[k:k + cabi.PART_LOSS_ITEMS]
+        first = pairs[0] if pairs and k == 0 else (None, None)
+        values, used = _part_loss_call(chunk, target, first[0], first[1], images[0] if pairs else None,
+                                       images[1] if pairs else None, epsilon, neg)
+        picked = _hand_out(values, used, range(len(chunk) + (2 if k == 0 and pairs else 0)))
+        pixel_loss += picked[:len(chunk)]
+        if k == 0 and pairs:
+            offset_loss.append(picked[len(chunk)])
+            sym_loss.append(picked[len(chunk) + 1])
+    for f0, f1 in pairs[1:]:
+        # (the library's call carries at least one diff: the first one rides along and its value is not handed out)
+        values, used = _part_loss_call([diffs[0].detach()], None if target is None else target, f0, f1, images[0], images[1],
+                                       epsilon, neg)
+        picked = _hand_out(values, used, (1, 2))
+        offset_loss.append(picked[0])
+        sym_loss.append(picked[1])
+    if not pairs:
+        offset_loss = [torch.zeros(1, device=diffs[0].device)]
+    return pixel_loss, offset_loss, sym_loss
+
+
 def padding_for(height, width):
     """(left, right, top, bottom) of `demo_MiddleBury.py:294-310`: next multiple of 128, or 32 each side."""
     def one(n):
