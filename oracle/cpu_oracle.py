@@ -282,12 +282,14 @@ def correlation_fwd_f16(f1, f2, pad=4, k=1, md=4, s1=1, s2=1):
     return out
 
 
-def correlation_bwd(f1, f2, gout, pad=4, k=1, md=4, s1=1, s2=1):
+def correlation_bwd(f1, f2, gout, pad=4, k=1, md=4, s1=1, s2=1, fmad=1):
+    """fmad=1 (the default, and what the fixtures hold): `prod_sum += g * v` contracted as nvcc does by default;
+    fmad=0: the strict C reading, which the CPU execution of the reference reproduces bit for bit."""
     f1, f2, gout = _f32(f1), _f32(f2), _f32(gout)
     B, C, H, W = f1.shape
     g1, g2 = np.zeros_like(f1), np.zeros_like(f2)
-    _check(lib().vfi_oracle_correlation_bwd(_p(f1), _p(f2), _p(gout), _p(g1), _p(g2), B, C, H, W, pad, k, md, s1,
-                                            s2), "correlation_bwd")
+    _check(lib().vfi_oracle_correlation_bwd_fmad(_p(f1), _p(f2), _p(gout), _p(g1), _p(g2), B, C, H, W, pad, k, md,
+                                                 s1, s2, int(fmad)), "correlation_bwd")
     return g1, g2
 
 

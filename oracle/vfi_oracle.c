@@ -1,10 +1,11 @@
 /*
  * vfi_oracle.c -- CPU restatement (plain C, fp32) of the reference's hot path.
  *
- * TEST INFRASTRUCTURE ONLY -- see vfi_oracle.h.  "parity unpinned": the
- * reference holds no golden vectors for this path; this file follows the .cu
- * sources operation by operation and is pinned by analytic cases and by an
- * independent numpy formulation (tests/test_oracle.py).
+ * TEST INFRASTRUCTURE ONLY -- see vfi_oracle.h.  The reference holds no golden
+ * vectors for this path; this file follows the .cu sources operation by
+ * operation and is pinned by the reference's kernels run on the CPU
+ * (oracle/refexec), by analytic cases and by an independent numpy formulation
+ * (tests/test_oracle.py).
  *
  * Written from the behavioural description of the reference kernels (one
  * output / source pixel per loop iteration, channel loop inside, same operation
@@ -954,6 +955,12 @@ int vfi_oracle_correlation_fwd(const float* f1, const float* f2, float* out,
 int vfi_oracle_correlation_bwd(const float* f1, const float* f2, const float* gout,
                                float* g1, float* g2, int B, int C, int H, int W,
                                int pad, int k, int md, int s1, int s2) {
+    return vfi_oracle_correlation_bwd_fmad(f1, f2, gout, g1, g2, B, C, H, W, pad, k, md, s1, s2, 1);
+}
+
+int vfi_oracle_correlation_bwd_fmad(const float* f1, const float* f2, const float* gout,
+                                    float* g1, float* g2, int B, int C, int H, int W,
+                                    int pad, int k, int md, int s1, int s2, int fmad) {
     int oC, oH, oW;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 1;
     if (vfi_oracle_correlation_out_dims(H, W, pad, k, md, s1, s2, &oC, &oH, &oW)) return 1;
@@ -987,7 +994,7 @@ int vfi_oracle_correlation_bwd(const float* f1, const float* f2, const float* go
                     const float val2 = padded(f2, C, H, W, pad, n, c, y + j2, x + i2);
                     for (int j = ymin; j <= ymax; ++j)
                     for (int i = xmin; i <= xmax; ++i)
-                        s = fmaf(gout[(((i64)n * oC + tc) * oH + j) * oW + i], val2, s);
+                        s = mac(gout[(((i64)n * oC + tc) * oH + j) * oW + i], val2, s, fmad);
                 }
                 part[l] = s;
             }
@@ -1011,7 +1018,7 @@ int vfi_oracle_correlation_bwd(const float* f1, const float* f2, const float* go
                     const float val1 = padded(f1, C, H, W, pad, n, c, y - j2, x - i2);
                     for (int j = ymin; j <= ymax; ++j)
                     for (int i = xmin; i <= xmax; ++i)
-                        s = fmaf(gout[(((i64)n * oC + tc) * oH + j) * oW + i], val1, s);
+                        s = mac(gout[(((i64)n * oC + tc) * oH + j) * oW + i], val1, s, fmad);
                 }
                 part[l] = s;
             }

@@ -5,13 +5,14 @@
  * product: only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
  * leg may load this library, and only as the checker.
  *
- * PARITY STATUS: "parity unpinned" by the reference.  The reference ships no
- * golden vectors, no tests and no CPU path for these ops (SURVEY.md section 4 and
- * 8c), and its CUDA sources cannot be compiled or run in this image (no nvcc,
- * no GPU, removed ATen APIs).  This restatement follows the .cu sources line
- * by line (citations on every function) and is pinned by (1) analytic
- * known-answer cases and (2) an independent vectorised numpy formulation
- * (oracle/np_oracle.py) -- see tests/test_oracle.py.
+ * PARITY STATUS: the reference ships no golden vectors, no tests and no CPU
+ * path for these ops.  This restatement follows
+ * the .cu sources line by line (citations on every function) and is pinned by
+ * (1) the reference's own kernel files executed on the CPU (oracle/refexec,
+ * tests/test_reference_exec.py and its recording tests/golden/reference.npz):
+ * fmad = 0 is bit for bit what they compute, (2) analytic known-answer cases
+ * and (3) an independent vectorised numpy formulation (oracle/np_oracle.py)
+ * -- see tests/test_oracle.py.
  *
  * All tensors are dense NCHW float32.  Every function returns 0 on success and
  * the reference binding's own error value (1) on a shape problem.
@@ -111,6 +112,11 @@ int vfi_oracle_correlation_fwd(const float* f1, const float* f2, float* out,
 int vfi_oracle_correlation_bwd(const float* f1, const float* f2, const float* gout,
                                float* g1, float* g2, int B, int C, int H, int W,
                                int pad, int k, int md, int s1, int s2);
+/* the same with the contraction switch of the forwards: fmad = 1 is vfi_oracle_correlation_bwd (nvcc's
+ * default contracts `prod_sum += g * v`, :226, :318); fmad = 0 is the strict C reading of those lines */
+int vfi_oracle_correlation_bwd_fmad(const float* f1, const float* f2, const float* gout,
+                                    float* g1, float* g2, int B, int C, int H, int W,
+                                    int pad, int k, int md, int s1, int s2, int fmad);
 
 /* ---- glue either side of the ops.  These restate torch built-ins the reference
  * calls (third-party: ATen of torch 1.0-1.4; restated from ATen's UpSampleBilinear2d and GridSampler

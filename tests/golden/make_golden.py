@@ -1,9 +1,12 @@
 """Generates tests/golden/*.npz: small seeded inputs + expected outputs of every op.
 
-The reference holds no golden vectors and cannot run here, so the
-expected outputs come from the CPU restatement (oracle/vfi_oracle.c, strict mode,
-fmad=0), after tests/test_oracle.py has cross-checked it against the independent
-numpy formulation and the analytic cases.  The fixtures freeze that behaviour:
+The reference holds no golden vectors, so the expected outputs
+come from the CPU restatement (oracle/vfi_oracle.c, strict mode, fmad=0), after
+tests/test_oracle.py has cross-checked it against the independent numpy formulation
+and the analytic cases.  tests/test_reference_exec.py re-derives every array here that
+the reference defines (all but glue.npz) with the reference's own kernels executed on
+the CPU (oracle/refexec), bit for bit; that executor's outputs on edge inputs are a
+fixture of their own, written by make_reference_golden.py.  The fixtures freeze that behaviour:
 the CPU suite checks the oracle still reproduces them, the GPU suite compares
 the HIP kernels with them without needing the oracle at all.
 
