@@ -14,7 +14,7 @@ that a per-tap kernel (launched with a different block shape) redoes the tile.  
 
   tiles(kernel, flow, ...)        -> per (z, tile row, tile column) a record: boxes, channels per pass, labels
   predict_image_grad(kernel, ...) -> the image gradient bit for bit: the exact integer sums of rint(fp32 addend x 2^k)
-                                     per cell, converted once as gradacc_convert does (vfi_common.h "Deterministic image
+                                     per cell, converted once as gradacc_convert does (gradacc.h "Deterministic image
                                      gradients"); the staged and the per-tap paths add the same integers, so one
                                      restatement holds for every class
   build_field(kernel, rng, B, h, w) -> inputs in which every reachable label owns a tile in every batch item (and direction)
@@ -331,7 +331,7 @@ def name_cells(recs, kernel, bad, h, w, limit=4):
     return "%d cells differ; classes of the tiles reaching them: %s\n  %s" % (len(bad), sorted(classes), "\n  ".join(lines))
 
 
-# ------------------------------------------------------------------ the scale (gradacc_begin / gradacc_ctx)
+# ------------------------------------------------------------------ the scale (gradacc_scan / gradacc_ctx)
 
 def _frexp_exp(v):
     return math.frexp(float(v))[1] if v != 0 else 0

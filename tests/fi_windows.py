@@ -141,7 +141,7 @@ def split_prologue(kernel, fs=4, variant=0, nflows=2):
 
 
 def fi_channel_split(ntiles, channel, prologue, cu_count):
-    """workspace.hip fi_channel_split: (ch_per_group, groups)"""
+    """filterinterp.hip fi_channel_split: (ch_per_group, groups)"""
     if prologue is None:
         return channel, 1
     slots = cu_count * 2

@@ -46,8 +46,8 @@ def test_decision_expressions_match_the_sources():
     assert "__float2ll_rn(g * (1.0f - alpha) * (1.0f - beta) * gctx.scale)" in ws
     assert "__float2ll_rn(qgq * wg * gctx.scale)" in de and "__float2ll_rn(qgq * gctx.scale)" in de
     assert "__float2ll_rn(anw_v * gctx.scale)" in pw
-    assert "return v * cx.scale * cx.scale2;" in _flat("vfi_common.h")
-    assert "cells[x] += (float)ldexp((double)sum, -k);" in _flat("workspace.hip")
+    assert "return v * cx.scale * cx.scale2;" in _flat("gradacc.h")
+    assert "cells[x] += (float)ldexp((double)sum, -k);" in _flat("gradacc.hip")
 
 
 def test_constants_come_from_the_sources():
@@ -183,14 +183,23 @@ def test_warp_restatement_within_the_float64_bound():
     assert np.all(np.abs(got - gx) <= 4e-7 * A + 2.0 ** -(k - 2) + np.abs(np.spacing(gx.astype(f32))))
 
 
-def test_scale_exponent_restates_grad_exponent():
-    from tests.test_gpu_backward import grad_exponent
-    rng = np.random.default_rng(14)
-    for scale in (1.0, 1e-30, 3e5):
-        g = (rng.standard_normal((1, 3, 9, 33)) * scale).astype(f32)
-        filt = rng.random((1, 16, 9, 33), dtype=f32)
-        assert bt.grad_scale(g, filt, 9, 33, 16)[0] == grad_exponent(g, filt, 9, 33, 16)
-        assert bt.grad_scale(g, None, 9, 33, 4)[0] == grad_exponent(g, None, 9, 33, 4)
+def test_scale_exponent_hand_worked():
+    """k = 62 - L - eg - max(ew, 1), every term written out: 2^L >= h w max(taps, 4), 2^eg > max |g|, 2^ew > max |weight|"""
+    cases = [  # gout, weights, h, w, taps, k, fp32 path (the maxima are all grad_scale takes from the tensors)
+        ([0.25, -1.5], [0.5, 0.0], 9, 33, 16, 62 - 13 - 1 - 1, False),      # 9 * 33 * 16 = 4752 <= 2^13, 1.5 < 2^1, ew 0 -> 1
+        ([0.25, -1.5], None, 9, 33, 4, 62 - 11 - 1 - 1, False),             # 9 * 33 * 4 = 1188 <= 2^11, no weights: ew = 1
+        ([1.0], None, 1, 128, 4, 62 - 9 - 1 - 1, False),                    # h w taps = 512 = 2^9; 1.0 = 0.5 * 2^1
+        ([1.0], None, 1, 129, 4, 62 - 10 - 1 - 1, False),                   # 516: one column above the power of two
+        ([0.0, 4.0], None, 9, 33, 4, 62 - 11 - 3 - 1, False),               # max |g| a power of two: 4 = 0.5 * 2^3
+        ([np.nextafter(f32(4), f32(0))], None, 9, 33, 4, 62 - 11 - 2 - 1, False),   # and just below: < 2^2
+        ([1.5], [0.0, 0.75], 9, 33, 16, 62 - 13 - 1 - 1, False),            # weights below 1: ew clamps to 1
+        ([1.5], [0.0, 3.0], 9, 33, 16, 62 - 13 - 1 - 2, False),             # weights above 1: 3 < 2^2
+        ([0.0, 0.0], None, 9, 33, 4, 62 - 11 - 0 - 1, False),               # an all-zero gradient: eg = 0
+        ([3e38], [3.0], 9, 33, 16, 62 - 13 - 128 - 2, True),                # 2^127 <= 3e38 < 2^128: eg + ew = 130 > 128
+    ]
+    assert [c[5] for c in cases] == [47, 49, 51, 50, 47, 48, 47, 46, 50, -81]
+    for g, wt, h, w, taps, k, fp32 in cases:
+        assert bt.grad_scale(g, wt, h, w, taps)[:2] == (k, fp32)
     k, fp32, scale, scale2 = bt.grad_scale(np.full((1, 1, 9, 33), 1e-30, f32), None, 9, 33, 4)
     assert k > 126 and not fp32 and scale2 != 1
     assert bt.grad_scale(np.array([[[[np.inf]]]], f32), None, 1, 1, 4)[1]

@@ -1,18 +1,17 @@
 """`-m gpu` backward passes: every backward entry point on hypothesis-drawn shapes around the kernels' tiles, on strided views,
-and at the magnitude edges of the fixed-point image-gradient scatter (vfi_common.h: gradacc_*).
+and at the magnitude edges of the fixed-point image-gradient scatter (gradacc.h: gradacc_*).
 
   * per-pixel gradients (flow, filter, offsets, SeparableConv v / h, projections, correlation): bit-exact against the C
     oracle in fmad=1 mode;
   * image gradients of the warping layers, per cell:  |g - (g0 + e)| <= c u S + n 2^-(k+1) + ulp(g0 + e), with e, S, n the
     float64 sum, absolute sum and count of the cell's addends (oracle/np_oracle.py), g0 the tensor's starting value, k the
-    scale exponent restated from vfi_common.h, u = 2^-24 and c the fp32 roundings of one addend plus one for the conversion
+    scale exponent restated from gradacc.h, u = 2^-24 and c the fp32 roundings of one addend plus one for the conversion
     of the integer sum to float (IMG_ROUNDINGS); bit-exact on dyadic inputs; a second call gives the same bits.
 """
-import math
-
 import numpy as np
 import pytest
 
+from tests.bwd_tiles import grad_scale
 from tests.test_gpu_parity import cpu, gpu, smooth_flow, f32, torch_mod, cabi  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -32,12 +31,8 @@ def _settings(n):
 
 
 def grad_exponent(gout, weights, h, w, taps):
-    """the scale exponent k of a call (vfi_common.h gradacc_exponent, gradacc_begin): 62 - ceil(log2(h w max(taps, 4))) - eg - ew"""
-    L = max(0, math.ceil(math.log2(h * w * max(taps, 4))))
-    eg = math.frexp(float(np.abs(gout).max()))[1] if gout.size else 0
-    mw = float(np.abs(weights).max()) if weights is not None else 0.0
-    ew = math.frexp(mw)[1] if mw != 0.0 else 1
-    return 62 - L - eg - max(ew, 1)
+    """the scale exponent k of a call (gradacc.h gradacc_exponent, gradacc_scan): 62 - ceil(log2(h w max(taps, 4))) - eg - ew"""
+    return grad_scale(gout, weights, h, w, taps)[0]
 
 
 def assert_image_grad(got, g0, stats, k, kind):

@@ -188,6 +188,37 @@ def test_deterministic_and_overwrites(torch_mod, cabi):
         assert_same(x, y, "run to run")
 
 
+def test_shared_scratch_between_layouts(torch_mod, cabi):
+    """Calls that lay the shared gradient scratch out differently, back to back on one stream, each give the bits of the
+    same call made alone on fresh workspaces: two directions + flags (two tiles across, the second ragged), one smaller
+    direction (interpolation_backward), flags only, then the first again."""
+    torch = torch_mod
+    refs, flows, filts, (gb, g0, g2) = make_case(torch, 81, 1, 2, 9, 65, 16)
+    rng = np.random.default_rng(82)
+    img, gout = (gpu(torch, rng.standard_normal((1, 1, 5, 64))) for _ in range(2))
+    flow = gpu(torch, make_flow(rng, "subpixel", 1, 5, 64))
+
+    def blend(want):
+        return [o for o in fused_bwd(torch, cabi, refs, flows, filts, gb, g0, g2, 0.75, 0.25, want) if o is not None]
+
+    def interp():
+        g1, g2_ = torch.zeros_like(img), torch.zeros_like(flow)
+        assert cabi.interpolation_backward(img, flow, gout, g1, g2_) == 0
+        torch.cuda.synchronize()
+        return [g1, g2_]
+
+    calls = [lambda: blend((True,) * 6), interp, lambda: blend((False, False, True, True, True, True)),
+             lambda: blend((True,) * 6)]
+    alone = []
+    for call in calls:
+        assert cabi.release_workspaces() == 0
+        alone.append(call())
+    assert cabi.release_workspaces() == 0
+    for i, (call, want) in enumerate(zip(calls, alone)):
+        for a, b in zip(call(), want):
+            assert_same(a, b, "call %d after the others" % i)
+
+
 def test_non_finite_grad_blend(torch_mod, cabi):
     torch = torch_mod
     refs, flows, filts, (gb, g0, g2) = make_case(torch, 51, 1, 3, 30, 70, 16, "smooth")

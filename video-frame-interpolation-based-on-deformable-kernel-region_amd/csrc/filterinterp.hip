@@ -12,11 +12,24 @@
 // back to the kernel here when a tile's tap window does not fit its LDS budget.
 #include "filterinterp_dev.h"
 #include "filterinterp_paths.h"
-#include "workspace.h"
+#include "gradacc.h"
 
 #include <limits.h>
 
 namespace vfi {
+
+FiSplit fi_channel_split(int ntiles, int channel, double prologue) {
+    const int slots = device_cu_count() * 2;
+    int best = 1;
+    double best_cost = 0.0;
+    for (int g = 1; g <= 8 && g <= channel; ++g) {
+        const double r = (double)ntiles * g / slots;
+        const double cost = (channel + prologue * g) * ((r + 0.5) / r) * (1.0 + 0.25 / r);
+        if (g == 1 || cost < best_cost) { best_cost = cost; best = g; }
+    }
+    const int ch_per_group = (channel + best - 1) / best;
+    return FiSplit{ch_per_group, (channel + ch_per_group - 1) / ch_per_group};
+}
 
 // ------------------------------------------------------------------ forward, _ori
 
@@ -165,7 +178,7 @@ __device__ __forceinline__ void fi_backward_ori_px(
                     const int64_t o = ro + clampi(i, 0, w - 1);
                     const int64_t k = (int64_t)((j - T) * fs + (i - L)) * s3.c;
                     const float pv = p[o], fv = fpx[k];
-                    // image gradient: other pixels hit the same cell -> order-free fixed-point atomic (vfi_common.h).
+                    // image gradient: other pixels hit the same cell -> order-free fixed-point atomic (gradacc.h).
                     // The filter gradient cell belongs to this thread alone (index is this pixel's own), so a plain
                     // read-modify-write is equivalent to the reference's atomicAdd.
                     if (wx) gradacc_add(gp, gfp, (int64_t)clampi(j, 0, h - 1) * w + clampi(i, 0, w - 1), o, qg[quad] * fv, gctx);
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_ori(
 // instead of 512 x 16 addends per tile and channel).  Taps outside, the pass's channels inside; the 16 filter taps and
 // the 16 filter-gradient sums of the pixel live in registers (the per-tap kernel re-reads the taps and read-modify-writes
 // the gradient cells in global memory once per channel and tap).  Every sum keeps the per-tap kernel's order and starting
-// value: its bits.  A call with non-finite inputs (fp32 atomics: vfi_common.h) and a tile whose window does not fit are
+// value: its bits.  A call with non-finite inputs (fp32 atomics: gradacc.h) and a tile whose window does not fit are
 // flagged, and fi_backward_ori, launched after this kernel, does those tiles only.  A tile with a large window takes two
 // channels, or one, per pass.  Without the image gradient (WANT_X = false) the LDS holds the windows only; the channels per
 // pass stay those of the window budget (at C = 3 one pass covers every channel either way).
@@ -792,23 +805,21 @@ extern "C" int vfi_filterinterp_backward_ori(const float* input1, const float* i
     if (!input1 || !input2 || !input3 || !gradoutput || !gradinput1 || !gradinput2 || !gradinput3)
         return VFI_ERR_SHAPE;
     const int fs = fi_filter_size(filter_channels);
-    unsigned long long* acc;
-    int* hdr;
-    int* flags = nullptr;                                   // one word per FB_TW x FB_TH (64 x 8) tile: "the staged kernel left it alone"
+    GradAccScratch sc;                                      // flags: one word per FB_TW x FB_TH (64 x 8) tile: "the staged kernel left it alone"
     const int ntiles = ((w + FB_TW - 1) / FB_TW) * ((h + FB_TH - 1) / FB_TH) * batch;
-    int err = gradacc_begin((hipStream_t)stream, gradoutput, batch, channel, h, w, s1, input3, filter_channels, s3, &acc, &hdr,
-                            fs == 4 ? ntiles : 0, &flags);
+    int err = gradacc_begin((hipStream_t)stream, gradoutput, batch, channel, h, w, s1, input3, filter_channels, s3,
+                            fs == 4 ? ntiles : 0, &sc);
     if (err != VFI_OK) return err;
     static_assert(VFI_TX == FB_TW && FB_TH % VFI_TY == 0, "fi_backward_ori's blocks nest in the staged kernel's tiles");
     if (fs == 4)
         hipLaunchKernelGGL(fi_backward_ori4_lds, dim3((w + FB_TW - 1) / FB_TW, (h + FB_TH - 1) / FB_TH, batch), dim3(FB_THREADS), 0,
-                           (hipStream_t)stream, input1, input2, input3, gradoutput, acc, hdr, flags, gradinput2, gradinput3,
-                           channel, h, w, s1, s2, s3);
+                           (hipStream_t)stream, input1, input2, input3, gradoutput, sc.dir[0].acc, sc.dir[0].hdr, sc.flags,
+                           gradinput2, gradinput3, channel, h, w, s1, s2, s3);
     hipLaunchKernelGGL(fi_backward_ori, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, (hipStream_t)stream,
-                       input1, input2, input3, gradoutput, acc, hdr, gradinput1, gradinput2, gradinput3,
-                       channel, h, w, fs, s1, s2, s3, fs == 4 ? flags : nullptr);
+                       input1, input2, input3, gradoutput, sc.dir[0].acc, sc.dir[0].hdr, gradinput1, gradinput2, gradinput3,
+                       channel, h, w, fs, s1, s2, s3, sc.flags);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    return gradacc_finish((hipStream_t)stream, acc, hdr, gradinput1, batch, channel, h, w, s1);
+    return gradacc_finish((hipStream_t)stream, sc.dir[0], gradinput1, batch, channel, h, w, s1);
 }
 
 extern "C" int vfi_filterinterp_blend_backward(const float* ref0, const float* ref2, const float* flow0, const float* flow2,
@@ -827,52 +838,38 @@ extern "C" int vfi_filterinterp_blend_backward(const float* ref0, const float* r
     // writes every channel of a requested filter gradient
     const bool staged = fs == 4 && filter_channels == 16;
     const bool want_x = grad_ref0 || grad_ref2;
-    FiBwdPair pr;
-    pr.d[0] = FiBwdSide{ref0, flow0, filt0, GradTerms{grad_blend, grad_out0, w0}, nullptr, nullptr, grad_ref0, grad_flow0, grad_filt0};
-    pr.d[1] = FiBwdSide{ref2, flow2, filt2, GradTerms{grad_blend, grad_out2, w2}, nullptr, nullptr, grad_ref2, grad_flow2, grad_filt2};
-    // scratch of WS_GRADACC: [header 0][header 1][sums 0][sums 1] when the image gradient is wanted, then one flag word per
-    // 64 x 8 tile of both directions (staged), all zeroed on the stream
-    const int64_t n = (int64_t)batch * channel * h * w;
+    // both directions' sums when an image gradient is wanted, and one flag word per 64 x 8 tile of both directions (staged)
     const int ntiles = staged ? ((w + FB_TW - 1) / FB_TW) * ((h + FB_TH - 1) / FB_TH) * 2 * batch : 0;
-    const size_t xbytes = want_x ? 512 + (size_t)n * 16 : 0;
-    const size_t bytes = xbytes + (size_t)ntiles * 4;
-    int* flags = nullptr;
-    if (bytes) {
-        char* p = static_cast<char*>(ws_get(st, WS_GRADACC, bytes, false, nullptr));
-        if (!p) return VFI_ERR_LAUNCH;
-        if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) return VFI_ERR_LAUNCH;
-        if (ntiles) flags = reinterpret_cast<int*>(p + xbytes);
-        if (want_x)
-            for (int d = 0; d < 2; ++d) {
-                pr.d[d].hdr = reinterpret_cast<const int*>(p + 256 * d);
-                pr.d[d].acc = reinterpret_cast<unsigned long long*>(p + 512 + (size_t)n * 8 * d);
-            }
-    }
+    GradAccScratch sc;
+    if (gradacc_reserve(st, want_x ? 2 : 0, (int64_t)batch * channel * h * w, ntiles, &sc) != VFI_OK) return VFI_ERR_LAUNCH;
+    FiBwdPair pr;
+    pr.d[0] = FiBwdSide{ref0, flow0, filt0, GradTerms{grad_blend, grad_out0, w0}, sc.dir[0].acc, sc.dir[0].hdr, grad_ref0, grad_flow0, grad_filt0};
+    pr.d[1] = FiBwdSide{ref2, flow2, filt2, GradTerms{grad_blend, grad_out2, w2}, sc.dir[1].acc, sc.dir[1].hdr, grad_ref2, grad_flow2, grad_filt2};
     if (want_x)
         for (int d = 0; d < 2; ++d) {
             const FiBwdSide& sd = pr.d[d];
             if (!sd.gref) continue;
             // the fixed-point scale from the direction's own gradient as the kernels form it, and its filter
-            if (sd.g.any() && gradacc_scan_terms(st, sd.g, batch, channel, h, w, s_grad, sd.filt, filter_channels, s_filt,
-                                                 const_cast<int*>(sd.hdr)) != VFI_OK)
+            if (sd.g.any() && gradacc_scan(st, sd.g, batch, channel, h, w, s_grad, sd.filt, filter_channels, s_filt,
+                                           sc.dir[d].hdr) != VFI_OK)
                 return VFI_ERR_LAUNCH;
             if (gradacc_zero_fp32(st, sd.hdr, sd.gref, batch, channel, h, w, s_ref) != VFI_OK) return VFI_ERR_LAUNCH;
         }
     const dim3 tiles((w + FB_TW - 1) / FB_TW, (h + FB_TH - 1) / FB_TH, 2 * batch);
     const dim3 px = pixel_grid(w, h, 2 * batch), pxb(VFI_TX, VFI_TY, 1);
     if (staged) {
-        if (want_x) hipLaunchKernelGGL(fi_blend_backward4_lds<true>, tiles, dim3(FB_THREADS), 0, st, pr, flags, batch, channel, h, w,
+        if (want_x) hipLaunchKernelGGL(fi_blend_backward4_lds<true>, tiles, dim3(FB_THREADS), 0, st, pr, sc.flags, batch, channel, h, w,
                                        s_ref, s_flow, s_filt, s_grad);
-        else hipLaunchKernelGGL(fi_blend_backward4_lds<false>, tiles, dim3(FB_THREADS), 0, st, pr, flags, batch, channel, h, w,
+        else hipLaunchKernelGGL(fi_blend_backward4_lds<false>, tiles, dim3(FB_THREADS), 0, st, pr, sc.flags, batch, channel, h, w,
                                 s_ref, s_flow, s_filt, s_grad);
     }
-    if (want_x) hipLaunchKernelGGL(fi_blend_backward_general<true>, px, pxb, 0, st, pr, flags, batch, channel, h, w, fs,
+    if (want_x) hipLaunchKernelGGL(fi_blend_backward_general<true>, px, pxb, 0, st, pr, sc.flags, batch, channel, h, w, fs,
                                    filter_channels, s_ref, s_flow, s_filt, s_grad);
-    else hipLaunchKernelGGL(fi_blend_backward_general<false>, px, pxb, 0, st, pr, flags, batch, channel, h, w, fs, filter_channels,
+    else hipLaunchKernelGGL(fi_blend_backward_general<false>, px, pxb, 0, st, pr, sc.flags, batch, channel, h, w, fs, filter_channels,
                             s_ref, s_flow, s_filt, s_grad);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     for (int d = 0; d < 2 && want_x; ++d)
-        if (pr.d[d].gref && gradacc_finish_overwrite(st, pr.d[d].acc, pr.d[d].hdr, pr.d[d].gref, batch, channel, h, w, s_ref) != VFI_OK)
+        if (pr.d[d].gref && gradacc_finish(st, sc.dir[d], pr.d[d].gref, batch, channel, h, w, s_ref, true) != VFI_OK)
             return VFI_ERR_LAUNCH;
     return VFI_OK;
 }
@@ -946,19 +943,19 @@ extern "C" int vfi_filterinterp_backward_defor(int variant, const float* input1,
     if (variant < 0 || variant > 2) return VFI_ERR_SHAPE;
     const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* acc;
-    int* hdr;
     // (the tap weights of the variant without a filter are 1)
-    int* flags = nullptr;                                   // one word per block: "the staged instance left it alone"
+    GradAccScratch sc;                                      // flags: one word per block: "the staged instance left it alone"
     const int err = gradacc_begin(st, gradoutput, batch, channel, h, w, s1, variant == VFI_DEFOR_NOFILTER ? nullptr : input3,
-                                  filter_size * filter_size, s3, &acc, &hdr, (int)(grid.x * grid.y * grid.z), &flags);
+                                  filter_size * filter_size, s3, (int)(grid.x * grid.y * grid.z), &sc);
     if (err != VFI_OK) return err;
+    unsigned long long* const acc = sc.dir[0].acc;
+    const int* const hdr = sc.dir[0].hdr;
     // fs == 4: the LDS-staged kernel, then the per-tap fs == 4 instance for the blocks it flagged.  Otherwise, and when the
     // staged kernel declines the shape, the STAGED per-tap instance for any filter size, then its !STAGED one for the blocks
     // that one flagged.
     bool staged = false;
     if (filter_size == 4) {
-        const int r = launch_fi_defor_bwd_lds(variant, input1, input2, input3, input4, gradoutput, acc, hdr, flags, gradinput2,
+        const int r = launch_fi_defor_bwd_lds(variant, input1, input2, input3, input4, gradoutput, acc, hdr, sc.flags, gradinput2,
                                               gradinput3, gradinput4, batch, channel, h, w, s1, s2, s3, s4, stream);
         if (r != VFI_OK && r != FI_DECLINED) return VFI_ERR_LAUNCH;
         staged = r == VFI_OK;
@@ -969,7 +966,7 @@ extern "C" int vfi_filterinterp_backward_defor(int variant, const float* input1,
     float* g4 = nofilter ? gradinput3 : gradinput4;
     const vfi_strides t4 = nofilter ? s3 : s4;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, input1, input2, input3, in4, gradoutput, acc, hdr, flags, gradinput1,
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, input1, input2, input3, in4, gradoutput, acc, hdr, sc.flags, gradinput1,
                            gradinput2, gradinput3, g4, channel, h, w, filter_size, s1, s2, s3, t4);
     };
     switch (variant) {
@@ -987,5 +984,5 @@ extern "C" int vfi_filterinterp_backward_defor(int variant, const float* input1,
         break;
     }
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    return gradacc_finish(st, acc, hdr, gradinput1, batch, channel, h, w, s1);
+    return gradacc_finish(st, sc.dir[0], gradinput1, batch, channel, h, w, s1);
 }

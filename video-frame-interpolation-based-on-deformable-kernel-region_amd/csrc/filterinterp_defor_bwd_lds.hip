@@ -11,7 +11,7 @@
 // the block is staged for the three planes by LDS-DMA (borders replicated while staging, as in
 // filterinterp_defor_lds.hip), the taps read their corners from LDS, and the image-gradient addends -- exact 64-bit
 // integers, scattered to the clamped UNDISPLACED taps as in the reference -- are summed in a second LDS window and leave
-// with one global atomic per non-zero cell (vfi_common.h: gradacc_*; fi_backward_ori4_lds in filterinterp.hip).  Per tap
+// with one global atomic per non-zero cell (gradacc.h; fi_backward_ori4_lds in filterinterp.hip).  Per tap
 // the corner index, the two fractions, the weight and the three gradient sums (filter, offset y, offset x) stay in
 // registers across the channels, summed in the reference's order from the cells' starting values: the per-tap kernel's
 // bits.  No counted vmcnt here: a chunk's windows are waited for together (two workgroups per CU overlap).
@@ -20,6 +20,7 @@
 // gradients or weights raises its flag and returns; fi_backward_defor<V, false, 4>, launched afterwards, does those.
 #include "filterinterp_dev.h"
 #include "filterinterp_paths.h"
+#include "gradacc.h"
 
 #include <limits.h>
 

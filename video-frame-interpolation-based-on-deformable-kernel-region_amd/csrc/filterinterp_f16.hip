@@ -22,6 +22,7 @@
 //     window moved inside and the weights of the clamped taps added onto the column they clamp to.
 #define FI_PITCH_SKEW 16                            // (dwords; see fi_pitch_for)
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 #include <hip/hip_fp16.h>
 #include <limits.h>

@@ -25,6 +25,7 @@
 // time), which the two outputs per window pay for.  The four blend weights of an evaluation are formed once per tile
 // (blend4's own products: same bits) instead of once per channel.
 #include "filterinterp_dev.h"
+#include "filterinterp_paths.h"
 
 namespace vfi {
 

@@ -11,6 +11,15 @@ namespace vfi {
 constexpr int FI_DECLINED = -1;
 static_assert(FI_DECLINED != VFI_OK && FI_DECLINED != VFI_ERR_SHAPE && FI_DECLINED != VFI_ERR_LAUNCH, "a distinct result");
 
+// How the staged FilterInterpolation kernels split a tile's channel range over blockIdx.y: ch_per_group channels per
+// workgroup, `groups` workgroups (gridDim.y).  The number of groups g minimises a cost, in channels: a workgroup pays
+// `prologue` channels' worth before its first channel (flow, filter, bounding box, first window); a launch leaves half a
+// round of its slots (2 workgroups per CU) idle at the end on average; and the more workgroups a slot runs, the better their
+// unequal durations even out (they go to whichever slot frees first).  Fitted to launches timed in isolation (fs=4, 1080p,
+// C=196: 1 group 1.12 ms, 2 1.00-1.03, 3 0.99, 4 1.00, 8 1.08).  Defined in filterinterp.hip.
+struct FiSplit { int ch_per_group, groups; };
+FiSplit fi_channel_split(int ntiles, int channel, double prologue);
+
 // filterinterp_lds.hip: _ori forward, fs == 4
 int launch_fi_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
                       int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);

@@ -8,13 +8,14 @@
 //   gix = sum_c gm[c] * ((ne - nw) (y0 + 1 - iy) + (se - sw) (iy - y0))            (a corner outside the map reads 0)
 //   giy = sum_c gm[c] * ((sw - nw) (x0 + 1 - ix) + (se - ne) (ix - x0))
 //   grad_flow = (gix, giy) x grid_sampler_unnormalize's factor ((W-1)/2 aligned, W/2 not) x 2 / max(W-1, 1)
-// The image gradient is summed by the 64-bit fixed-point accumulator (vfi_common.h "Deterministic image gradients"): a
+// The image gradient is summed by the 64-bit fixed-point accumulator (gradacc.h "Deterministic image gradients"): a
 // 64x8 tile adds its integer addends in LDS over the bounding box of the corners its masked-in pixels touch and issues
 // one global atomic per non-zero cell (as interp_backward_lds, warp_sepconv.hip).  A tile whose box does not fit, a
 // call whose scale needs its second factor and a call on the fp32 path add per corner instead (gradacc_add).  The flow
 // gradient is a per-thread sum over the channels in a fixed order; when a pixel's channels are split over workgroups
 // (blockIdx.z = batch x channel groups, for parallelism at the coarse levels) the partial sums go to a scratch plane
 // and pwc_warp_flow_combine adds them in group order.  No float atomics outside the fp32 path: bit-reproducible.
+#include "gradacc.h"
 #include "pwc_warp.h"
 #include "workspace.h"
 
@@ -216,14 +217,13 @@ extern "C" int vfi_pwc_warp_backward(const float* x, const float* flow, const fl
         partial = static_cast<float*>(ws_get(st, WS_PWC_FLOW, (size_t)batch * groups * 2 * h * w * sizeof(float), false, nullptr));
         if (!partial) return VFI_ERR_LAUNCH;
     }
-    unsigned long long* acc = nullptr;
-    int* hdr = nullptr;
+    GradAccScratch sc{};
     if (grad_x) {                                           // (bilinear weights times the mask: at most 1; 4 taps per pixel)
-        const int err = gradacc_begin(st, grad_output, batch, channel, h, w, sgo, nullptr, 4, sgo, &acc, &hdr);
+        const int err = gradacc_begin(st, grad_output, batch, channel, h, w, sgo, nullptr, 4, sgo, 0, &sc);
         if (err != VFI_OK) return err;
     }
     hipLaunchKernelGGL(pwc_warp_backward_tile, dim3(tiles.x, tiles.y, (unsigned)(batch * groups)), dim3(PB_THREADS), 0, st,
-                       x, flow, grad_output, acc, hdr, grad_x, grad_flow, partial, channel, cgroup, groups, h, w,
+                       x, flow, grad_output, sc.dir[0].acc, sc.dir[0].hdr, grad_x, grad_flow, partial, channel, cgroup, groups, h, w,
                        align_corners ? 1 : 0, sfx, sfy, sx, sf, sgo, sgx, sgf);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     if (partial) {
@@ -231,5 +231,5 @@ extern "C" int vfi_pwc_warp_backward(const float* x, const float* flow, const fl
                            groups, h, w, sfx, sfy, sgf);
         if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     }
-    return grad_x ? gradacc_finish(st, acc, hdr, grad_x, batch, channel, h, w, sgx) : VFI_OK;
+    return grad_x ? gradacc_finish(st, sc.dir[0], grad_x, batch, channel, h, w, sgx) : VFI_OK;
 }

@@ -7,7 +7,7 @@
 // interpolation_cuda.cc, interpolationch_cuda.cc, separableconv_cuda.cc and
 // separableconvflow_cuda.cc.  One thread per output pixel, a wave = 64
 // consecutive x (coalesced plane rows), channel loop inside the thread.
-#include "vfi_common.h"
+#include "gradacc.h"
 
 namespace vfi {
 
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void interp_backward(
     const int R = min(L + 1, w - 1), Bm = min(T + 1, h - 1);
     const float alpha = x2 - (float)L, beta = y2 - (float)T;
     const float* img = in1 + (int64_t)b * s1.b;
-    unsigned long long* gimg = acc + (int64_t)b * channel * h * w;       // dense [b][c][y][x] fixed-point sums (vfi_common.h)
+    unsigned long long* gimg = acc + (int64_t)b * channel * h * w;       // dense [b][c][y][x] fixed-point sums (gradacc.h)
     const float* gpx = gout + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
     const int64_t oT = (int64_t)T * s1.h, oB = (int64_t)Bm * s1.h;
     const int64_t aT = (int64_t)T * w, aB = (int64_t)Bm * w;
@@ -381,21 +381,19 @@ extern "C" int vfi_interpolation_backward(const float* input1, const float* inpu
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || !input1 || !input2 || !gradoutput || !gradinput1 ||
         !gradinput2)
         return VFI_ERR_SHAPE;
-    unsigned long long* acc;
-    int* hdr;
     // (the tap weights are bilinear fractions: at most 1)
-    int* flags = nullptr;                                   // one word per 64x8 tile: "the staged kernel left it alone"
+    GradAccScratch sc;                                      // flags: one word per 64x8 tile: "the staged kernel left it alone"
     const dim3 tiles((w + IB_TW - 1) / IB_TW, (h + IB_TH - 1) / IB_TH, batch);
-    const int err = gradacc_begin((hipStream_t)stream, gradoutput, batch, channel, h, w, s1, nullptr, 0, s1, &acc, &hdr,
-                                  (int)(tiles.x * tiles.y * tiles.z), &flags);
+    const int err = gradacc_begin((hipStream_t)stream, gradoutput, batch, channel, h, w, s1, nullptr, 0, s1,
+                                  (int)(tiles.x * tiles.y * tiles.z), &sc);
     if (err != VFI_OK) return err;
     static_assert(VFI_TX == IB_TW && IB_TH % VFI_TY == 0, "interp_backward's blocks nest in the staged kernel's tiles");
     hipLaunchKernelGGL(interp_backward_lds, tiles, dim3(IB_THREADS), 0, (hipStream_t)stream,
-                       input1, input2, gradoutput, acc, hdr, flags, gradinput2, channel, h, w, s1, s2);
+                       input1, input2, gradoutput, sc.dir[0].acc, sc.dir[0].hdr, sc.flags, gradinput2, channel, h, w, s1, s2);
     hipLaunchKernelGGL(interp_backward, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, (hipStream_t)stream,
-                       input1, input2, gradoutput, acc, hdr, gradinput1, gradinput2, channel, h, w, s1, s2, flags);
+                       input1, input2, gradoutput, sc.dir[0].acc, sc.dir[0].hdr, gradinput1, gradinput2, channel, h, w, s1, s2, sc.flags);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    return gradacc_finish((hipStream_t)stream, acc, hdr, gradinput1, batch, channel, h, w, s1);
+    return gradacc_finish((hipStream_t)stream, sc.dir[0], gradinput1, batch, channel, h, w, s1);
 }
 
 extern "C" int vfi_separableconv_forward(const float* input1, const float* input2, const float* input3, float* output,

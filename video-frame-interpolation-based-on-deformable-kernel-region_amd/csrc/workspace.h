@@ -21,7 +21,7 @@ enum WsSlot {
     WS_PROJ_PLANES,         // projection fallback: three dense fp32 planes, zero between calls
     WS_PROJ_UPFLOW,         // *_forward_up4: the upsampled full-resolution flow (pure scratch)
     WS_MINDEPTH,            // MinDepthFlowProjection: 64-bit keys + bitmaps
-    WS_GRADACC,             // backward passes: 64-bit fixed-point image-gradient sums (vfi_common.h: gradacc_*)
+    WS_GRADACC,             // backward passes: 64-bit fixed-point image-gradient sums (gradacc.h lays it out)
     WS_PWC_FLOW,            // PWC-Net warp backward: per-channel-group partial flow gradients (pure scratch)
     WS_LOSS,                // part_loss: one double partial per workgroup and quantity (pure scratch, written before it is read)
     WS_SLOTS

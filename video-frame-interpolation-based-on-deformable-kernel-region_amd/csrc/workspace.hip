@@ -87,155 +87,6 @@ bool ws_get_group(hipStream_t stream, const WsSlot* slots, const size_t* bytes, 
     return true;
 }
 
-// ---- deterministic image gradients (vfi_common.h)
-// largest |element| of a [batch, channel, h, w] tensor into hdr[slot] (non-negative floats order like their bits); a NaN or an
-// infinity raises hdr[1]
-// G: a plain tensor (GradPlain) or the two terms of the blend backward's gradient (GradTerms, formed as its kernels form it)
-template <class G>
-__global__ __launch_bounds__(256) void gradacc_max(G g, int channel, int h, int w, vfi_strides sg, int64_t n,
-                                                   int* __restrict__ hdr, int slot, int cells_log2) {
-    int m = 0;
-    bool bad = false;
-    // a block per image row at a time: one set of divisions per row, consecutive lanes on consecutive elements
-    const int rows = (int)(n / w);
-    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int y = row % h, bc = row / h;
-        const int c = bc % channel, b = bc / channel;
-        const auto p = g.row((int64_t)b * sg.b + (int64_t)c * sg.c + (int64_t)y * sg.h);
-        for (int x = threadIdx.x; x < w; x += 256) {
-            const int bits = __float_as_int(fabsf(p[x]));
-            bad = bad || bits >= 0x7f800000;                // infinity or NaN
-            m = max(m, bits >= 0x7f800000 ? 0 : bits);
-        }
-    }
-    // one atomic per block, and only from a block that raises the maximum: thousands of atomics on one word serialise
-    // in L2 (measured: 0.2 ms per pass when every wave issued its own)
-    __shared__ int wm[4], wbad[4];
-    m = wave_max_i32(m);
-    const bool anybad = __builtin_amdgcn_ballot_w64(bad) != 0ull;       // (all lanes active here)
-    if ((threadIdx.x & 63) == 0) {
-        wm[threadIdx.x >> 6] = m;
-        wbad[threadIdx.x >> 6] = anybad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
-        if (m > __atomic_load_n(&hdr[slot], __ATOMIC_RELAXED)) atomicMax(&hdr[slot], m);
-        if ((wbad[0] | wbad[1] | wbad[2] | wbad[3]) && !__atomic_load_n(&hdr[1], __ATOMIC_RELAXED)) atomicOr(&hdr[1], 1);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && slot == 0) hdr[3] = cells_log2;
-}
-
-// OVERWRITE: every cell of g1 is written (the blend backward's caller does not zero its gradient); else added into
-template <bool OVERWRITE>
-__global__ __launch_bounds__(256) void gradacc_convert(const unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
-                                                       float* __restrict__ g1, int channel, int h, int w, vfi_strides s1, int64_t n) {
-    if (gradacc_fp32(hdr)) return;                          // the call scattered with fp32 atomics: nothing in the scratch
-    const int k = gradacc_exponent(hdr);
-    const int rows = (int)(n / w);
-    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int y = row % h, bc = row / h;
-        const int c = bc % channel, b = bc / channel;
-        const unsigned long long* a = acc + (int64_t)row * w;
-        float* cells = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c + (int64_t)y * s1.h;
-        for (int x = threadIdx.x; x < w; x += 256) {
-            const long long sum = (long long)a[x];
-            if constexpr (OVERWRITE) cells[x] = sum != 0 ? (float)ldexp((double)sum, -k) : 0.0f;    // (0 + v: the bits of v)
-            else if (sum != 0) cells[x] += (float)ldexp((double)sum, -k);    // exact integer sum -> float once
-        }
-    }
-}
-
-// before an fp32 scatter into a gradient the caller has not zeroed: zero it (nothing to do on the integer path)
-__global__ __launch_bounds__(256) void gradacc_zero_fp32_k(const int* __restrict__ hdr, float* __restrict__ g1, int channel, int h,
-                                                           int w, vfi_strides s1, int64_t n) {
-    if (!gradacc_fp32(hdr)) return;
-    const int rows = (int)(n / w);
-    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int y = row % h, bc = row / h;
-        const int c = bc % channel, b = bc / channel;
-        float* cells = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c + (int64_t)y * s1.h;
-        for (int x = threadIdx.x; x < w; x += 256) cells[x] = 0.0f;
-    }
-}
-
-int gradacc_begin(hipStream_t st, const float* gout, int batch, int channel, int h, int w, vfi_strides sg,
-                  const float* weights, int wchannel, vfi_strides sw, unsigned long long** acc, int** hdr,
-                  int nflags, int** flags) {
-    const int64_t n = (int64_t)batch * channel * h * w;
-    const size_t bytes = (size_t)n * 8 + 256 + (size_t)nflags * 4;
-    void* p = ws_get(st, WS_GRADACC, bytes, false, nullptr);
-    if (!p) return VFI_ERR_LAUNCH;
-    if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) return VFI_ERR_LAUNCH;
-    *hdr = static_cast<int*>(p);
-    *acc = reinterpret_cast<unsigned long long*>(static_cast<char*>(p) + 256);
-    if (flags) *flags = reinterpret_cast<int*>(static_cast<char*>(p) + 256 + (size_t)n * 8);
-    // addends one cell can receive: every pixel of the frame, with every one of its taps -- border clamping can put all fs x fs
-    // taps of a pixel (the four corners of a bilinear sample) on one cell (h w alone left (9/4) h w addends of
-    // nearly 2^(62 - L) possible on a corner cell at fs = 6)
-    const int64_t taps = wchannel > 4 ? wchannel : 4;
-    int cells_log2 = 0;
-    while (((int64_t)1 << cells_log2) < (int64_t)h * w * taps) ++cells_log2;
-    const int64_t rows = n / w;
-    const int blocks = (int)(rows < 2048 ? rows : 2048);
-    hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(blocks), dim3(256), 0, st, GradPlain{gout}, channel, h, w, sg, n, *hdr, 0,
-                       cells_log2);
-    if (weights) {
-        const int64_t nw = (int64_t)batch * wchannel * h * w;
-        const int64_t wrows = nw / w;
-        const int wblocks = (int)(wrows < 2048 ? wrows : 2048);
-        hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(wblocks), dim3(256), 0, st, GradPlain{weights}, wchannel, h, w, sw, nw,
-                           *hdr, 2, cells_log2);
-    }
-    return launch_status();
-}
-
-// gradacc_begin's scans with the gradient formed from its two terms (same header words, same cells_log2 rule)
-int gradacc_scan_terms(hipStream_t st, GradTerms g, int batch, int channel, int h, int w, vfi_strides sg,
-                       const float* weights, int wchannel, vfi_strides sw, int* hdr) {
-    const int64_t n = (int64_t)batch * channel * h * w;
-    const int64_t taps = wchannel > 4 ? wchannel : 4;
-    int cells_log2 = 0;
-    while (((int64_t)1 << cells_log2) < (int64_t)h * w * taps) ++cells_log2;
-    const int64_t rows = n / w;
-    const int blocks = (int)(rows < 2048 ? rows : 2048);
-    hipLaunchKernelGGL(gradacc_max<GradTerms>, dim3(blocks), dim3(256), 0, st, g, channel, h, w, sg, n, hdr, 0, cells_log2);
-    if (weights) {
-        const int64_t nw = (int64_t)batch * wchannel * h * w;
-        const int64_t wrows = nw / w;
-        const int wblocks = (int)(wrows < 2048 ? wrows : 2048);
-        hipLaunchKernelGGL(gradacc_max<GradPlain>, dim3(wblocks), dim3(256), 0, st, GradPlain{weights}, wchannel, h, w, sw, nw,
-                           hdr, 2, cells_log2);
-    }
-    return launch_status();
-}
-
-int gradacc_zero_fp32(hipStream_t st, const int* hdr, float* g1, int batch, int channel, int h, int w, vfi_strides s1) {
-    const int64_t n = (int64_t)batch * channel * h * w;
-    const int64_t rows = n / w;
-    const int blocks = (int)(rows < 2048 ? rows : 2048);
-    hipLaunchKernelGGL(gradacc_zero_fp32_k, dim3(blocks), dim3(256), 0, st, hdr, g1, channel, h, w, s1, n);
-    return launch_status();
-}
-
-int gradacc_finish(hipStream_t st, const unsigned long long* acc, const int* hdr, float* g1, int batch, int channel, int h, int w,
-                   vfi_strides s1) {
-    const int64_t n = (int64_t)batch * channel * h * w;
-    const int64_t rows = n / w;
-    const int blocks = (int)(rows < 8192 ? rows : 8192);
-    hipLaunchKernelGGL(gradacc_convert<false>, dim3(blocks), dim3(256), 0, st, acc, hdr, g1, channel, h, w, s1, n);
-    return launch_status();
-}
-
-int gradacc_finish_overwrite(hipStream_t st, const unsigned long long* acc, const int* hdr, float* g1, int batch, int channel,
-                             int h, int w, vfi_strides s1) {
-    const int64_t n = (int64_t)batch * channel * h * w;
-    const int64_t rows = n / w;
-    const int blocks = (int)(rows < 8192 ? rows : 8192);
-    hipLaunchKernelGGL(gradacc_convert<true>, dim3(blocks), dim3(256), 0, st, acc, hdr, g1, channel, h, w, s1, n);
-    return launch_status();
-}
-
 int device_cu_count() {
     static int cus[64];                             // 0 = not asked yet; racing first calls write the same value
     int dev = 0;
@@ -245,19 +96,6 @@ int device_cu_count() {
         cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     }
     return cus[dev];
-}
-
-FiSplit fi_channel_split(int ntiles, int channel, double prologue) {
-    const int slots = device_cu_count() * 2;
-    int best = 1;
-    double best_cost = 0.0;
-    for (int g = 1; g <= 8 && g <= channel; ++g) {
-        const double r = (double)ntiles * g / slots;
-        const double cost = (channel + prologue * g) * ((r + 0.5) / r) * (1.0 + 0.25 / r);
-        if (g == 1 || cost < best_cost) { best_cost = cost; best = g; }
-    }
-    const int ch_per_group = (channel + best - 1) / best;
-    return FiSplit{ch_per_group, (channel + ch_per_group - 1) / ch_per_group};
 }
 
 }  // namespace vfi
