@@ -42,23 +42,20 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct(
     const int y = blockIdx.y * VFI_TY + threadIdx.y;
     if (x >= w || y >= h) return;
     const int b = blockIdx.z;
-    const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-    const float fx = flow[0];
-    const float fy = flow[s2.c];
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y);
+    const float fx = fl.fx, fy = fl.fy;
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     const float* img = in1 + (int64_t)b * s1.b;
     float* dst = out + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
-    if (!fi_valid(fx, fy, x2, y2, w, h)) {
-        // copy-through (:2814-2818)
-        const float* src = img + (int64_t)y * s1.h + x;
-        for (int c = 0; c < channel; ++c) dst[(int64_t)c * s1.c] = src[(int64_t)c * s1.c];
+    if (!fi_valid(fx, fy, x2, y2, w, h)) {                  // (fi_point changes this kernel's code)
+        fi_copy_through(img + (int64_t)y * s1.h + x, dst, 0, channel, s1.c);
         return;
     }
-    const int ix = (int)x2, iy = (int)y2;
+    const FiGeom g = fi_cell(FiPoint{true, x2, y2});
+    const int ix = g.ix, iy = g.iy;
     const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
-    const float alpha = x2 - (float)ix;
-    const float beta = y2 - (float)iy;
+    const float alpha = g.alpha, beta = g.beta;
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
     if constexpr (FS4) {
         // fs == 4: every quadrant is 2x2; taps, clamped rows and columns hoisted out of the channel loop
@@ -135,26 +132,25 @@ __device__ __forceinline__ void fi_backward_ori_px(
     if (tileflag && !tileflag[(zb * ((h + FB_TH - 1) / FB_TH) + y / FB_TH) * gridDim.x + blockIdx.x]) return;
     const bool wx = WANT_X && (!BLEND || g1 != nullptr);   // (uniform: this direction's image gradient is wanted)
     const GradAccCtx gctx = wx ? gradacc_ctx(hdr) : GradAccCtx{1.0f, 1.0f, false};
-    const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-    const float fx = flow[0];
-    const float fy = flow[s2.c];
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y);
+    const float fx = fl.fx, fy = fl.fy;
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     float* gfpx = (!BLEND || g3) ? g3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x : nullptr;
     if constexpr (BLEND) {
         float* gf0 = g2 ? g2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x : nullptr;
-        if (!gsrc.any() || !fi_valid(fx, fy, x2, y2, w, h)) {
+        if (!gsrc.any() || !fi_valid(fx, fy, x2, y2, w, h)) {       // (fi_point changes this kernel's code)
             fi_bwd_zero_px(gf0, s2.c, gfpx, s3.c, fc);
             return;
         }
         if (gfpx) for (int k = 0; k < fc; ++k) gfpx[(int64_t)k * s3.c] = 0.0f;     // (every filter channel, taps or not)
     }
     if (!fi_valid(fx, fy, x2, y2, w, h)) return;           // no gradient (:2863-2864)
-    const int ix = (int)x2, iy = (int)y2;
+    const FiGeom g = fi_cell(FiPoint{true, x2, y2});
+    const int ix = g.ix, iy = g.iy;
     const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
     const int R = L + fs, Bm = T + fs;
-    const float alpha = x2 - (float)ix;
-    const float beta = y2 - (float)iy;
+    const float alpha = g.alpha, beta = g.beta;
     const float* img = in1 + (int64_t)b * s1.b;
     unsigned long long* gimg = acc + (int64_t)b * channel * h * w;       // dense [b][c][y][x] fixed-point sums
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
@@ -251,12 +247,9 @@ __device__ __forceinline__ void fi_backward_ori4_tile(
     const bool wx = WANT_X && (!BLEND || g1 != nullptr);   // (uniform: this direction's image gradient is wanted)
     const GradAccCtx gctx = wx ? gradacc_ctx(hdr) : GradAccCtx{1.0f, 1.0f, false};
     const bool inimg = x < w && y < h;
-    float fx = 0.0f, fy = 0.0f;
-    if (inimg) {
-        const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-        fx = flow[0];
-        fy = flow[s2.c];
-    }
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y, inimg);
+    // (written out: fi_geom changes the blend instances of this kernel)
+    const float fx = fl.fx, fy = fl.fy;
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     const bool valid = inimg && gsrc.any() && fi_valid(fx, fy, x2, y2, w, h);     // an invalid pixel has no gradient (:2863-2864)
@@ -469,24 +462,23 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_defor(
     const int y = blockIdx.y * VFI_TY + threadIdx.y;
     if (x >= w || y >= h) return;
     const int b = blockIdx.z;
-    const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-    const float fx = flow[0];
-    const float fy = flow[s2.c];
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y);
+    const float fx = fl.fx, fy = fl.fy;
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     const float* img = in1 + (int64_t)b * s1.b;
     float* dst = out + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
-    if (!fi_valid(fx, fy, x2, y2, w, h)) {
+    if (!fi_valid(fx, fy, x2, y2, w, h)) {                  // (fi_point changes this kernel's code)
         const float* src = img + (int64_t)y * s1.h + x;
         for (int c = 0; c < channel; ++c) dst[(int64_t)c * s1.c] = src[(int64_t)c * s1.c];
         return;
     }
     const int fs2 = fs * fs;
-    const int ix = (int)x2, iy = (int)y2;
+    const FiGeom g = fi_cell(FiPoint{true, x2, y2});
+    const int ix = g.ix, iy = g.iy;
     const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
     const int R = L + fs, Bm = T + fs;
-    const float alpha = x2 - (float)ix;
-    const float beta = y2 - (float)iy;
+    const float alpha = g.alpha, beta = g.beta;
     // VARIANT 2: the third input IS the offset field, there are no filter weights
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
     const float* opx = (VARIANT == VFI_DEFOR_NOFILTER) ? fpx : in4 + (int64_t)b * s4.b + (int64_t)y * s4.h + x;
@@ -577,12 +569,9 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_defor(
     }
     const bool inimg = x < w && y < h;
     const GradAccCtx gctx = gradacc_ctx(hdr);
-    float fx = 0.0f, fy = 0.0f;
-    if (inimg) {
-        const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-        fx = flow[0];
-        fy = flow[s2.c];
-    }
+    // (written out: fi_geom changes every instance of this kernel)
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y, inimg);
+    const float fx = fl.fx, fy = fl.fy;
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     const bool valid = inimg && fi_valid(fx, fy, x2, y2, w, h);

@@ -54,19 +54,11 @@ __global__ __launch_bounds__(DB_THREADS, 2) void fi_backward_defor_lds(
     const int tile = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const GradAccCtx gctx = gradacc_ctx(hdr);
     const bool inimg = x < w && y < h;
-    float fx = 0.0f, fy = 0.0f;
-    if (inimg) {
-        const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-        fx = flow[0];
-        fy = flow[s2.c];
-    }
-    const float x2 = (float)x + fx;
-    const float y2 = (float)y + fy;
-    const bool valid = inimg && fi_valid(fx, fy, x2, y2, w, h);
-    const int ix = valid ? (int)x2 : 0, iy = valid ? (int)y2 : 0;
-    const int L = ix + 1 - FS / 2, T = iy + 1 - FS / 2;
-    const float alpha = x2 - (float)ix;
-    const float beta = y2 - (float)iy;
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y, inimg);
+    const FiGeom g = fi_geom(fl.fx, fl.fy, x, y, w, h, inimg);
+    const bool valid = g.valid;
+    const int L = g.ix + 1 - FS / 2, T = g.iy + 1 - FS / 2;
+    const float x2 = g.x2, y2 = g.y2, alpha = g.alpha, beta = g.beta;
 
     // VARIANT 2: the third input IS the offset field and g3 its gradient; no filter
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;

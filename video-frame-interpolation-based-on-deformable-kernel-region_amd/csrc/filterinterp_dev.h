@@ -1,5 +1,5 @@
-// filterinterp_dev.h -- per-pixel device code shared by the direct and the
-// LDS-staged FilterInterpolation (_ori, fs == 4) forward kernels.
+// filterinterp_dev.h -- device code shared by the whole FilterInterpolation family: the direct and the LDS-staged
+// kernels, _ori and deformable, forward and backward, fp32 and fp16, and the fused blend in glue.hip.
 #pragma once
 #include "vfi_common.h"
 
@@ -8,6 +8,68 @@
 #include <type_traits>
 
 namespace vfi {
+
+// ---- one pixel's geometry (filterinterpolation_cuda_kernel.cu:2731-2747): the one definition for every kernel of the family
+// and for the host mirrors, oracle/np_oracle.py:_fi_geometry and tests/fi_windows.py:samples.  A kernel whose code a helper
+// changes keeps that step written out and says so there: the validity test of the kernels that return on an invalid pixel,
+// all of fi_backward_ori4_tile and fi_backward_defor.
+
+// validity test of the adaptive-warping layer (:2735-2736)
+__device__ __forceinline__ bool fi_valid(float fx, float fy, float x2, float y2, int w, int h) {
+    return x2 >= 0.0f && y2 >= 0.0f && x2 <= (float)(w - 1) && y2 <= (float)(h - 1) &&
+           fabsf(fx) < (float)w / 2.0f && fabsf(fy) < (float)h / 2.0f;
+}
+
+// the flow of pixel (x, y) of batch item b; 0 for a thread outside the image
+struct FiFlow { float fx, fy; };
+__device__ __forceinline__ FiFlow fi_flow_at(const float* __restrict__ in2, const vfi_strides& s2, int b, int x, int y,
+                                             bool inimg = true) {
+    FiFlow f{0.0f, 0.0f};
+    if (inimg) {
+        const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
+        f.fx = flow[0];
+        f.fy = flow[s2.c];
+    }
+    return f;
+}
+
+// FiPoint: where the flow sends the pixel, and whether the layer interpolates there.  FiGeom adds the cell: the integer
+// position (ix, iy) and the blend weights.  (The window corner L, T = ix + 1 - fs / 2, iy + 1 - fs / 2 stays with the kernels:
+// formed in here it changes their code.)
+struct FiPoint { bool valid; float x2, y2; };
+struct FiGeom : FiPoint { int ix, iy; float alpha, beta; };
+__device__ __forceinline__ FiPoint fi_point(float fx, float fy, int x, int y, int w, int h, bool inimg = true) {
+    FiPoint p;
+    p.x2 = (float)x + fx;
+    p.y2 = (float)y + fy;
+    p.valid = inimg && fi_valid(fx, fy, p.x2, p.y2, w, h);
+    return p;
+}
+// An invalid pixel that stays alive gets cell (ix_invalid, 0), and no conversion of an x2 that may be NaN or huge; nothing
+// reads its results.  The fp16 staged kernel passes 1, so that L = ix - 1 = 0: a window its column clamp leaves where it is.
+__device__ __forceinline__ FiGeom fi_cell(const FiPoint& p, int ix_invalid = 0) {
+    FiGeom g;
+    g.valid = p.valid; g.x2 = p.x2; g.y2 = p.y2;
+    g.ix = p.valid ? (int)p.x2 : ix_invalid;
+    g.iy = p.valid ? (int)p.y2 : 0;
+    g.alpha = p.x2 - (float)g.ix;
+    g.beta = p.y2 - (float)g.iy;
+    return g;
+}
+__device__ __forceinline__ FiGeom fi_geom(float fx, float fy, int x, int y, int w, int h, bool inimg = true, int ix_invalid = 0) {
+    return fi_cell(fi_point(fx, fy, x, y, w, h, inimg), ix_invalid);
+}
+
+// copy-through of an invalid pixel (:2814-2818), channels [c0, c1) in planes cs apart: from pointers to the pixel, or (the
+// staged kernels) from plane pointers and the pixel's element offset.  Two spellings, because either changes the other's kernels.
+template <typename E>
+__device__ __forceinline__ void fi_copy_through(const E* src, E* dst, int c0, int c1, int64_t cs) {
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * cs] = src[(int64_t)c * cs];
+}
+template <typename E>
+__device__ __forceinline__ void fi_copy_through(const E* src, E* dst, unsigned pix, int c0, int c1, int64_t cs) {
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * cs + pix] = src[(int64_t)c * cs + pix];
+}
 
 // One pixel's 4x4 window, fs == 4: every quadrant is 2x2.  v = the 16 image
 // taps (row major), f = the 16 filter taps.  Accumulation order inside each
@@ -91,6 +153,13 @@ __device__ __forceinline__ bool fi_box_fold(int* box, int tid, int lo_x, int lo_
     }
     __syncthreads();
     return box[0] != INT_MAX;
+}
+// a thread's own running box (lo_x, lo_y, hi_x, hi_y), widened by the 4x4 window at (L, T) of a valid pixel
+__device__ __forceinline__ void fi_box_add4(bool valid, int L, int T, int& lo_x, int& lo_y, int& hi_x, int& hi_y) {
+    if (valid) {
+        lo_x = min(lo_x, L); lo_y = min(lo_y, T);
+        hi_x = max(hi_x, L + 3); hi_y = max(hi_y, T + 3);
+    }
 }
 
 // A tile of a launch over tiles_x x tiles_y tiles per batch item, tile index row-major within an item: batch item b, tile

@@ -64,16 +64,15 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct_f16(
     const float y2 = (float)y + fy;
     const __half* img = in1 + (int64_t)b * s1.b;
     __half* dst = out + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
-    if (!fi_valid(fx, fy, x2, y2, w, h)) {
-        const __half* src = img + (int64_t)y * s1.h + x;
-        for (int c = 0; c < channel; ++c) dst[(int64_t)c * s1.c] = src[(int64_t)c * s1.c];
+    if (!fi_valid(fx, fy, x2, y2, w, h)) {                  // (fi_point changes this kernel's code)
+        fi_copy_through(img + (int64_t)y * s1.h + x, dst, 0, channel, s1.c);
         return;
     }
-    const int ix = (int)x2, iy = (int)y2;
+    const FiGeom g = fi_cell(FiPoint{true, x2, y2});
+    const int ix = g.ix, iy = g.iy;
     const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
     const int R = L + fs, Bm = T + fs;
-    const float alpha = x2 - (float)ix;
-    const float beta = y2 - (float)iy;
+    const float alpha = g.alpha, beta = g.beta;
     const float* fpx = in3 + (int64_t)b * s3.b + (int64_t)y * s3.h + x;
     for (int c = 0; c < channel; ++c) {
         const __half* plane = img + (int64_t)c * s1.c;
@@ -223,8 +222,7 @@ __device__ __forceinline__ void f16_run_channels(const __half* __restrict__ img,
     pixel(1, pout - cs);                                        // pixel 1 of the last channel
 #pragma unroll
     for (int p = 0; p < F16_PX; ++p)
-        if (px[p].inimg && !px[p].valid)
-            for (int cc = c_begin; cc < c_end; ++cc) out[(int64_t)cc * cs + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
+        if (px[p].inimg && !px[p].valid) fi_copy_through(img, out, px[p].pix, c_begin, c_end, cs);
 }
 
 __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
@@ -254,25 +252,18 @@ __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
         const int y = y0 + p * F16_PASS_ROWS;
         px[p].inimg = x < w && y < h;
         px[p].pix = (unsigned)(y * (int)s1.h + x);
-        float fx = 0.0f, fy = 0.0f;
+        float fx = 0.0f, fy = 0.0f;                         // (fi_flow_at changes this kernel's code)
         if (px[p].inimg) {
             const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
             fx = flow[0];
             fy = flow[s2.c];
         }
-        const float x2 = (float)x + fx;
-        const float y2 = (float)y + fy;
-        px[p].valid = px[p].inimg && fi_valid(fx, fy, x2, y2, w, h);
-        const int ix = px[p].valid ? (int)x2 : 1, iy = px[p].valid ? (int)y2 : 0;
-        L[p] = ix - 1;
-        T[p] = iy - 1;
+        const FiGeom g = fi_geom(fx, fy, x, y, w, h, px[p].inimg, 1);      // (an invalid pixel's window: L = 0)
+        px[p].valid = g.valid;
+        L[p] = g.ix - 1; T[p] = g.iy - 1;
         Lc[p] = clampi(L[p], 0, w - 4);                     // the window moved inside the image (w >= 4)
-        alpha[p] = x2 - (float)ix;
-        beta[p] = y2 - (float)iy;
-        if (px[p].valid) {
-            bx_lo = min(bx_lo, Lc[p]); by_lo = min(by_lo, T[p]);
-            bx_hi = max(bx_hi, Lc[p] + 3); by_hi = max(by_hi, T[p] + 3);
-        }
+        alpha[p] = g.alpha; beta[p] = g.beta;
+        fi_box_add4(g.valid, Lc[p], T[p], bx_lo, by_lo, bx_hi, by_hi);
     }
 
     if (tid == 0) fi_box_clear(box);
@@ -325,7 +316,7 @@ __global__ __launch_bounds__(F16_THREADS, 4) void fi_forward_ori_lds_f16(
                     dst[(int64_t)c * s1.c + px[p].pix] = f16_store_value(acc);
                 }
             } else if (px[p].inimg) {
-                for (int c = c_begin; c < c_end; ++c) dst[(int64_t)c * s1.c + px[p].pix] = img[(int64_t)c * s1.c + px[p].pix];
+                fi_copy_through(img, dst, px[p].pix, c_begin, c_end, s1.c);
             }
         }
         return;

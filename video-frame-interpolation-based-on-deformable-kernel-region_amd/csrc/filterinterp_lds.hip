@@ -480,8 +480,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
 #undef FI_READ64
 #pragma unroll
     for (int p = 0; p < FI_PX; ++p)                             // copy-through of the (rare) invalid pixels (:2814-2818)
-        if (px[p].inimg && !px[p].valid)
-            for (int cc = c_begin; cc < c_end; ++cc) out[(int64_t)cc * cs + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
+        if (px[p].inimg && !px[p].valid) fi_copy_through(img, out, px[p].pix, c_begin, c_end, cs);
 }
 
 // two 512-thread workgroups per CU (4 waves per SIMD): at most 128 VGPRs.
@@ -534,19 +533,11 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
 #pragma unroll
     for (int p = 0; p < FI_PX; ++p) {
         const int y = y0 + p * FI_PASS_ROWS;
-        const float fx = fxv[p], fy = fyv[p];
-        const float x2 = (float)x + fx;
-        const float y2 = (float)y + fy;
-        px[p].valid = px[p].inimg && fi_valid(fx, fy, x2, y2, w, h);
-        const int ix = px[p].valid ? (int)x2 : 0, iy = px[p].valid ? (int)y2 : 0;
-        L[p] = ix - 1;                                      // ix + 1 - fs/2, fs == 4
-        T[p] = iy - 1;
-        px[p].alpha = x2 - (float)ix;
-        px[p].beta = y2 - (float)iy;
-        if (px[p].valid) {
-            bx_lo = min(bx_lo, L[p]); by_lo = min(by_lo, T[p]);
-            bx_hi = max(bx_hi, L[p] + 3); by_hi = max(by_hi, T[p] + 3);
-        }
+        const FiGeom g = fi_geom(fxv[p], fyv[p], x, y, w, h, px[p].inimg);
+        px[p].valid = g.valid;
+        L[p] = g.ix - 1; T[p] = g.iy - 1;                   // ix + 1 - fs/2, fs == 4
+        px[p].alpha = g.alpha; px[p].beta = g.beta;
+        fi_box_add4(g.valid, L[p], T[p], bx_lo, by_lo, bx_hi, by_hi);
     }
 
     // ---- bounding box of every tap of the tile (unclamped window coordinates)
@@ -599,7 +590,7 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
                 fi4_channels_direct(img, dst + px[p].pix, c_begin, c_end, s1.c, (int)s1.h, h, w, L[p], T[p], px[p].f,
                                     px[p].alpha, px[p].beta);
             } else if (px[p].inimg) {
-                for (int c = c_begin; c < c_end; ++c) dst[(int64_t)c * s1.c + px[p].pix] = img[(int64_t)c * s1.c + px[p].pix];
+                fi_copy_through(img, dst, px[p].pix, c_begin, c_end, s1.c);
             }
             if (BLEND && px[p].inimg)                           // (this thread wrote dst[...] itself: it reads its own stores)
                 for (int c = c_begin; c < c_end; ++c) {

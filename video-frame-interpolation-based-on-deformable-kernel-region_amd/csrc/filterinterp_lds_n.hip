@@ -98,8 +98,7 @@ __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, f
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
-    if (px.inimg && !px.valid)                               // copy-through (:2814-2818)
-        for (int c = c_begin; c < c_end; ++c) out[(int64_t)c * cs + px.pix] = img[(int64_t)c * cs + px.pix];
+    if (px.inimg && !px.valid) fi_copy_through(img, out, px.pix, c_begin, c_end, cs);
 }
 
 template <int FS>
@@ -121,19 +120,10 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
     FnPixel<FS> px;
     px.inimg = x < w && y < h;
     px.pix = (unsigned)(y * (int)s1.h + x);
-    float fx = 0.0f, fy = 0.0f;
-    if (px.inimg) {
-        const float* flow = in2 + (int64_t)b * s2.b + (int64_t)y * s2.h + x;
-        fx = flow[0];
-        fy = flow[s2.c];
-    }
-    const float x2 = (float)x + fx;
-    const float y2 = (float)y + fy;
-    px.valid = px.inimg && fi_valid(fx, fy, x2, y2, w, h);
-    const int ix = px.valid ? (int)x2 : 0, iy = px.valid ? (int)y2 : 0;
-    const int L = ix + 1 - FS / 2, T = iy + 1 - FS / 2;
-    px.alpha = x2 - (float)ix;
-    px.beta = y2 - (float)iy;
+    const FiFlow fl = fi_flow_at(in2, s2, b, x, y, px.inimg);
+    const FiGeom g = fi_geom(fl.fx, fl.fy, x, y, w, h, px.inimg);
+    const int L = g.ix + 1 - FS / 2, T = g.iy + 1 - FS / 2;
+    px.valid = g.valid; px.alpha = g.alpha; px.beta = g.beta;
 
     if (tid == 0) fi_box_clear(box);
     __syncthreads();
@@ -181,7 +171,7 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
                 });
             }
         } else if (px.inimg) {
-            for (int c = c_begin; c < c_end; ++c) dst[(int64_t)c * s1.c + px.pix] = img[(int64_t)c * s1.c + px.pix];
+            fi_copy_through(img, dst, px.pix, c_begin, c_end, s1.c);
         }
         return;
     }

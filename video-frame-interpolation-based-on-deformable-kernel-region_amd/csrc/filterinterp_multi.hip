@@ -230,7 +230,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
         }
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
-    // copy-through of the invalid pixels (:2814-2818), outside the pipelined loop
+    // copy-through of the invalid pixels (:2814-2818), outside the pipelined loop (written out: fi_copy_through changes this code)
 #pragma unroll
     for (int t = 0; t < FM_NT; ++t)
 #pragma unroll
@@ -386,7 +386,7 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
         }
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
-    // copy-through of the invalid pixels (:2814-2818), outside the pipelined loop
+    // copy-through of the invalid pixels (:2814-2818), outside the pipelined loop (written out: fi_copy_through changes this code)
 #pragma unroll
     for (int t = 0; t < FM_NT; ++t)
 #pragma unroll
@@ -446,19 +446,11 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
         const int y = y0 + p * FM_PASS_ROWS;
 #pragma unroll
         for (int t = 0; t < FM_NT; ++t) {
-            const float fx = fxv[p][t], fy = fyv[p][t];
-            const float x2 = (float)x + fx;
-            const float y2 = (float)y + fy;
-            px[p].valid[t] = px[p].inimg && fi_valid(fx, fy, x2, y2, w, h);
-            const int ix = px[p].valid[t] ? (int)x2 : 0, iy = px[p].valid[t] ? (int)y2 : 0;
-            L[p][t] = ix - 1;                               // ix + 1 - fs/2, fs == 4
-            T[p][t] = iy - 1;
-            px[p].alpha[t] = x2 - (float)ix;
-            px[p].beta[t] = y2 - (float)iy;
-            if (px[p].valid[t]) {
-                bx_lo = min(bx_lo, L[p][t]); by_lo = min(by_lo, T[p][t]);
-                bx_hi = max(bx_hi, L[p][t] + 3); by_hi = max(by_hi, T[p][t] + 3);
-            }
+            const FiGeom g = fi_geom(fxv[p][t], fyv[p][t], x, y, w, h, px[p].inimg);
+            px[p].valid[t] = g.valid;
+            L[p][t] = g.ix - 1; T[p][t] = g.iy - 1;         // ix + 1 - fs/2, fs == 4
+            px[p].alpha[t] = g.alpha; px[p].beta[t] = g.beta;
+            fi_box_add4(g.valid, L[p][t], T[p][t], bx_lo, by_lo, bx_hi, by_hi);
         }
     }
 
@@ -496,7 +488,7 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
                     fi4_channels_direct(img, dst + px[p].pix, c_begin, c_end, s1.c, (int)s1.h, h, w, L[p][t], T[p][t], px[p].f,
                                         px[p].alpha[t], px[p].beta[t]);
                 } else if (px[p].inimg) {
-                    for (int c = c_begin; c < c_end; ++c) dst[(int64_t)c * s1.c + px[p].pix] = img[(int64_t)c * s1.c + px[p].pix];
+                    fi_copy_through(img, dst, px[p].pix, c_begin, c_end, s1.c);
                 }
             }
         return;

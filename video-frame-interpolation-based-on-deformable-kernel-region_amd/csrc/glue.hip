@@ -16,23 +16,15 @@ namespace vfi {
 
 // ------------------------------------------------------------------ FilterInterpolate x2 + blend
 
+// one side's pixel geometry (fi_geom) and window corner
 struct FiSide {
     bool valid;
     int L, T, ix, iy;
     float alpha, beta;
 };
 __device__ __forceinline__ FiSide fi_side(const float* __restrict__ flow, int64_t cstride, int x, int y, int w, int h, int fs) {
-    FiSide s;
-    const float fx = flow[0], fy = flow[cstride];
-    const float x2 = (float)x + fx, y2 = (float)y + fy;
-    s.valid = fi_valid(fx, fy, x2, y2, w, h);
-    s.ix = s.valid ? (int)x2 : 0;
-    s.iy = s.valid ? (int)y2 : 0;
-    s.L = s.ix + 1 - fs / 2;
-    s.T = s.iy + 1 - fs / 2;
-    s.alpha = x2 - (float)s.ix;
-    s.beta = y2 - (float)s.iy;
-    return s;
+    const FiGeom g = fi_geom(flow[0], flow[cstride], x, y, w, h);
+    return FiSide{g.valid, g.ix + 1 - fs / 2, g.iy + 1 - fs / 2, g.ix, g.iy, g.alpha, g.beta};
 }
 __device__ __forceinline__ float fi_side_value(const FiSide& s, const float* __restrict__ plane, const float* __restrict__ fpx,
                                                int64_t fcs, int hs, int h, int w, int fs, int x, int y) {

@@ -37,12 +37,6 @@ __device__ __forceinline__ float blend4(float a, float b, float TL, float TR, fl
     return t;
 }
 
-// validity test of the adaptive-warping layer (filterinterpolation_cuda_kernel.cu:2735-2736)
-__device__ __forceinline__ bool fi_valid(float fx, float fy, float x2, float y2, int w, int h) {
-    return x2 >= 0.0f && y2 >= 0.0f && x2 <= (float)(w - 1) && y2 <= (float)(h - 1) &&
-           fabsf(fx) < (float)w / 2.0f && fabsf(fy) < (float)h / 2.0f;
-}
-
 // Wave-wide min / max as six DPP steps at VALU rate (prefix within each row of 16 lanes, then
 // row_bcast:15 and row_bcast:31 carry the row results to lane 63), read back as a scalar.  The
 // __shfl_xor butterfly compiles to six dependent ds_bpermute_b32, each an LDS round trip.
