@@ -268,10 +268,12 @@ def test_depthflowprojection_4k_and_large_flows(torch_mod, cabi, oracle):
 
 
 @pytest.mark.parametrize("shape", [(1, 196, 18, 31), (1, 128, 36, 62), (2, 96, 72, 124), (1, 64, 144, 248), (1, 32, 288, 496),
-                                   (1, 7, 9, 13), (3, 16, 20, 44)])
+                                   (1, 7, 9, 13), (3, 16, 20, 44), (2, 5, 33, 130), (1, 3, 136, 514)])
 def test_correlation_pair_equals_two_calls(torch_mod, cabi, oracle, shape):
     """Both directions of a pyramid level in one launch == the two single calls bit for bit (all five 1080p level shapes, a
-    batch, unaligned widths), and == the oracle on the smallest."""
+    batch, unaligned widths), and == the oracle on the smallest.  The last two shapes are unaligned and take the pair through
+    the two kernels the others do not reach: corr_forward_k1_rows (324 tiles of 16x4, 100 of 32x8) and corr_forward_k1<4,32,8>
+    (578 tiles of 32x8); test_correlation_forward pins their single calls to the oracle."""
     torch = torch_mod
     from vfidkr_amd import fused
     B, C, H, W = shape

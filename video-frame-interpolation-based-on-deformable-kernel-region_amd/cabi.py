@@ -493,27 +493,28 @@ def correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, strid
     return oc.value, oh.value, ow.value
 
 
+def _corr_call(f32_name, f16_name, tensors, *args):
+    """The float entry, or for float16 tensors the reference's at::Half instantiation (no conversion), on the tensors' stream."""
+    half = tensors[0].dtype == torch.float16
+    for t in (tensors if half else tensors[:1]):            # (the float path checks its first tensor, as it always has)
+        _dev(t, torch.float16 if half else torch.float32)
+    device = tensors[0].device
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        err = getattr(lib(), f16_name if half else f32_name)(*[_ptr(t) for t in tensors], *args, stream)
+    if err != 0:
+        raise RuntimeError("CUDA call failed")
+
+
 def correlation_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2):
     """Allocates and returns the output, as the reference binding resizes its `output` argument."""
     input1, input2 = input1.contiguous(), input2.contiguous()
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
-    if input1.dtype == torch.float16:                       # the reference's at::Half instantiation
-        _dev(input1, torch.float16), _dev(input2, torch.float16)
-        output = torch.empty((b, oc, oh, ow), dtype=torch.float16, device=input1.device)
-        with torch.cuda.device(input1.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(input1.device).cuda_stream)
-            err = lib().vfi_correlation_forward_f16(_ptr(input1), _ptr(input2), _ptr(output), b, c, h, w, pad_size,
-                                                    kernel_size, max_displacement, stride1, stride2, stream)
-        if err != 0:
-            raise RuntimeError("CUDA call failed")
-        return output
-    output = torch.empty((b, oc, oh, ow), dtype=torch.float32, device=input1.device)
-    with torch.cuda.device(_dev(input1)):
-        err = lib().vfi_correlation_forward(_ptr(input1), _ptr(input2), _ptr(output), b, c, h, w, pad_size,
-                                            kernel_size, max_displacement, stride1, stride2, _stream(input1))
-    if err != 0:
-        raise RuntimeError("CUDA call failed")
+    dtype = torch.float16 if input1.dtype == torch.float16 else torch.float32
+    output = torch.empty((b, oc, oh, ow), dtype=dtype, device=input1.device)
+    _corr_call("vfi_correlation_forward", "vfi_correlation_forward_f16", (input1, input2, output), b, c, h, w, pad_size,
+               kernel_size, max_displacement, stride1, stride2)
     return output
 
 
@@ -542,23 +543,9 @@ def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_
     if input2.shape != input1.shape or \
             tuple(gradoutput.shape) != (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2):
         raise RuntimeError("correlation_backward: input2 / gradoutput do not match input1's shape and the output dimensions")
-    if input1.dtype == torch.float16:                       # the reference's at::Half instantiation (no conversion)
-        _dev(input1, torch.float16), _dev(input2, torch.float16), _dev(gradoutput, torch.float16)
-        g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
-        with torch.cuda.device(input1.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(input1.device).cuda_stream)
-            err = lib().vfi_correlation_backward_f16(_ptr(input1), _ptr(input2), _ptr(gradoutput), _ptr(g1), _ptr(g2), b, c,
-                                                     h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream)
-        if err != 0:
-            raise RuntimeError("CUDA call failed")
-        return g1, g2
     g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
-    with torch.cuda.device(_dev(input1)):
-        err = lib().vfi_correlation_backward(_ptr(input1), _ptr(input2), _ptr(gradoutput), _ptr(g1), _ptr(g2), b, c,
-                                             h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
-                                             _stream(input1))
-    if err != 0:
-        raise RuntimeError("CUDA call failed")
+    _corr_call("vfi_correlation_backward", "vfi_correlation_backward_f16", (input1, input2, gradoutput, g1, g2), b, c, h, w,
+               pad_size, kernel_size, max_displacement, stride1, stride2)
     return g1, g2
 
 

@@ -17,21 +17,17 @@
 // levels (hundreds to a few thousand pixels, up to 196 channels) would leave most of the chip
 // idle that way; they use 16x4-pixel tiles with one WAVE PER DISPLACEMENT ROW (9 waves per
 // workgroup, 9 running sums per lane), which spreads the same work over 9x more waves.
-#include "vfi_common.h"
+#include "correlation_dev.h"
 
 #include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 
 #include <hip/hip_fp16.h>
 
 namespace vfi {
 
-// The tensors of a launch: one call, or two calls of equal shape in one launch (both flow directions of a pyramid level: at
-// the coarse levels a launch is latency, 13-18 us for 1 MB, and two cost what one does).  Images 0 .. per - 1 are item 0's.
-struct CorrItems { const float* in1[2]; const float* in2[2]; float* out[2]; int per; };
-
-#define CORR_CC 8       // channels staged per LDS fill
-#define CORR_CC_ROWS 8   // ... in the small-frame kernel (16 measured the same: its chunk loop is LDS-bound, one workgroup per CU)
+#define CORR_CC 8       // channels staged per LDS fill of the 32x8 kernel (the others: CORR_CC_ROWS, correlation_dev.h)
 
 __device__ __forceinline__ float padded_at(const float* __restrict__ f, int h, int w, int y, int x) {
     return (y >= 0 && y < h && x >= 0 && x < w) ? f[(int64_t)y * w + x] : 0.0f;
@@ -49,11 +45,11 @@ __global__ __launch_bounds__(CORR_TW * CORR_TH) void corr_forward_k1(
 
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int ox = blockIdx.x * CORR_TW + tx, oy = blockIdx.y * CORR_TH + ty;
-    const int item_ = (int)blockIdx.z >= items.per ? 1 : 0;   // (two calls in one launch: vfi_correlation_forward_pair)
-    const int b = (int)blockIdx.z - item_ * items.per;
-    const float* __restrict__ in1 = items.in1[item_];
-    const float* __restrict__ in2 = items.in2[item_];
-    float* __restrict__ out = items.out[item_];
+    const CorrImage im = corr_image((int)blockIdx.z, items.per);
+    const int b = im.b;
+    const float* __restrict__ in1 = items.in1[im.item];
+    const float* __restrict__ in2 = items.in2[im.item];
+    float* __restrict__ out = items.out[im.item];
     const int64_t plane = (int64_t)h * w;
     const float* f1 = in1 + (int64_t)b * channel * plane;
     const float* f2 = in2 + (int64_t)b * channel * plane;
@@ -147,11 +143,11 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows(
     const int tid = tj * 64 + lane;
     const int px = lane & (TW - 1), py = lane >> 4;
     const int ox = blockIdx.x * TW + px, oy = blockIdx.y * TH + py;
-    const int item_ = (int)blockIdx.z >= items.per ? 1 : 0;   // (two calls in one launch: vfi_correlation_forward_pair)
-    const int b = (int)blockIdx.z - item_ * items.per;
-    const float* __restrict__ in1 = items.in1[item_];
-    const float* __restrict__ in2 = items.in2[item_];
-    float* __restrict__ out = items.out[item_];
+    const CorrImage im = corr_image((int)blockIdx.z, items.per);
+    const int b = im.b;
+    const float* __restrict__ in1 = items.in1[im.item];
+    const float* __restrict__ in2 = items.in2[im.item];
+    float* __restrict__ out = items.out[im.item];
     const int64_t plane = (int64_t)h * w;
     const float* f1 = in1 + (int64_t)b * channel * plane;
     const float* f2 = in2 + (int64_t)b * channel * plane;
@@ -232,113 +228,78 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows(
 template <int MD>
 __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
     CorrItems items, int channel, int h, int w, int oh, int ow, int org) {
-    constexpr int D = 2 * MD + 1;
-    constexpr int TW = 32, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;          // LW = 40: 10 aligned 16-byte units
-    constexpr int NT = 64 * D;
-    constexpr int UW = LW / 4, NU = CORR_CC_ROWS * LH * UW;                      // staged 16-byte units per chunk
-    constexpr int NPT = (NU + NT - 1) / NT;
-    constexpr int FU = CORR_CC_ROWS * TH * (TW / 4);                             // ... of the first map
-    constexpr int NF1 = (FU + NT - 1) / NT;
+    typedef CorrTile2<MD> T;                                                    // LW = 40: 10 aligned 16-byte units
+    constexpr int D = T::D, TW = T::TW, TH = T::TH;
     typedef float v2f __attribute__((ext_vector_type(2)));
     typedef float v4f __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) float tile[CORR_CC_ROWS][LH][LW];
-    __shared__ __attribute__((aligned(16))) float f1s[CORR_CC_ROWS][TH * TW];
+    __shared__ __attribute__((aligned(16))) float tile[T::CC][T::LH][T::LW];
+    __shared__ __attribute__((aligned(16))) float f1s[T::CC][TH * TW];
 
     const int lane = threadIdx.x, tj = threadIdx.y;
     const int tid = tj * 64 + lane;
-    const int px = 2 * (lane & 15), py = lane >> 4;
+    const int px = T::px(lane), py = T::py(lane);
     const int ox = blockIdx.x * TW + px, oy = blockIdx.y * TH + py;
-    const int item_ = (int)blockIdx.z >= items.per ? 1 : 0;   // (two calls in one launch: vfi_correlation_forward_pair)
-    const int b = (int)blockIdx.z - item_ * items.per;
-    const float* __restrict__ in1 = items.in1[item_];
-    const float* __restrict__ in2 = items.in2[item_];
-    float* __restrict__ out = items.out[item_];
+    const CorrImage im = corr_image((int)blockIdx.z, items.per);
+    const int b = im.b;
+    const float* __restrict__ in1 = items.in1[im.item];
+    const float* __restrict__ in2 = items.in2[im.item];
+    float* __restrict__ out = items.out[im.item];
     const int64_t plane = (int64_t)h * w;
     const float* f1 = in1 + (int64_t)b * channel * plane;
     const float* f2 = in2 + (int64_t)b * channel * plane;
-    // window origin in input coordinates; a multiple of 4 columns (the host checks org and MD), so with
-    // w a multiple of 4 every 16-byte unit lies wholly inside or wholly outside the frame
-    const int wy0 = blockIdx.y * TH + org - MD, wx0 = blockIdx.x * TW + org - MD;
 
-    // staging plans: unit e = tid + k*NT of the chunk's [CC][LH][UW] window block and of its [CC][TH][TW/4] first-map block
-    // (constant divisors), as byte offsets from the chunk's first plane; the loads are buffer loads through a descriptor that
-    // spans exactly the chunk's planes (corr_forward_k1_quad: units outside the frame and channels past the last return zeros)
-    unsigned soff[NPT], foff[NF1];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (LH * UW), rem = e - c * (LH * UW);
-        const int r = rem / UW, col = 4 * (rem - r * UW);
-        const int gy = wy0 + r, gx = wx0 + col;
-        const bool ok = e < NU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        soff[k] = ok ? 4u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
-#pragma unroll
-    for (int k = 0; k < NF1; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (TH * (TW / 4)), rem = e - c * (TH * (TW / 4));
-        const int gy = blockIdx.y * TH + rem / (TW / 4) + org, gx = blockIdx.x * TW + 4 * (rem % (TW / 4)) + org;
-        const bool ok = e < FU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        foff[k] = ok ? 4u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
+    // staging plans of the chunk's [CC][LH][UW] window block and of its [CC][TH][TW/4] first-map block (corr_unit_plan).  The
+    // window origin is a multiple of 4 columns: the host checks org and MD
+    unsigned soff[T::NPT], foff[T::NF1];
+    corr_unit_plan<4u, T::CC, T::LH, T::UW, T::NT>(soff, tid, blockIdx.y * TH + org - MD, blockIdx.x * TW + org - MD, h, w, (int)plane);
+    corr_unit_plan<4u, T::CC, TH, TW / 4, T::NT>(foff, tid, blockIdx.y * TH + org, blockIdx.x * TW + org, h, w, (int)plane);
 
     float acc[2][D];
 #pragma unroll
     for (int ti = 0; ti < D; ++ti) { acc[0][ti] = 0.0f; acc[1][ti] = 0.0f; }
 
     // the next chunk's units are fetched into registers before the current chunk is multiplied
-    v4f nv[NPT], nf[NF1];
+    v4f nv[T::NPT], nf[T::NF1];
     auto fetch = [&](int c0) {
-        const int cn = min(CORR_CC_ROWS, channel - c0);
+        const int cn = min(T::CC, channel - c0);
         const int bytes = cn * (int)plane * 4;
         const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, bytes);
         const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, bytes);
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) nv[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(d2, soff[k], 0, 0));
+        for (int k = 0; k < T::NPT; ++k) nv[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(d2, soff[k], 0, 0));
 #pragma unroll
-        for (int k = 0; k < NF1; ++k) nf[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(d1, foff[k], 0, 0));
+        for (int k = 0; k < T::NF1; ++k) nf[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(d1, foff[k], 0, 0));
     };
     fetch(0);
-    for (int c0 = 0; c0 < channel; c0 += CORR_CC_ROWS) {
-        const int cn = min(CORR_CC_ROWS, channel - c0);
+    for (int c0 = 0; c0 < channel; c0 += T::CC) {
+        const int cn = min(T::CC, channel - c0);
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const int e = tid + k * NT;
-            if (e < NU) reinterpret_cast<v4f*>(&tile[0][0][0])[e] = nv[k];
+        for (int k = 0; k < T::NPT; ++k) {
+            const int e = tid + k * T::NT;
+            if (e < T::NU) reinterpret_cast<v4f*>(&tile[0][0][0])[e] = nv[k];
         }
 #pragma unroll
-        for (int k = 0; k < NF1; ++k) {
-            const int e = tid + k * NT;
-            if (e < FU) reinterpret_cast<v4f*>(&f1s[0][0])[e] = nf[k];
+        for (int k = 0; k < T::NF1; ++k) {
+            const int e = tid + k * T::NT;
+            if (e < T::FU) reinterpret_cast<v4f*>(&f1s[0][0])[e] = nf[k];
         }
         __syncthreads();
-        if (c0 + CORR_CC_ROWS < channel) fetch(c0 + CORR_CC_ROWS);
+        if (c0 + T::CC < channel) fetch(c0 + T::CC);
         for (int c = 0; c < cn; ++c) {
             const v2f a = *reinterpret_cast<const v2f*>(&f1s[c][py * TW + px]);
-            const v2f* row = reinterpret_cast<const v2f*>(&tile[c][py + tj][px]);
-            float t[D + 1];
-#pragma unroll
-            for (int k = 0; k < (D + 1) / 2; ++k) {
-                const v2f q = row[k];
-                t[2 * k] = q.x;
-                t[2 * k + 1] = q.y;
-            }
+            v2f t[T::PAIRS];
+            T::read_row(&tile[c][py + tj][px], t);
             // (one v_fmac per term: left to itself the compiler packs the two pixels' terms into v_pk_fma_f32 -- 1.6 x a plain
             //  multiply-add each on gfx950 -- and pays four v_pk_mov per channel to line up the odd operand pairs: no faster)
 #pragma unroll
             for (int ti = 0; ti < D; ++ti) {
-                asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc[0][ti]) : "v"(a.x), "v"(t[ti]));
-                asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc[1][ti]) : "v"(a.y), "v"(t[ti + 1]));
+                asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc[0][ti]) : "v"(a.x), "v"(t[ti / 2][ti & 1]));
+                asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc[1][ti]) : "v"(a.y), "v"(t[(ti + 1) / 2][(ti + 1) & 1]));
             }
         }
     }
-    // (the mean of a power-of-two channel count as a product with the exact reciprocal: corr_forward_k1_quad)
-    const float nelems = (float)channel;
-    const bool pow2 = (channel & (channel - 1)) == 0;
-    const float inv = 1.0f / nelems;
-    auto store = [&](auto POW2) {
-        auto mean = [&](float v) { return decltype(POW2)::value ? v * inv : v / nelems; };
+    corr_store_mean(channel, [&](auto mean) {
         if (oy < oh && ox + 1 < ow && (ow & 1) == 0) {
             // the lane's two pixels as one 8-byte store: a wave writes whole 128-byte row segments
             float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox;
@@ -353,8 +314,7 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
                     for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = mean(acc[q][ti]);
                 }
         }
-    };
-    if (pow2) store(std::true_type{}); else store(std::false_type{});
+    });
 }
 
 // k == 1, strides 1, 16-byte-aligned rows, the LARGE levels (the finest pyramid level at 1080p: 288 x 496).  With one wave per
@@ -402,35 +362,20 @@ __device__ __forceinline__ void corr_quad_body(
     const int tj = G * g + wv;
     const int px = 4 * (lane & 15), py = lane >> 4;
     const int ox = txi * TW + px, oy = tyi * TH + py;
-    const int item_ = img_ >= items.per ? 1 : 0;
-    const int b = img_ - item_ * items.per;
-    const float* __restrict__ in1 = items.in1[item_];
-    const float* __restrict__ in2 = items.in2[item_];
-    float* __restrict__ out = items.out[item_];
+    const CorrImage im = corr_image(img_, items.per);
+    const int b = im.b;
+    const float* __restrict__ in1 = items.in1[im.item];
+    const float* __restrict__ in2 = items.in2[im.item];
+    float* __restrict__ out = items.out[im.item];
     const int64_t plane = (int64_t)h * w;
     const float* f1 = in1 + (int64_t)b * channel * plane;
     const float* f2 = in2 + (int64_t)b * channel * plane;
     const int wy0 = tyi * TH + org - MD + G * g, wx0 = txi * TW + org - MD;
 
-    // byte offsets of this thread's units from the chunk's first plane (out of any range: a unit outside the frame)
+    // byte offsets of this thread's units from the chunk's first plane (corr_unit_plan)
     unsigned soff[NPT], foff[NF1];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (LH * UW), rem = e - c * (LH * UW);
-        const int r = rem / UW, col = 4 * (rem - r * UW);
-        const int gy = wy0 + r, gx = wx0 + col;
-        const bool ok = e < NU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        soff[k] = ok ? 4u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
-#pragma unroll
-    for (int k = 0; k < NF1; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (TH * (TW / 4)), rem = e - c * (TH * (TW / 4));
-        const int gy = tyi * TH + rem / (TW / 4) + org, gx = txi * TW + 4 * (rem % (TW / 4)) + org;
-        const bool ok = e < FU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        foff[k] = ok ? 4u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
+    corr_unit_plan<4u, CCQ, LH, UW, NT>(soff, tid, wy0, wx0, h, w, (int)plane);
+    corr_unit_plan<4u, CCQ, TH, TW / 4, NT>(foff, tid, tyi * TH + org, txi * TW + org, h, w, (int)plane);
     // a wave's 64 lanes write 64 consecutive units: wave-uniform destination + lane * 16 bytes (M0).  A staging instruction whose
     // units lie past the block's end is skipped by the waves it has nothing for and runs with a partial exec mask in the last one.
     auto issue = [&](int c0, int buf) {
@@ -489,11 +434,7 @@ __device__ __forceinline__ void corr_quad_body(
     static_assert(CCQ == 4, "four channels per chunk");
     if (oy >= oh) return;
     float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox;
-    const float nelems = (float)channel;
-    const bool pow2 = (channel & (channel - 1)) == 0;
-    const float inv = 1.0f / nelems;
-    auto store = [&](auto POW2) {
-        auto mean = [&](float v) { return decltype(POW2)::value ? v * inv : v / nelems; };
+    corr_store_mean(channel, [&](auto mean) {
         if (ox + 3 < ow && (ow & 3) == 0) {
 #pragma unroll
             for (int ti = 0; ti < D; ++ti)
@@ -506,8 +447,7 @@ __device__ __forceinline__ void corr_quad_body(
                     for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow + q] = mean(acc[q][ti]);
                 }
         }
-    };
-    if (pow2) store(std::true_type{}); else store(std::false_type{});
+    });
 }
 
 // (the body is a device function: its inline assembly must not be instantiated by the host pass)
@@ -536,11 +476,11 @@ __global__ __launch_bounds__(256) void corr_forward_k1_flat(
     const int oy = (int)((gid / ow) % oh);
     const int tc = (int)((gid / ((int64_t)ow * oh)) % (D * D));
     const int bz = (int)(gid / ((int64_t)ow * oh * D * D));
-    const int item_ = bz >= items.per ? 1 : 0;              // (two calls in one launch: vfi_correlation_forward_pair)
-    const int b = bz - item_ * items.per;
-    const float* __restrict__ in1 = items.in1[item_];
-    const float* __restrict__ in2 = items.in2[item_];
-    float* __restrict__ out = items.out[item_];
+    const CorrImage im = corr_image(bz, items.per);
+    const int b = im.b;
+    const float* __restrict__ in1 = items.in1[im.item];
+    const float* __restrict__ in2 = items.in2[im.item];
+    float* __restrict__ out = items.out[im.item];
     const int y1 = oy + org, x1 = ox + org;
     const int y2 = y1 + tc / D - MD, x2 = x1 + tc % D - MD;
     float acc = 0.0f;
@@ -558,7 +498,7 @@ __global__ __launch_bounds__(256) void corr_forward_k1_flat(
         }
         for (; c < channel; ++c) acc = fmaf(p1[(int64_t)c * plane], p2[(int64_t)c * plane], acc);
     }
-    out[gid - (int64_t)item_ * items.per * D * D * oh * ow] = acc / (float)channel;
+    out[gid - (int64_t)im.item * items.per * D * D * oh * ow] = acc / (float)channel;
 }
 
 // any kernel size / strides: one thread per output element, sequential channel order
@@ -599,85 +539,61 @@ template <int MD>
 __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2_f16(
     const __half* __restrict__ in1, const __half* __restrict__ in2, __half* __restrict__ out,
     int channel, int h, int w, int oh, int ow, int org) {
-    constexpr int D = 2 * MD + 1;
-    constexpr int TW = 32, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;          // LW = 40 halves: 10 aligned 8-byte units
-    constexpr int NT = 64 * D;
-    constexpr int UW = LW / 4, NU = CORR_CC_ROWS * LH * UW;
-    constexpr int NPT = (NU + NT - 1) / NT;
-    constexpr int FU = CORR_CC_ROWS * TH * (TW / 4);
-    constexpr int NF1 = (FU + NT - 1) / NT;
-    __shared__ __attribute__((aligned(16))) __half tile[CORR_CC_ROWS][LH][LW];
-    __shared__ __attribute__((aligned(16))) __half f1s[CORR_CC_ROWS][TH * TW];
+    typedef CorrTile2<MD> T;                                                    // LW = 40 halves: 10 aligned 8-byte units
+    constexpr int D = T::D, TW = T::TW, TH = T::TH;
+    __shared__ __attribute__((aligned(16))) __half tile[T::CC][T::LH][T::LW];
+    __shared__ __attribute__((aligned(16))) __half f1s[T::CC][TH * TW];
 
     const int lane = threadIdx.x, tj = threadIdx.y;
     const int tid = tj * 64 + lane;
-    const int px = 2 * (lane & 15), py = lane >> 4;
+    const int px = T::px(lane), py = T::py(lane);
     const int ox = blockIdx.x * TW + px, oy = blockIdx.y * TH + py;
     const int b = blockIdx.z;
     const int64_t plane = (int64_t)h * w;
     const __half* f1 = in1 + (int64_t)b * channel * plane;
     const __half* f2 = in2 + (int64_t)b * channel * plane;
-    const int wy0 = blockIdx.y * TH + org - MD, wx0 = blockIdx.x * TW + org - MD;
 
-    // staging plans as byte offsets from the chunk's first plane; buffer loads through a descriptor that spans exactly the chunk's
-    // planes (corr_forward_k1_quad: units outside the frame and channels past the last one arrive as zeros)
-    unsigned soff[NPT], foff[NF1];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (LH * UW), rem = e - c * (LH * UW);
-        const int r = rem / UW, col = 4 * (rem - r * UW);
-        const int gy = wy0 + r, gx = wx0 + col;
-        const bool ok = e < NU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        soff[k] = ok ? 2u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
-#pragma unroll
-    for (int k = 0; k < NF1; ++k) {
-        const int e = tid + k * NT;
-        const int c = e / (TH * (TW / 4)), rem = e - c * (TH * (TW / 4));
-        const int gy = blockIdx.y * TH + rem / (TW / 4) + org, gx = blockIdx.x * TW + 4 * (rem % (TW / 4)) + org;
-        const bool ok = e < FU && gy >= 0 && gy < h && gx >= 0 && gx < w;
-        foff[k] = ok ? 2u * (unsigned)(c * (int)plane + gy * w + gx) : 0x80000000u;
-    }
+    // staging plans of the window block and the first-map block, in 8-byte units (corr_unit_plan)
+    unsigned soff[T::NPT], foff[T::NF1];
+    corr_unit_plan<2u, T::CC, T::LH, T::UW, T::NT>(soff, tid, blockIdx.y * TH + org - MD, blockIdx.x * TW + org - MD, h, w, (int)plane);
+    corr_unit_plan<2u, T::CC, TH, TW / 4, T::NT>(foff, tid, blockIdx.y * TH + org, blockIdx.x * TW + org, h, w, (int)plane);
 
     float acc[2][D];
 #pragma unroll
     for (int ti = 0; ti < D; ++ti) { acc[0][ti] = 0.0f; acc[1][ti] = 0.0f; }
 
-    uint2 nv[NPT], nf[NF1];
+    uint2 nv[T::NPT], nf[T::NF1];
     typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
     auto fetch = [&](int c0) {
-        const int cn = min(CORR_CC_ROWS, channel - c0);
+        const int cn = min(T::CC, channel - c0);
         const int bytes = cn * (int)plane * 2;
         const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, bytes);
         const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, bytes);
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) { const v2u_ v = __builtin_amdgcn_raw_buffer_load_b64(d2, soff[k], 0, 0); nv[k] = make_uint2(v.x, v.y); }
+        for (int k = 0; k < T::NPT; ++k) { const v2u_ v = __builtin_amdgcn_raw_buffer_load_b64(d2, soff[k], 0, 0); nv[k] = make_uint2(v.x, v.y); }
 #pragma unroll
-        for (int k = 0; k < NF1; ++k) { const v2u_ v = __builtin_amdgcn_raw_buffer_load_b64(d1, foff[k], 0, 0); nf[k] = make_uint2(v.x, v.y); }
+        for (int k = 0; k < T::NF1; ++k) { const v2u_ v = __builtin_amdgcn_raw_buffer_load_b64(d1, foff[k], 0, 0); nf[k] = make_uint2(v.x, v.y); }
     };
     fetch(0);
-    for (int c0 = 0; c0 < channel; c0 += CORR_CC_ROWS) {
-        const int cn = min(CORR_CC_ROWS, channel - c0);
+    for (int c0 = 0; c0 < channel; c0 += T::CC) {
+        const int cn = min(T::CC, channel - c0);
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const int e = tid + k * NT;
-            if (e < NU) reinterpret_cast<uint2*>(&tile[0][0][0])[e] = nv[k];
+        for (int k = 0; k < T::NPT; ++k) {
+            const int e = tid + k * T::NT;
+            if (e < T::NU) reinterpret_cast<uint2*>(&tile[0][0][0])[e] = nv[k];
         }
 #pragma unroll
-        for (int k = 0; k < NF1; ++k) {
-            const int e = tid + k * NT;
-            if (e < FU) reinterpret_cast<uint2*>(&f1s[0][0])[e] = nf[k];
+        for (int k = 0; k < T::NF1; ++k) {
+            const int e = tid + k * T::NT;
+            if (e < T::FU) reinterpret_cast<uint2*>(&f1s[0][0])[e] = nf[k];
         }
         __syncthreads();
-        if (c0 + CORR_CC_ROWS < channel) fetch(c0 + CORR_CC_ROWS);
+        if (c0 + T::CC < channel) fetch(c0 + T::CC);
         for (int c = 0; c < cn; ++c) {
             const __half2 a = *reinterpret_cast<const __half2*>(&f1s[c][py * TW + px]);
-            const __half2* row = reinterpret_cast<const __half2*>(&tile[c][py + tj][px]);
-            __half2 r[(D + 1) / 2];
-#pragma unroll
-            for (int k = 0; k < (D + 1) / 2; ++k) r[k] = row[k];
+            __half2 r[T::PAIRS];
+            T::read_row(&tile[c][py + tj][px], r);
 #pragma unroll
             for (int ti = 0; ti < D; ++ti) {
                 // (t[ti], t[ti + 1]): pixel 0 meets displacement column ti, pixel 1 the next one
@@ -691,19 +607,15 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2_f16(
         }
     }
     // (the mean of a power-of-two channel count as a product with the exact reciprocal: the same real number, rounded to half once)
-    const float nelems = (float)channel;
-    const bool pow2 = (channel & (channel - 1)) == 0;
-    const float inv = 1.0f / nelems;
-    auto store = [&](auto POW2) {
+    corr_store_mean(channel, [&](auto mean) {
 #pragma unroll
         for (int q = 0; q < 2; ++q)
             if (ox + q < ow && oy < oh) {
                 __half* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox + q;
 #pragma unroll
-                for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = __float2half_rn(decltype(POW2)::value ? acc[q][ti] * inv : acc[q][ti] / nelems);
+                for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = __float2half_rn(mean(acc[q][ti]));
             }
-    };
-    if (pow2) store(std::true_type{}); else store(std::false_type{});
+    });
 }
 
 // half inputs and output, the reference's `scalar_t = at::Half` instantiation (correlation_cuda_kernel.cu:386,403):
@@ -750,14 +662,49 @@ __global__ __launch_bounds__(256) void corr_forward_generic_f16(
     out[gid] = __float2half_rn(acc / (float)(k * k * channel));
 }
 
-// backward, stride1 == 1 (correlation_cuda_kernel.cu:151-334).  One thread per input
-// element; the reference's reduction order (32 partial sums over tc = l, l+32, ...,
-// then a sequential sum of the partials) is kept.
-template <bool SECOND>
-__global__ __launch_bounds__(256) void corr_backward(
-    const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
-    int batch, int channel, int h, int w, int oc, int oh, int ow,
-    int pad, int kr, int md, int s2, int dr) {
+// The arithmetic of a backward kernel: the element type, zero, the count the mean divides by, the term s <- s (+) g (*) v,
+// the sum of two partials and the mean.  CorrF32 is the reference's float instantiation, its `acc += a * b` fused as nvcc
+// fuses it.
+struct CorrF32 {
+    typedef float T;
+    static __device__ __forceinline__ T zero() { return 0.0f; }
+    static __device__ __forceinline__ float count(int n) { return (float)n; }
+    static __device__ __forceinline__ T term(T s, T g, T v) { return fmaf(g, v, s); }
+    static __device__ __forceinline__ T add(T r, T s) { return r + s; }
+    static __device__ __forceinline__ T mean(T r, float nelems) { return r / nelems; }
+};
+
+// The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541).
+// The terms, windows and skips are corr_backward's; the arithmetic is at::Half's, which goes through float and rounds back to
+// half after every operation: p = half(g * v), the 32 partials `__shared__ scalar_t prod_sum[32]` accumulate IN HALF,
+// r = half(r + s_l) for l = 0..31, gin = half(r / nelems_h) with nelems_h = half(k*k*C) (not the exact count above 2048).
+// float32 has 24 >= 2*11 + 2 significand bits, so float-then-round is the correctly rounded half operation: the products and
+// sums here are plain v_mul_f16 / v_add_f16 (never fused: -ffp-contract=off, no fma written), and the one division is done in
+// float on the two widened halves and rounded once.  A term whose other-map tap lies in the zero padding is NOT skipped: it
+// adds half(g * 0), which is NaN when g is inf or NaN.
+__device__ __forceinline__ __half corr_mean_f16(__half r, float nelems_h) {
+    float rf = __half2float(r);
+    asm volatile("" : "+v"(rf));        // (keeps the widening a v_cvt: nothing mixed-precision may be folded into the division)
+    return __float2half_rn(rf / nelems_h);
+}
+
+struct CorrF16 {
+    typedef __half T;
+    static __device__ __forceinline__ T zero() { return __float2half_rn(0.0f); }
+    static __device__ __forceinline__ float count(int n) { return __half2float(__float2half_rn((float)n)); }   // nelems_h
+    static __device__ __forceinline__ T term(T s, T g, T v) { return __hadd(s, __hmul(g, v)); }
+    static __device__ __forceinline__ T add(T r, T s) { return __hadd(r, s); }
+    static __device__ __forceinline__ T mean(T r, float nelems_h) { return corr_mean_f16(r, nelems_h); }
+};
+
+// backward, stride1 == 1, any pad / k / md / stride2 (correlation_cuda_kernel.cu:151-334).  One thread per gradient
+// element; the reference's reduction order (32 partial sums over tc = l, l+32, ..., then a sequential sum of the
+// partials) is kept.  A term whose other-map tap lies in the zero padding is not skipped: it adds g * 0 in A's arithmetic.
+template <class A, bool SECOND>
+__device__ __forceinline__ void corr_backward_body(
+    const typename A::T* __restrict__ other, const typename A::T* __restrict__ gout, typename A::T* __restrict__ gin,
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr) {
+    typedef typename A::T T;
     const int64_t total = (int64_t)batch * channel * h * w;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
@@ -767,44 +714,56 @@ __global__ __launch_bounds__(256) void corr_backward(
     const int n = (int)(gid / ((int64_t)w * h * channel));
     const int dsz = 2 * dr + 1;
     const int y = by + pad, x = bx + pad;                   // padded coordinates
-    const float* of = other + ((int64_t)n * channel + c) * h * w;
-    const float* go = gout + (int64_t)n * oc * oh * ow;
-    const float nelems = (float)((2 * kr + 1) * (2 * kr + 1) * channel);
-    float r = 0.0f;
+    const T* of = other + ((int64_t)n * channel + c) * h * w;
+    const T* go = gout + (int64_t)n * oc * oh * ow;
+    const float nelems = A::count((2 * kr + 1) * (2 * kr + 1) * channel);
     bool any = SECOND;
     if constexpr (!SECOND) {
         const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
         any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
     }
-    if (any) {
-        for (int l = 0; l < 32; ++l) {
-            float s = 0.0f;
-            for (int tc = l; tc < oc; tc += 32) {
-                const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
-                int xmin, ymin, xmax, ymax;
-                float val;
-                if constexpr (SECOND) {
-                    xmin = x - kr - md - i2; ymin = y - kr - md - j2;
-                    xmax = x + kr - md - i2; ymax = y + kr - md - j2;
-                    if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
-                    val = padded_at(of, h, w, y - j2 - pad, x - i2 - pad);
-                } else {
-                    xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
-                    val = padded_at(of, h, w, y + j2 - pad, x + i2 - pad);
-                }
-                xmin = max(0, xmin); xmax = min(ow - 1, xmax);
-                ymin = max(0, ymin); ymax = min(oh - 1, ymax);
-                const float* g = go + (int64_t)tc * oh * ow;
-                for (int j = ymin; j <= ymax; ++j)
-                    for (int i = xmin; i <= xmax; ++i) s = fmaf(g[(int64_t)j * ow + i], val, s);
-            }
-            r += s;
-        }
-        gin[gid] = r / nelems;
-    } else {
-        gin[gid] = 0.0f;        // the binding zero-fills gradInput (correlation_cuda.cc:112-113)
+    if (!any) {
+        gin[gid] = A::zero();   // the binding zero-fills gradInput (correlation_cuda.cc:112-113)
+        return;
     }
+    T r = A::zero();
+    for (int l = 0; l < 32; ++l) {
+        T s = A::zero();
+        for (int tc = l; tc < oc; tc += 32) {
+            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
+            int xmin, ymin, xmax, ymax, vy, vx;
+            if constexpr (SECOND) {
+                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
+                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
+                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
+                vy = y - j2 - pad; vx = x - i2 - pad;
+            } else {
+                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
+                vy = y + j2 - pad; vx = x + i2 - pad;
+            }
+            const T val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? of[(int64_t)vy * w + vx] : A::zero();
+            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
+            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
+            const T* g = go + (int64_t)tc * oh * ow;
+            for (int j = ymin; j <= ymax; ++j)
+                for (int i = xmin; i <= xmax; ++i) s = A::term(s, g[(int64_t)j * ow + i], val);
+        }
+        r = A::add(r, s);
+    }
+    gin[gid] = A::mean(r, nelems);
 }
+
+#define CORR_BACKWARD_ARGS(T) const T* __restrict__ other, const T* __restrict__ gout, T* __restrict__ gin, \
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward(CORR_BACKWARD_ARGS(float)) {
+    corr_backward_body<CorrF32, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr);
+}
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__half)) {
+    corr_backward_body<CorrF16, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr);
+}
+#undef CORR_BACKWARD_ARGS
 
 // Backward for PWC-Net's configuration (k == 1, strides 1, pad == md == 4; round 3).  corr_backward above is one thread per
 // gradient element: 81 loads of gradOutput + 81 of the other map + 81 multiply-adds each, and a gradOutput element is
@@ -818,13 +777,13 @@ template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward_k1(
     const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
     int channel, int h, int w, int groups, int ch_per_group) {
-    constexpr int MD = 4, D = 2 * MD + 1, OC = D * D, TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;
-    __shared__ float win[2][LH][LW];
+    typedef CorrBwdTile T;
+    constexpr int MD = T::MD, D = T::D, OC = T::OC;
+    __shared__ float win[2][T::LH][T::LW];
+    const T t(channel, groups, ch_per_group);
     const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    const int bx = x0 + px, by = y0 + py;
-    const int n = blockIdx.z / groups, cg = blockIdx.z - n * groups;
-    const int c_begin = cg * ch_per_group, c_end = min(channel, c_begin + ch_per_group);
+    const int bx = t.x0 + px, by = t.y0 + py;
+    const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
     const bool in = bx < w && by < h;
     const int64_t plane = (int64_t)h * w;
     const float* go = gout + (int64_t)n * OC * plane;
@@ -841,10 +800,9 @@ __global__ __launch_bounds__(256) void corr_backward_k1(
 
     auto stage = [&](int c, int buf) {
         const float* of = other + ((int64_t)n * channel + c) * plane;
-        for (int e = tid; e < LH * LW; e += 256) {
-            const int r = e / LW, col = e - r * LW;
-            const int gy = y0 - MD + r, gx = x0 - MD + col;
-            win[buf][r][col] = (gy >= 0 && gy < h && gx >= 0 && gx < w) ? of[(int64_t)gy * w + gx] : 0.0f;
+        for (int e = tid; e < T::LH * T::LW; e += 256) {
+            const T::Elem p = t.window(e);
+            win[buf][p.r][p.col] = (p.gy >= 0 && p.gy < h && p.gx >= 0 && p.gx < w) ? of[(int64_t)p.gy * w + p.gx] : 0.0f;
         }
     };
     if (c_begin >= c_end) return;
@@ -870,75 +828,6 @@ __global__ __launch_bounds__(256) void corr_backward_k1(
     }
 }
 
-// The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541).
-// The terms, windows and skips are corr_backward's; the arithmetic is at::Half's, which goes through float and rounds back to
-// half after every operation: p = half(g * v), the 32 partials `__shared__ scalar_t prod_sum[32]` accumulate IN HALF,
-// r = half(r + s_l) for l = 0..31, gin = half(r / nelems_h) with nelems_h = half(k*k*C) (not the exact count above 2048).
-// float32 has 24 >= 2*11 + 2 significand bits, so float-then-round is the correctly rounded half operation: the products and
-// sums here are plain v_mul_f16 / v_add_f16 (never fused: -ffp-contract=off, no fma written), and the one division is done in
-// float on the two widened halves and rounded once.  A term whose other-map tap lies in the zero padding is NOT skipped: it
-// adds half(g * 0), which is NaN when g is inf or NaN.
-__device__ __forceinline__ __half corr_mean_f16(__half r, float nelems_h) {
-    float rf = __half2float(r);
-    asm volatile("" : "+v"(rf));        // (keeps the widening a v_cvt: nothing mixed-precision may be folded into the division)
-    return __float2half_rn(rf / nelems_h);
-}
-
-// any pad / k / md / stride2, stride1 == 1: one thread per gradient element
-template <bool SECOND>
-__global__ __launch_bounds__(256) void corr_backward_f16(
-    const __half* __restrict__ other, const __half* __restrict__ gout, __half* __restrict__ gin,
-    int batch, int channel, int h, int w, int oc, int oh, int ow,
-    int pad, int kr, int md, int s2, int dr) {
-    const int64_t total = (int64_t)batch * channel * h * w;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= total) return;
-    const int bx = (int)(gid % w);
-    const int by = (int)((gid / w) % h);
-    const int c = (int)((gid / ((int64_t)w * h)) % channel);
-    const int n = (int)(gid / ((int64_t)w * h * channel));
-    const int dsz = 2 * dr + 1;
-    const int y = by + pad, x = bx + pad;                   // padded coordinates
-    const __half* of = other + ((int64_t)n * channel + c) * h * w;
-    const __half* go = gout + (int64_t)n * oc * oh * ow;
-    const __half zero = __float2half_rn(0.0f);
-    const float nelems_h = __half2float(__float2half_rn((float)((2 * kr + 1) * (2 * kr + 1) * channel)));
-    bool any = SECOND;
-    if constexpr (!SECOND) {
-        const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
-        any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
-    }
-    if (!any) {
-        gin[gid] = zero;        // the binding zero-fills gradInput (correlation_cuda.cc:112-113)
-        return;
-    }
-    __half r = zero;
-    for (int l = 0; l < 32; ++l) {
-        __half s = zero;
-        for (int tc = l; tc < oc; tc += 32) {
-            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
-            int xmin, ymin, xmax, ymax, vy, vx;
-            if constexpr (SECOND) {
-                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
-                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
-                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
-                vy = y - j2 - pad; vx = x - i2 - pad;
-            } else {
-                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
-                vy = y + j2 - pad; vx = x + i2 - pad;
-            }
-            const __half val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? of[(int64_t)vy * w + vx] : zero;
-            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
-            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
-            const __half* g = go + (int64_t)tc * oh * ow;
-            for (int j = ymin; j <= ymax; ++j)
-                for (int i = xmin; i <= xmax; ++i) s = __hadd(s, __hmul(g[(int64_t)j * ow + i], val));
-        }
-        r = __hadd(r, s);
-    }
-    gin[gid] = corr_mean_f16(r, nelems_h);
-}
-
 // PWC-Net's configuration (k == 1, strides 1, pad == md == 4), modelled on corr_backward_k1: a workgroup owns 64x4 pixels and
 // stages the other map's 12x72 window per channel in LDS (double-buffered, zero padded); a lane owns TWO horizontally adjacent
 // pixels, whose 81 gradOutput values are 81 packed-half registers for all channels of the group.  Per channel a term is one
@@ -951,13 +840,13 @@ template <bool SECOND>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void corr_backward_k1_f16(
     const __half* __restrict__ other, const __half* __restrict__ gout, __half* __restrict__ gin,
     int channel, int h, int w, int groups, int ch_per_group) {
-    constexpr int MD = 4, D = 2 * MD + 1, OC = D * D, TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD, NT = 128;
-    __shared__ __attribute__((aligned(16))) __half win[2][LH][LW];
+    typedef CorrBwdTile T;
+    constexpr int MD = T::MD, D = T::D, OC = T::OC;
+    __shared__ __attribute__((aligned(16))) __half win[2][T::LH][T::LW];
+    const T t(channel, groups, ch_per_group);
     const int tid = threadIdx.x, px = 2 * (tid & 31), py = tid >> 5;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    const int bx = x0 + px, by = y0 + py;
-    const int n = blockIdx.z / groups, cg = blockIdx.z - n * groups;
-    const int c_begin = cg * ch_per_group, c_end = min(channel, c_begin + ch_per_group);
+    const int bx = t.x0 + px, by = t.y0 + py;
+    const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
     const bool in0 = bx < w && by < h, in1 = bx + 1 < w && by < h;
     const int64_t plane = (int64_t)h * w;
     const __half* go = gout + (int64_t)n * OC * plane;
@@ -985,11 +874,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void c
 
     auto stage = [&](int c, int buf) {
         const auto od = buffer_rsrc(other + ((int64_t)n * channel + c) * plane, (int)(plane * 2));
-        for (int e = tid; e < LH * LW; e += NT) {
-            const int r = e / LW, col = e - r * LW;
-            const int gy = y0 - MD + r, gx = x0 - MD + col;
-            const bool ok = gy >= 0 && gy < h && gx >= 0 && gx < w;
-            win[buf][r][col] = __ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(od, ok ? 2u * (unsigned)(gy * w + gx) : 0x80000000u, 0, 0));
+        for (int e = tid; e < T::LH * T::LW; e += 128) {
+            const T::Elem p = t.window(e);
+            const bool ok = p.gy >= 0 && p.gy < h && p.gx >= 0 && p.gx < w;
+            win[buf][p.r][p.col] = __ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(od, ok ? 2u * (unsigned)(p.gy * w + p.gx) : 0x80000000u, 0, 0));
         }
     };
     stage(c_begin, 0);
@@ -1053,18 +941,50 @@ extern "C" int vfi_correlation_output_dims(int h, int w, int pad_size, int kerne
     return VFI_OK;
 }
 
+// The checks every entry makes before it launches, in this order: a positive shape, no null tensor, valid parameters, and
+// at least one output pixel; the output dimensions come back.  (The reference's backward indexes gradInput rows by
+// blockIdx * stride1 and leaves the tensor for stride1 > 1: only stride1 == 1 is defined.)
+static int corr_check(std::initializer_list<const void*> tensors, int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                      int max_displacement, int stride1, int stride2, bool backward, int* oc, int* oh, int* ow) {
+    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
+    for (const void* t : tensors)
+        if (!t) return VFI_ERR_SHAPE;
+    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, oc, oh, ow))
+        return VFI_ERR_SHAPE;
+    if ((backward && stride1 != 1) || *oh <= 0 || *ow <= 0) return VFI_ERR_SHAPE;
+    return VFI_OK;
+}
+
+// The tiled backward kernels' split of the channels into groups over blockIdx.z, so that a small level fills the chip
+// (about 2048 workgroups); the group count comes back, 0 where batch * groups does not fit a grid.
+static int corr_backward_groups(int tiles, int batch, int channel, int* ch_per_group) {
+    int groups = (int)std::min<int64_t>(channel, std::max<int64_t>(1, (2048 + (int64_t)tiles * batch - 1) / ((int64_t)tiles * batch)));
+    *ch_per_group = (channel + groups - 1) / groups;
+    groups = (channel + *ch_per_group - 1) / *ch_per_group;
+    return (int64_t)batch * groups <= 65535 ? groups : 0;
+}
+
+// both gradients: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
+template <class K, class T, class... Rest>
+static int corr_launch_both(K first, K second, dim3 grid, dim3 block, hipStream_t st, const T* input1, const T* input2, const T* gradoutput,
+                            T* gradinput1, T* gradinput2, Rest... rest) {
+    hipLaunchKernelGGL(first, grid, block, 0, st, input2, gradoutput, gradinput1, rest...);
+    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
+    hipLaunchKernelGGL(second, grid, block, 0, st, input1, gradoutput, gradinput2, rest...);
+    return launch_status();
+}
+
 // one call, or two calls of equal shape (nitems == 2) in one launch
 static int correlation_forward_items(const float* const* in1s, const float* const* in2s, float* const* outs, int nitems, int per,
                                      int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
                                      int stride1, int stride2, vfi_stream_t stream) {
     int oc, oh, ow;
-    if (nitems < 1 || nitems > 2 || per <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
-    for (int i = 0; i < nitems; ++i)
-        if (!in1s[i] || !in2s[i] || !outs[i]) return VFI_ERR_SHAPE;
-    if (nitems == 2 && outs[0] == outs[1]) return VFI_ERR_SHAPE;
-    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow))
+    if (nitems < 1 || nitems > 2) return VFI_ERR_SHAPE;
+    const int last = nitems - 1;
+    if (corr_check({in1s[0], in2s[0], outs[0], in1s[last], in2s[last], outs[last]}, per, channel, h, w, pad_size, kernel_size,
+                   max_displacement, stride1, stride2, false, &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
-    if (oh <= 0 || ow <= 0) return VFI_ERR_SHAPE;
+    if (nitems == 2 && outs[0] == outs[1]) return VFI_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int batch = nitems * per;                          // images of the launch
     CorrItems items;
@@ -1150,10 +1070,9 @@ extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input
                                             int h, int w, int pad_size, int kernel_size, int max_displacement,
                                             int stride1, int stride2, vfi_stream_t stream) {
     int oc, oh, ow;
-    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || !input1 || !input2 || !output) return VFI_ERR_SHAPE;
-    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow))
+    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
+                   &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
-    if (oh <= 0 || ow <= 0) return VFI_ERR_SHAPE;
     const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
     const int64_t total = (int64_t)batch * oc * oh * ow;
     if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
@@ -1177,83 +1096,57 @@ extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input
     return launch_status();
 }
 
+// float, or the reference's at::Half instantiation
+template <class T>
+static int correlation_backward_any(const T* input1, const T* input2, const T* gradoutput, T* gradinput1, T* gradinput2, int batch,
+                                    int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
+                                    int stride2, vfi_stream_t stream) {
+    constexpr bool HALF = std::is_same<T, __half>::value;
+    int oc, oh, ow;
+    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                   stride1, stride2, true, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    const int64_t total = (int64_t)batch * channel * h * w;
+    if (HALF && (total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
+        // PWC-Net's configuration: the pixel-owns-its-gradOutput kernels; channel groups over blockIdx.z fill the chip.
+        // (The half kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.)
+        int ch_per_group;
+        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
+        if (groups && (!HALF || (int64_t)81 * h * w * 2 < INT_MAX)) {
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
+            if constexpr (HALF)
+                return corr_launch_both(corr_backward_k1_f16<false>, corr_backward_k1_f16<true>, grid, dim3(128), st, input1, input2,
+                                        gradoutput, gradinput1, gradinput2, channel, h, w, groups, ch_per_group);
+            else
+                return corr_launch_both(corr_backward_k1<false>, corr_backward_k1<true>, grid, dim3(256), st, input1, input2,
+                                        gradoutput, gradinput1, gradinput2, channel, h, w, groups, ch_per_group);
+        }
+    }
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if constexpr (HALF)
+        return corr_launch_both(corr_backward_f16<false>, corr_backward_f16<true>, grid, block, st, input1, input2, gradoutput, gradinput1,
+                                gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    else
+        return corr_launch_both(corr_backward<false>, corr_backward<true>, grid, block, st, input1, input2, gradoutput, gradinput1,
+                                gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+}
+
 extern "C" int vfi_correlation_backward(const float* input1, const float* input2, const float* gradoutput,
                                          float* gradinput1, float* gradinput2, int batch, int channel, int h, int w,
                                          int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                          vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
-    if (!input1 || !input2 || !gradoutput || !gradinput1 || !gradinput2) return VFI_ERR_SHAPE;
-    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    // the reference's backward indexes gradInput rows by blockIdx*stride1 and leaves
-    // the tensor for stride1 > 1: only stride1 == 1 is defined
-    if (stride1 != 1 || oh <= 0 || ow <= 0) return VFI_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
-        // PWC-Net's configuration: the pixel-owns-its-gradOutput kernel; channel groups over blockIdx.z fill the chip
-        const int tiles = ((w + 63) / 64) * ((h + 3) / 4);
-        int groups = (int)std::min<int64_t>(channel, std::max<int64_t>(1, (2048 + (int64_t)tiles * batch - 1) / ((int64_t)tiles * batch)));
-        const int ch_per_group = (channel + groups - 1) / groups;
-        groups = (channel + ch_per_group - 1) / ch_per_group;
-        if ((int64_t)batch * groups <= 65535) {
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            hipLaunchKernelGGL(corr_backward_k1<false>, grid, dim3(256), 0, st, input2, gradoutput, gradinput1, channel, h, w, groups, ch_per_group);
-            if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-            hipLaunchKernelGGL(corr_backward_k1<true>, grid, dim3(256), 0, st, input1, gradoutput, gradinput2, channel, h, w, groups, ch_per_group);
-            return launch_status();
-        }
-    }
-    const int64_t total = (int64_t)batch * channel * h * w;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipLaunchKernelGGL(corr_backward<false>, grid, block, 0, st, input2, gradoutput, gradinput1, batch, channel, h, w,
-                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    hipLaunchKernelGGL(corr_backward<true>, grid, block, 0, st, input1, gradoutput, gradinput2, batch, channel, h, w,
-                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    return launch_status();
+    return correlation_backward_any(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                    max_displacement, stride1, stride2, stream);
 }
 
 extern "C" int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,
                                              void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
                                              int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                              vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
-    if (!input1 || !input2 || !gradoutput || !gradinput1 || !gradinput2) return VFI_ERR_SHAPE;
-    if (vfi_correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (stride1 != 1 || oh <= 0 || ow <= 0) return VFI_ERR_SHAPE;      // (as vfi_correlation_backward)
-    const int64_t total = (int64_t)batch * channel * h * w;
-    if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const __half* in1 = (const __half*)input1;
-    const __half* in2 = (const __half*)input2;
-    const __half* go = (const __half*)gradoutput;
-    __half* g1 = (__half*)gradinput1;
-    __half* g2 = (__half*)gradinput2;
-    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
-        // PWC-Net's configuration: the tiled kernel, channel groups over blockIdx.z as in vfi_correlation_backward
-        const int tiles = ((w + 63) / 64) * ((h + 3) / 4);
-        int groups = (int)std::min<int64_t>(channel, std::max<int64_t>(1, (2048 + (int64_t)tiles * batch - 1) / ((int64_t)tiles * batch)));
-        const int ch_per_group = (channel + groups - 1) / groups;
-        groups = (channel + ch_per_group - 1) / ch_per_group;
-        // (the kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB)
-        if ((int64_t)batch * groups <= 65535 && (int64_t)81 * h * w * 2 < INT_MAX) {
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            hipLaunchKernelGGL(corr_backward_k1_f16<false>, grid, dim3(128), 0, st, in2, go, g1, channel, h, w, groups, ch_per_group);
-            if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-            hipLaunchKernelGGL(corr_backward_k1_f16<true>, grid, dim3(128), 0, st, in1, go, g2, channel, h, w, groups, ch_per_group);
-            return launch_status();
-        }
-    }
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipLaunchKernelGGL(corr_backward_f16<false>, grid, block, 0, st, in2, go, g1, batch, channel, h, w,
-                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    hipLaunchKernelGGL(corr_backward_f16<true>, grid, block, 0, st, in1, go, g2, batch, channel, h, w,
-                       oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    return launch_status();
+    return correlation_backward_any((const __half*)input1, (const __half*)input2, (const __half*)gradoutput, (__half*)gradinput1,
+                                    (__half*)gradinput2, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
+                                    stride2, stream);
 }

@@ -1,0 +1,91 @@
+// correlation_dev.h -- the pieces the correlation kernels share (correlation.hip, warp_correlation.hip): which image of a
+// launch a workgroup works on, the staging plan in aligned units, the 32x4 tile with two pixels per lane, the mean of the
+// running sums, and the tile of the tiled backward kernels.  Internal to the library.
+#pragma once
+#include "vfi_common.h"
+
+namespace vfi {
+
+#define CORR_CC_ROWS 8   // channels staged per LDS fill by the wave-per-displacement-row kernels (16 measured the same: their chunk loop is LDS-bound, one workgroup per CU)
+
+// The tensors of a launch: one call, or two calls of equal shape in one launch (both flow directions of a pyramid level: at
+// the coarse levels a launch is latency, 13-18 us for 1 MB, and two cost what one does).  Images 0 .. per - 1 are item 0's.
+struct CorrItems { const float* in1[2]; const float* in2[2]; float* out[2]; int per; };
+
+// Image `img` of a launch: the item it belongs to and its index `b` inside that item.  A kernel indexes its own `items`
+// argument with `item` and binds the three pointers to __restrict__ locals: handing `items` to a helper takes the
+// argument's address, and the compiler then loads all six pointers and selects, instead of the three at `item`.
+struct CorrImage { int item, b; };
+__device__ __forceinline__ CorrImage corr_image(int img, int per) {
+    const int item = img >= per ? 1 : 0;                    // (two calls in one launch: vfi_correlation_forward_pair)
+    return {item, img - item * per};
+}
+
+// Staging plan in aligned units of four elements of EB bytes: unit e = tid + k * NT of a chunk's [CC][ROWS][UW] block whose
+// rows start at frame position (y0, x0), x0 and w multiples of 4 (so a unit lies wholly inside or wholly outside the frame),
+// as a byte offset from the chunk's first plane.  The loads are buffer loads through a descriptor that spans exactly the
+// chunk's planes: a unit outside the frame gets an offset out of any range, a channel past the last one falls out of the
+// descriptor's, and both arrive as zeros.
+template <unsigned EB, int CC, int ROWS, int UW, int NT, int N>
+__device__ __forceinline__ void corr_unit_plan(unsigned (&off)[N], int tid, int y0, int x0, int h, int w, int plane) {
+    static_assert(N == (CC * ROWS * UW + NT - 1) / NT, "units per thread");
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const int e = tid + k * NT;
+        const int c = e / (ROWS * UW), rem = e - c * (ROWS * UW);
+        const int r = rem / UW, col = 4 * (rem - r * UW);
+        const int gy = y0 + r, gx = x0 + col;
+        const bool ok = e < CC * ROWS * UW && gy >= 0 && gy < h && gx >= 0 && gx < w;
+        off[k] = ok ? EB * (unsigned)(c * plane + gy * w + gx) : 0x80000000u;
+    }
+}
+
+// The 32x4 tile of output pixels with one wave per displacement row (threadIdx.y = tj) and TWO horizontally adjacent pixels
+// per lane: per channel a lane reads the D + 1 window values its two D-wide displacement rows share as (D + 1) / 2 aligned
+// pairs.
+template <int MD_>
+struct CorrTile2 {
+    static constexpr int MD = MD_, D = 2 * MD + 1, TW = 32, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD, NT = 64 * D, CC = CORR_CC_ROWS;
+    static constexpr int UW = LW / 4, NU = CC * LH * UW, NPT = (NU + NT - 1) / NT;    // window units of four elements per chunk, per thread
+    static constexpr int FU = CC * TH * (TW / 4), NF1 = (FU + NT - 1) / NT;           // ... of the first map
+    static constexpr int PAIRS = (D + 1) / 2;
+    static __device__ __forceinline__ int px(int lane) { return 2 * (lane & 15); }
+    static __device__ __forceinline__ int py(int lane) { return lane >> 4; }
+    // the pairs at window row `row` from column px on (P: float2-like or __half2)
+    template <class P, class E>
+    static __device__ __forceinline__ void read_row(const E* row, P (&r)[PAIRS]) {
+#pragma unroll
+        for (int k = 0; k < PAIRS; ++k) r[k] = reinterpret_cast<const P*>(row)[k];
+    }
+};
+
+// The mean of the running sums, handed to `store` as a function of one sum: a product with the exact reciprocal for a
+// power-of-two channel count (the same real number), a division otherwise.
+template <class Store>
+__device__ __forceinline__ void corr_store_mean(int channel, Store&& store) {
+    const float nelems = (float)channel;
+    const float inv = 1.0f / nelems;
+    if ((channel & (channel - 1)) == 0) store([&](float v) { return v * inv; });
+    else store([&](float v) { return v / nelems; });
+}
+
+// The tile of the tiled backward kernels (PWC-Net's configuration: k == 1, strides 1, pad == md == 4): a workgroup owns 64x4
+// pixels of one image and one channel group, and stages the other map's window (tile + 4 halo, zero padded) per channel.
+struct CorrBwdTile {
+    static constexpr int MD = 4, D = 2 * MD + 1, OC = D * D, TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;
+    int x0, y0, n, c_begin, c_end;
+    __device__ __forceinline__ CorrBwdTile(int channel, int groups, int ch_per_group) {
+        x0 = blockIdx.x * TW; y0 = blockIdx.y * TH;
+        n = blockIdx.z / groups;
+        c_begin = (blockIdx.z - n * groups) * ch_per_group;
+        c_end = min(channel, c_begin + ch_per_group);
+    }
+    // window element e: its row and column in the window and its position in the frame (outside it: the zero padding)
+    struct Elem { int r, col, gy, gx; };
+    __device__ __forceinline__ Elem window(int e) const {
+        const int r = e / LW, col = e - r * LW;
+        return {r, col, y0 - MD + r, x0 - MD + col};
+    }
+};
+
+}  // namespace vfi
