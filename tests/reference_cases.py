@@ -206,6 +206,13 @@ def cases(extra=False):
         c["x_interp"], c["x_interpch"] = Case("interp", i), Case("interpch", i)
         s = _sep_inputs(rng, 2, 3, 20, 40, 5)
         c["x_sepconv"], c["x_sepconvflow"] = Case("sepconv", s), Case("sepconvflow", s)
+        # the correlation forward on non-finite, overflowing and subnormal features (tests/corr_edges.py): what the
+        # reference's zero-padded buffers make of an infinity next to the frame edge
+        from tests import corr_edges
+        f1, f2, _ = corr_edges.plant(rng, 2, 5, 6, 13, f32)
+        c["x_corr_planted"] = Case("corr_planted", dict(f1=f1, f2=f2), cfg=pwc)
+        # pad 8: the output origin lies outside the frame, so the FIRST map's tap meets the padding too (0 * inf)
+        c["x_corr_planted_pad8"] = Case("corr_planted", dict(f1=f1, f2=f2), cfg=(8, 1, 4, 1, 1))
     return c
 
 
@@ -304,6 +311,8 @@ def run_ref(R, case, given=None):
         o["out"], o["mask"] = R.correlation_fwd(i["f1"], i["f2"], *cfg, canvas=True)
         if cfg[3] == 1:     # stride1 > 1: the reference's backward writes outside gradInput (not run)
             o["g1"], o["g2"], (o["mask1"], o["mask2"]) = R.correlation_bwd(i["f1"], i["f2"], i["gout"], *cfg, canvas=True)
+    elif op == "corr_planted":
+        o["out"] = R.correlation_fwd(i["f1"], i["f2"], *p["cfg"])      # (NaN is a result here: no canvas mask)
     else:
         raise KeyError(op)
     return o
@@ -354,6 +363,8 @@ def run_oracle(O, case, ref):
         o["out"] = O.correlation_fwd(i["f1"], i["f2"], *cfg, order=0, fmad=0)
         if cfg[3] == 1:
             o["g1"], o["g2"] = O.correlation_bwd(i["f1"], i["f2"], i["gout"], *cfg, fmad=0)
+    elif op == "corr_planted":
+        o["out"] = O.correlation_fwd(i["f1"], i["f2"], *p["cfg"], order=0, fmad=0)
     else:
         raise KeyError(op)
     return o
@@ -434,6 +445,22 @@ def check_gaps(name, case, ref):
 
 def check(name, case, ref_raster, got, ref_blocks=None):
     """`got` (the oracle) against the executor's raster-order outputs and, when given, its block-order outputs."""
+    if case.op == "corr_planted":
+        # NaN and infinity are the expected results: NaN masks equal, everything else bit for bit, in both thread orders;
+        # and the reference does turn a non-finite value that meets its padding into NaN
+        from tests import corr_edges
+        want = ref_raster["out"]
+        cfg = case.params["cfg"]
+        sites1, sites2 = corr_edges.padding_sites(case.inputs["f1"], case.inputs["f2"], cfg)
+        assert sites1.any() and np.isnan(want[sites1]).all(), (name, "inf * 0 of the padding")
+        # (a first-map tap in the padding needs an output origin outside the frame: pad > max_displacement)
+        assert sites2.any() == (cfg[0] > cfg[2]) and np.isnan(want[sites2]).all(), (name, "0 * inf of the padding")
+        assert np.isinf(want).any() and np.isfinite(want).mean() >= 0.75, name
+        if ref_blocks is not None:
+            assert corr_edges.same_bits_nan_aware(ref_blocks["out"], want), (name, "the executor's two orders differ")
+        assert corr_edges.same_bits_nan_aware(got["out"], want), (name, "oracle != reference",
+                                                                  corr_edges.describe_difference(got["out"], want))
+        return
     scatter = SCATTER.get(case.op, {})
     check_masks(case, ref_raster)
     check_gaps(name, case, ref_raster)

@@ -465,6 +465,12 @@ template __global__ void corr_forward_k1_quad<4>(CorrItems, int, int, int, int, 
 // channels): one thread per output element, x fastest, so a wave reads 64 consecutive pixels of each
 // map; eight channels in flight per thread.  A tiled kernel leaves most of the chip idle here (10
 // workgroups for 18x31).  Sequential channel order, as everywhere.
+//
+// A tap outside the frame is a zero of the reference's padded buffers, and the reference multiplies it
+// (correlation_cuda_kernel.cu:66-69, :124): with one tap inside, a * 0 per channel -- +0 in the sum unless a is infinite or
+// NaN, then NaN.  Such a lane runs the same loop: its outside tap is read at the inside tap's pixel (a valid address) and
+// `keep` clears what was read.  (A loop of its own for these lanes would run in nearly every wave, after the other one; and
+// reading the inside tap's own address twice instead doubled this kernel's time at 196 x 18 x 31.  Both measured: DESIGN.md 4.3.)
 template <int MD>
 __global__ __launch_bounds__(256) void corr_forward_k1_flat(
     CorrItems items, int batch, int channel, int h, int w, int oh, int ow, int org) {
@@ -483,20 +489,26 @@ __global__ __launch_bounds__(256) void corr_forward_k1_flat(
     float* __restrict__ out = items.out[im.item];
     const int y1 = oy + org, x1 = ox + org;
     const int y2 = y1 + tc / D - MD, x2 = x1 + tc % D - MD;
+    const bool ok1 = y1 >= 0 && y1 < h && x1 >= 0 && x1 < w, ok2 = y2 >= 0 && y2 < h && x2 >= 0 && x2 < w;
     float acc = 0.0f;
-    if (y1 >= 0 && y1 < h && x1 >= 0 && x1 < w && y2 >= 0 && y2 < h && x2 >= 0 && x2 < w) {     // else zero padding
+    if (ok1 || ok2) {                                                                           // else zero padding on both sides: +0
         const int64_t plane = (int64_t)h * w;
-        const float* p1 = in1 + (int64_t)b * channel * plane + (int64_t)y1 * w + x1;
-        const float* p2 = in2 + (int64_t)b * channel * plane + (int64_t)y2 * w + x2;
+        // pa: the tap inside the frame (the first map's where both are), pv: the other tap, where it is outside a valid
+        // address whose value `keep` turns into the padding's zero (the product commutes)
+        const int64_t at1 = (int64_t)y1 * w + x1, at2 = (int64_t)y2 * w + x2;
+        const float* pa = (ok1 ? in1 : in2) + (int64_t)b * channel * plane + (ok1 ? at1 : at2);
+        const float* pv = (ok1 ? in2 : in1) + (int64_t)b * channel * plane + (ok2 ? at2 : at1);
+        const unsigned keep = (ok1 && ok2) ? ~0u : 0u;
+        auto tap = [&](int c) { return __uint_as_float(__float_as_uint(pv[(int64_t)c * plane]) & keep); };
         int c = 0;
         for (; c + 8 <= channel; c += 8) {
             float a[8], v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { a[k] = p1[(int64_t)(c + k) * plane]; v[k] = p2[(int64_t)(c + k) * plane]; }
+            for (int k = 0; k < 8; ++k) { a[k] = pa[(int64_t)(c + k) * plane]; v[k] = tap(c + k); }
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc = fmaf(a[k], v[k], acc);
         }
-        for (; c < channel; ++c) acc = fmaf(p1[(int64_t)c * plane], p2[(int64_t)c * plane], acc);
+        for (; c < channel; ++c) acc = fmaf(pa[(int64_t)c * plane], tap(c), acc);
     }
     out[gid - (int64_t)im.item * items.per * D * D * oh * ow] = acc / (float)channel;
 }
@@ -644,19 +656,27 @@ __global__ __launch_bounds__(256) void corr_forward_generic_f16(
     for (int j = -kr; j <= kr; ++j)
         for (int i = -kr; i <= kr; ++i) {
             const int ya = y1 + j, xa = x1 + i, yb = y2 + j, xb = x2 + i;
-            // a tap outside either map multiplies a zero of the padding: +0 for every channel
-            if (ya < 0 || ya >= h || xa < 0 || xa >= w || yb < 0 || yb >= h || xb < 0 || xb >= w) continue;
-            const __half* pa = f1 + (int64_t)ya * w + xa;
-            const __half* pb = f2 + (int64_t)yb * w + xb;
+            // a tap outside a map is a zero of the reference's padded buffer.  Outside both: +0 for every channel, skipped.
+            // Inside one: half(a * 0) per channel, +-0 unless a is infinite or NaN -- then NaN; the lane runs the same loop, its
+            // outside tap read at the inside tap's pixel (a valid address) and cleared by `keep` (the product commutes).  (A
+            // loop of their own for these lanes, and a second pass of workgroups for them, were built and measured slower than
+            // this at the 1080p pyramid's half levels -- nearly every wave holds such a lane: DESIGN.md 4.3, padding taps.)
+            const bool oka = ya >= 0 && ya < h && xa >= 0 && xa < w, okb = yb >= 0 && yb < h && xb >= 0 && xb < w;
+            if (!oka && !okb) continue;
+            const int64_t ata = (int64_t)ya * w + xa, atb = (int64_t)yb * w + xb;
+            const __half* pa = (oka ? f1 : f2) + (oka ? ata : atb);
+            const __half* pb = (oka ? f2 : f1) + (okb ? atb : ata);
+            const unsigned short keep = (oka && okb) ? 0xffffu : 0u;
+            auto tap = [&](int c) { return __ushort_as_half((unsigned short)(__half_as_ushort(pb[(int64_t)c * plane]) & keep)); };
             int c = 0;
             for (; c + 8 <= channel; c += 8) {
                 __half va[8], vb[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { va[q] = pa[(int64_t)(c + q) * plane]; vb[q] = pb[(int64_t)(c + q) * plane]; }
+                for (int q = 0; q < 8; ++q) { va[q] = pa[(int64_t)(c + q) * plane]; vb[q] = tap(c + q); }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) acc += __half2float(__hmul(va[q], vb[q]));
             }
-            for (; c < channel; ++c) acc += __half2float(__hmul(pa[(int64_t)c * plane], pb[(int64_t)c * plane]));
+            for (; c < channel; ++c) acc += __half2float(__hmul(pa[(int64_t)c * plane], tap(c)));
         }
     const int k = 2 * kr + 1;
     out[gid] = __float2half_rn(acc / (float)(k * k * channel));
