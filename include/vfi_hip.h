@@ -78,6 +78,23 @@ int vfi_filterinterp_forward_ori_multi(const float* input1, const float* const* 
                                        vfi_strides s1, vfi_strides s2, vfi_strides s3,
                                        vfi_stream_t stream);
 
+/* The backward of that call as the context path needs it (networks/DAIN.py:544-552, networks/DAIN_slowmotion.py:311-317
+ * detach flow and filter): gradinput1 = the sum over t < nflows of the IMAGE gradient of
+ * vfi_filterinterp_forward_ori(., flows[t], input3) for gradoutputs[t].  The image itself is not an argument: its gradient
+ * depends on the flow, the filter and the incoming gradient only.  No flow or filter gradient is formed.
+ * gradinput1 is WRITTEN, every element (+0 where no tap lands): it need not arrive zeroed.  An invalid pixel contributes
+ * nothing (filterinterpolation_cuda_kernel.cu:2863-2864).  Deterministic (one fixed-point accumulation over all flows, one
+ * scale from the largest |gradient| of all of them and the largest |filter tap|; a cell may take all filter_channels x nflows
+ * taps of every pixel); for nflows == 1 bit for bit gradinput1 of vfi_filterinterp_backward_ori on a zero-filled buffer.
+ * Non-finite inputs: the reference's fp32 atomics, as there.
+ * flows / gradoutputs: HOST arrays of nflows device pointers, every entry non-null; every flow has strides s2, every
+ * gradoutput sg, gradinput1 s1.  Scratch: 8 bytes per element of gradinput1 (the per-stream workspace). */
+int vfi_filterinterp_backward_ori_image_multi(const float* const* flows, const float* input3,
+                                              const float* const* gradoutputs, float* gradinput1, int nflows,
+                                              int batch, int channel, int h, int w, int filter_channels,
+                                              vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
+                                              vfi_stream_t stream);
+
 /* fp16 STORAGE, fp32 arithmetic (BASELINE.json configs[2]): input1 and output are IEEE
  * half tensors (strides in half elements), flow and filter stay float32.  The result is the fp32
  * result of the function above on the widened inputs, rounded to half once; the LDS-staged path

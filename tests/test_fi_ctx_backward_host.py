@@ -1,0 +1,286 @@
+"""CPU checks of the context warp's backward (vfi_filterinterp_backward_ori_image_multi) and of tests/fi_ctx_backward.py:
+
+  * the header declares the entry point, libvfi_hip.so exports it, cabi knows its 15 arguments, and argument errors return 1
+    without a GPU;
+  * the mirror's constants and decision expressions are the new source's, hand-worked boxes sit on either side of every
+    threshold, and the kernels hold no scratch;
+  * the builder's fields send every label through a tile of every batch item, for 1, 2 and 3 flows;
+  * the restatement composes (one flow: bwd_tiles.predict_image_grad bit for bit), equals the C oracle's per-flow gradients
+    summed in float64 bit for bit on dyadic inputs, and stays within the float64 bound on random ones;
+  * fused.FilterInterpolate_ctx_all reaches its autograd Function only when a context tensor can train, and the Function
+    hands the live gradients and their flows to ONE backward call (launches stubbed).
+"""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from tests import bwd_tiles as bt
+from tests import fi_ctx_backward as fc
+from tests.fi_windows import source
+
+f32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "video-frame-interpolation-based-on-deformable-kernel-region_amd", "csrc")
+NAME = "vfi_filterinterp_backward_ori_image_multi"
+
+
+@pytest.fixture(scope="module")
+def built():
+    import vfidkr_amd  # noqa: F401
+    from vfidkr_amd import build
+    build.build_all()
+    return build
+
+
+def test_header_declares_and_library_exports_the_entry_point(built):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vfi_hip.h")).read(), flags=re.S)
+    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % NAME, text)
+    assert m
+    lib = ctypes.CDLL(built.LIB_PATH)
+    assert hasattr(lib, NAME)
+    from vfidkr_amd import cabi
+    assert len(cabi.SIGNATURES[NAME]) == len(m.group(1).split(",")) == 15
+    assert callable(cabi.filterinterp_backward_ori_image_multi)
+
+
+def test_argument_errors_return_1_without_a_gpu(built):
+    from vfidkr_amd import cabi
+    f = getattr(cabi.lib(), NAME)
+    s = cabi.Strides(0, 0, 0)
+    p = ctypes.c_void_p(16)                 # never dereferenced: every call below returns before any launch
+    two = (ctypes.c_void_p * 2)(16, 16)
+    hole = (ctypes.c_void_p * 2)(16, None)
+
+    def call(flows=two, filt=p, gouts=two, g1=p, n=2, dims=(1, 3, 8, 8), fcn=16):
+        return f(flows, filt, gouts, g1, n, *dims, fcn, s, s, s, s, None)
+    assert call(flows=None) == 1 and call(gouts=None) == 1 and call(filt=None) == 1 and call(g1=None) == 1
+    assert call(flows=hole) == 1 and call(gouts=hole) == 1
+    assert call(n=0) == 1 and call(n=-1) == 1 and call(fcn=0) == 1
+    for dims in ((0, 3, 8, 8), (1, 0, 8, 8), (1, 3, 0, 8), (1, 3, 8, -1)):
+        assert call(dims=dims) == 1
+
+
+def test_decision_expressions_and_constants_match_the_source():
+    src = " ".join(source(fc.SRC).split())
+    assert (fc.CB_TW, fc.CB_TH, fc.CB_THREADS, fc.CB_CH, fc.CB_CELLS, fc.CB_NT) == (64, 8, 512, 6, 6144, 3)
+    assert "const int pc = min(CB_CH, CB_CELLS / n);" in src
+    assert "if (!gradacc_staged_ok(gctx) || pc == 0) {" in src
+    assert "if (!fi_box_fold(box, tid, lo_x, lo_y, hi_x, hi_y)) return;" in src
+    # the union: every flow's clamped taps widen one box
+    assert "lo_x = min(lo_x, px[t].co[0]); lo_y = min(lo_y, px[t].ro[0]);" in src
+    assert "hi_x = max(hi_x, px[t].co[3]); hi_y = max(hi_y, px[t].ro[3]);" in src
+    # flags: written per 64 x 8 tile of the batch item, found again from the per-tap kernel's 64 x 4 blocks
+    assert src.count("tileflag[(b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = 1;") == 1
+    assert "if (tileflag && !tileflag[(b * ((h + CB_TH - 1) / CB_TH) + y / CB_TH) * gridDim.x + blockIdx.x]) return;" in src
+    # the launcher: channel groups, launches of CB_NT flows, the call's tap count
+    assert ("while (groups < 8 && (int64_t)ntiles * groups < 2 * slots && channel / (groups * 2) >= 4 * CB_CH && "
+            "(int64_t)batch * groups * 2 <= 65535)") in src
+    assert "ch_per_group = ((channel + groups - 1) / groups + CB_CH - 1) / CB_CH * CB_CH;" in src
+    assert "groups = (channel + ch_per_group - 1) / ch_per_group;" in src
+    assert "const int launches = (nflows + CB_NT - 1) / CB_NT;" in src
+    assert "const int64_t taps = (int64_t)(filter_channels > 4 ? filter_channels : 4) * nflows;" in src
+    assert "return gradacc_finish(st, sc.dir[0], gradinput1, batch, channel, h, w, s1, true);" in src
+    # the addends, as the restatement forms them (and as fi_backward_ori4_tile does)
+    assert "__float2ll_rn(qg[quad] * fv[k] * gctx.scale)" in src
+    assert src.count("{ g * (1.0f - alpha) * (1.0f - beta), g * alpha * (1.0f - beta), g * (1.0f - alpha) * beta, g * alpha * beta }") == 1
+    assert "gradacc_add(gp, gfp, (int64_t)cy * w + cx, (int64_t)cy * s1.h + cx, qg[quad] * fv, gctx);" in src
+    assert "const int quad = (T + j > iy ? 2 : 0) + (L + i > ix ? 1 : 0);" in src
+    # nothing of the existing kernels is copied: the shared helpers are called
+    for helper in ("fi_flow_at(", "fi_valid(", "fi_box_clear(", "fi_box_fold(", "gradacc_ctx(", "gradacc_reserve(", "gradacc_scan("):
+        assert helper in src, helper
+
+
+def test_thresholds_on_either_side():
+    last = lambda v: max(n for n in range(1, 7000) if fc.channels(n) == v)
+    assert [last(pc) for pc in (6, 5, 4, 3, 2, 1)] == [1024, 1228, 1536, 2048, 3072, 6144] and fc.channels(6145) == 0
+    assert [fc.channels(n) for n in (1024, 1025, 1228, 1229, 1536, 1537, 2048, 2049, 3072, 3073, 6144, 6145)] == \
+        [6, 5, 5, 4, 4, 3, 3, 2, 2, 1, 1, 0]
+    assert fc.channel_groups(2, 7, 43, 200) == (12, 1) and fc.channel_groups(1, 196, 24, 72) == (30, 7)
+    assert fc.channel_groups(3, 196, 256, 448) == (102, 2) and fc.channel_groups(1, 196, 1152, 1984) == (198, 1)
+
+
+def test_hand_worked_tiles():
+    h, w = 24, 200
+    zero = np.zeros((1, 2, h, w), f32)
+    rec = fc.tiles([zero], 7)
+    assert rec[0, 1, 1]["box"] == (63, 7, 129, 17) and rec[0, 1, 1]["labels"] == {"pc6", "short_pass"}
+    assert fc.tiles([zero], 6)[0, 1, 1]["labels"] == {"pc6"}
+    left, right = zero.copy(), zero.copy()
+    left[0, 0, 8:16, 64:128], right[0, 0, 8:16, 64:128] = -5, 7
+    rec = fc.tiles([left, right], 6)[0, 1, 1]
+    assert rec["boxes"] == [(58, 7, 124, 17), (70, 7, 136, 17)] and rec["box"] == (58, 7, 136, 17)
+    assert rec["labels"] == {"pc6", "union_sides"}
+    gone = zero.copy()
+    gone[0, 0, 8:16, 64:128] = 1000
+    assert fc.tiles([gone, zero, gone], 6)[0, 1, 1]["labels"] == {"pc6", "one_flow"}
+    assert fc.tiles([gone, gone], 6)[0, 1, 1]["labels"] == {"empty"}
+    assert fc.tiles([zero], 6, scale2_one=False)[0, 1, 1]["labels"] == {"flag_call"}
+
+
+def test_kernels_hold_no_scratch(built, tmp_path):
+    """the new unit's device assembly at the launch bound: no scratch instruction, no private segment"""
+    asm = str(tmp_path / "ctx.s")
+    flags = re.search(r"^HIPFLAGS\s*\?=\s*(.*)$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M).group(1)
+    flags = flags.replace("$(ARCH)", "gfx950").split()
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, fc.SRC), "-o", asm], check=True)
+    text = open(asm).read()
+    names = re.findall(r"^(_Z\S*fi_ctx_\S*):", text, flags=re.M)
+    assert len(names) == 3, names
+    for name in names:
+        body = text.split(name + ":", 1)[1].split(".Lfunc_end", 1)[0]
+        assert not re.search(r"^\s*scratch_", body, flags=re.M), name
+        meta = text.split(".amdhsa_kernel " + name, 1)[1].split(".end_amdhsa_kernel", 1)[0]
+        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", meta), name
+
+
+@pytest.mark.parametrize("nflows", [1, 2, 3])
+def test_built_fields_cover_every_label(nflows):
+    flows = fc.build_field(np.random.default_rng(7), 2, 43, 200, nflows)
+    recs = fc.tiles(flows, 7)
+    seen = []
+    for b in range(2):
+        counts = bt.label_counts(recs, b)
+        missing = [lab for lab in fc.all_labels(nflows) if lab not in counts]
+        assert not missing, (nflows, b, missing, counts)
+        seen.append({k[1:]: frozenset(r["labels"]) for k, r in recs.items() if k[0] == b})
+    assert seen[0] != seen[1]               # the two batch items put different classes on the same tiles
+    if nflows > 1:                          # the flows of a recipe tile hit the same cells with different weights
+        k = next(k for k, r in recs.items() if "flag_window" in r["labels"])
+        assert len(set(recs[k]["boxes"])) == 1
+        sl = (slice(k[1] * 8, k[1] * 8 + 8), slice(k[2] * 64, k[2] * 64 + 64))
+        assert not np.array_equal(flows[0][k[0], 0][sl], flows[1][k[0], 0][sl])
+
+
+def _inputs(rng, nflows, fcn=16, dyadic=False, B=2, C=3, h=21, w=70):
+    flows = [rng.uniform(-3, 3, (B, 2, h, w)).astype(f32) for _ in range(nflows)]
+    filt = rng.random((B, fcn, h, w), dtype=f32)
+    gouts = [rng.standard_normal((B, C, h, w)).astype(f32) for _ in range(nflows)]
+    if dyadic:
+        flows = [(np.round(f * 4) / 4).astype(f32) for f in flows]
+        filt = (np.round(filt * 16) / 16).astype(f32)
+        gouts = [(np.round(g * 16) / 16).astype(f32) for g in gouts]
+    flows[0][0, 0, :4] = f32(1000)          # invalid pixels
+    return flows, filt, gouts
+
+
+def test_restatement_composes():
+    flows, filt, gouts = _inputs(np.random.default_rng(21), 3)
+    h, w = gouts[0].shape[2:]
+    one, k1, _ = fc.predict(flows[:1], gouts[:1], filt)
+    ref, k1r, _ = bt.predict_image_grad("ori", flows[0], gouts[0], np.zeros_like(gouts[0]), filt)
+    assert k1 == k1r and np.array_equal(one, ref)
+    # three flows: the scale drops by the flows' share of the tap count, the sums add up
+    got, k3, fp32 = fc.predict(flows, gouts, filt)
+    assert not fp32 and k3 == bt.grad_scale(np.stack(gouts), filt, h, w, 48)[0]
+    _, _, scale, scale2 = fc.call_scale(gouts, filt, h, w)
+    parts = [bt.integer_sums("ori", fl, g, (scale, scale2), filt) for fl, g in zip(flows, gouts)]
+    assert np.array_equal(got, bt.convert(parts[0] + parts[1] + parts[2], k3, overwrite=True))
+    assert np.array_equal(got, fc.predict(flows[::-1], gouts[::-1], filt)[0])
+    # the generic-size addends are the 4 x 4 ones at 16 channels
+    assert np.array_equal(parts[0], fc.window_sums(flows[0], gouts[0], (scale, scale2), filt, 4))
+    assert fc.call_scale([np.full((1, 1, 9, 33), 1e-30, f32)] * 2, np.ones((1, 16, 9, 33), f32), 9, 33)[3] != 1
+    assert fc.call_scale([np.array([[[[np.inf]]]], f32)], np.ones((1, 16, 1, 1), f32), 1, 1)[1]
+
+
+@pytest.mark.parametrize("fcn", [16, 25])
+def test_restatement_equals_the_oracle_on_dyadic_inputs(oracle, fcn):
+    """dyadic inputs: every addend and partial sum is exact, so the C oracle's sequential fp32 sums per flow, added in
+    float64, are the restatement bit for bit"""
+    flows, filt, gouts = _inputs(np.random.default_rng(22), 3, fcn, dyadic=True)
+    img = np.zeros_like(gouts[0])
+    ref = sum(oracle.filterinterp_ori_bwd(img, fl, filt, g, fmad=1)[0].astype(np.float64) for fl, g in zip(flows, gouts))
+    got, k, fp32 = fc.predict(flows, gouts, filt)
+    assert not fp32 and np.array_equal(got.astype(np.float64), ref)
+
+
+@pytest.mark.parametrize("fcn", [16, 25])
+def test_restatement_within_the_float64_bound(oracle, np_oracle, fcn):
+    from tests.test_gpu_backward import IMG_ROUNDINGS, U, assert_image_grad
+    flows, filt, gouts = _inputs(np.random.default_rng(23), 3, fcn)
+    got, k, _ = fc.predict(flows, gouts, filt)
+    stats = [np_oracle.filterinterp_ori_bwd_img(fl, filt, g) for fl, g in zip(flows, gouts)]
+    e, S, n = (sum(s[i] for s in stats) for i in range(3))
+    assert_image_grad(got, np.zeros_like(got), (e, S, n), k, "ori")
+    # and the reference-pinned C oracle's own per-flow gradients, summed in float64: its sequential fp32 sums carry one
+    # rounding per addend (n U S at most) on top of the bound above
+    img = np.zeros_like(gouts[0])
+    ref = sum(oracle.filterinterp_ori_bwd(img, fl, filt, g, fmad=1)[0].astype(np.float64) for fl, g in zip(flows, gouts))
+    bound = (IMG_ROUNDINGS["ori"] + n) * U * S * (1 + 1e-6) + n * 2.0 ** -(k + 1) + np.abs(np.spacing(ref.astype(f32)))
+    assert np.all(np.abs(got.astype(np.float64) - ref) <= bound)
+
+
+# ------------------------------------------------------------------ fused.py, launches stubbed
+
+class _Stub:
+    def __init__(self):
+        self.forward, self.backward = [], []
+
+    def fwd(self, image, flows, filt, outs):
+        self.forward.append(len(flows))
+        for t, o in enumerate(outs):
+            o.fill_(float(t + 1))
+        return 0
+
+    def bwd(self, flows, filt, gouts, g1):
+        self.backward.append((list(flows), filt, list(gouts)))
+        g1.fill_(5.0)
+        return 0
+
+
+@pytest.fixture
+def stubbed(monkeypatch):
+    from vfidkr_amd import cabi, fused
+    stub = _Stub()
+    monkeypatch.setattr(cabi, "filterinterp_forward_ori_multi", stub.fwd)
+    monkeypatch.setattr(cabi, "filterinterp_backward_ori_image_multi", stub.bwd)
+    return fused, stub
+
+
+def _ctx_inputs(nt=3):
+    ctx0, ctx2 = torch.rand(1, 4, 5, 6), torch.rand(1, 4, 5, 6)
+    offs = [[torch.rand(1, 2, 5, 6, requires_grad=True) for _ in range(nt)] for _ in range(2)]
+    filts = [torch.rand(1, 16, 5, 6, requires_grad=True) for _ in range(2)]
+    return ctx0, ctx2, offs, filts
+
+
+def test_inference_path_reaches_no_autograd_function(stubbed, monkeypatch):
+    fused, stub = stubbed
+
+    def refuse(*a, **k):
+        raise AssertionError("the autograd Function was reached")
+    monkeypatch.setattr(fused._FilterInterpolateCtx, "apply", refuse)
+    ctx0, ctx2, offs, filts = _ctx_inputs()
+    outs = fused.FilterInterpolate_ctx_all(ctx0, ctx2, offs, filts)     # flows and filters require grad; the contexts do not
+    assert len(outs) == 3 and all(o.grad_fn is None and not o.requires_grad for pair in outs for o in pair)
+    ctx0.requires_grad_()
+    with torch.no_grad():
+        outs = fused.FilterInterpolate_ctx_all(ctx0, ctx2, offs, filts)
+    assert all(o.grad_fn is None for pair in outs for o in pair)
+    o0, o2 = fused.FilterInterpolate_ctx(ctx0.detach(), ctx2, [offs[0][0], offs[1][0]], filts)
+    assert o0.grad_fn is None and o2.grad_fn is None and stub.forward == [3, 3, 3, 3, 1, 1] and not stub.backward
+
+
+def test_training_path_hands_the_live_gradients_to_one_call(stubbed):
+    fused, stub = stubbed
+    ctx0, ctx2, offs, filts = _ctx_inputs()
+    ctx0.requires_grad_()
+    wide = torch.rand(1, 9, 5, 6, requires_grad=True)
+    view = wide[:, 2:6]                                     # a channel slice: the gradient buffer keeps its layout
+    outs = fused.FilterInterpolate_ctx_all(view, ctx0, offs, filts)
+    assert all(a.grad_fn is not None and b.grad_fn is not None for a, b in outs)
+    # the saved tensors are the filter and the flows, never the context tensor
+    assert [tuple(t.shape) for t in outs[0][0].grad_fn.saved_tensors] == [(1, 16, 5, 6)] + [(1, 2, 5, 6)] * 3
+    ga, gb = torch.rand(1, 4, 5, 6), torch.rand(1, 4, 5, 6)
+    ((outs[0][0] * ga).sum() + (outs[2][0] * gb).sum()).backward()
+    assert len(stub.backward) == 1                          # direction 0 only, the unused offset absent
+    flows, filt, gouts = stub.backward[0]
+    assert len(flows) == 2 and all(torch.equal(f, o) for f, o in zip(flows, (offs[0][0], offs[0][2])))
+    assert torch.equal(filt, filts[0]) and torch.equal(gouts[0], ga) and torch.equal(gouts[1], gb)
+    assert torch.equal(wide.grad[:, 2:6], torch.full((1, 4, 5, 6), 5.0)) and not wide.grad[:, :2].any() and ctx0.grad is None
+    assert all(f.grad is None for f in offs[0] + offs[1]) and all(f.grad is None for f in filts)

@@ -31,6 +31,7 @@ SIGNATURES = {
     "vfi_filterinterp_backward_ori": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_f16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_backward_ori_image_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_defor": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                        Strides, _p],
     "vfi_filterinterp_backward_defor": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides,
@@ -214,6 +215,30 @@ def filterinterp_backward_ori(input1, input2, input3, gradoutput, gradinput1, gr
         return _finish(lib().vfi_filterinterp_backward_ori(
             _ptr(input1), _ptr(input2), _ptr(input3), _ptr(gradoutput), _ptr(gradinput1), _ptr(gradinput2),
             _ptr(gradinput3), b, c, h, w, input3.size(1), _st(input1), _st(input2), _st(input3), _stream(input1)))
+
+
+def filterinterp_backward_ori_image_multi(flows, input3, gradoutputs, gradinput1):
+    """gradinput1 = the sum over t of the image gradient of FilterInterpolation(., flows[t], input3) for gradoutputs[t]: the
+    backward of filterinterp_forward_ori_multi towards the image alone.  gradinput1 is written in full (no zero fill needed)."""
+    n = len(flows)
+    if n == 0 or len(gradoutputs) != n:
+        return 1
+    for fl, g in zip(flows, gradoutputs):
+        # gradinput1 in the image's place: the binding's checks, then one layout per list and the gradients shaped like gradinput1
+        if _fi_checks(gradinput1, fl, input3, None) is None or not _same_strides(fl, flows[0]) or \
+                g.dim() != 4 or g.shape != gradinput1.shape or g.stride(3) != 1 or not _same_strides(g, gradoutputs[0]):
+            return 1
+        _dev(fl), _dev(g)
+    if not _fi_filter_ok(gradinput1, input3):
+        return 1
+    _dev(input3)
+    b, c, h, w = gradinput1.shape
+    fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
+    gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in gradoutputs])
+    with torch.cuda.device(_dev(gradinput1)):
+        return _finish(lib().vfi_filterinterp_backward_ori_image_multi(
+            fp, _ptr(input3), gp, _ptr(gradinput1), n, b, c, h, w, input3.size(1), _st(gradinput1), _st(flows[0]), _st(input3),
+            _st(gradoutputs[0]), _stream(gradinput1)))
 
 
 def filterinterp_forward_defor(variant, input1, input2, input3, input4, output, general=False):

@@ -9,8 +9,10 @@ the blend's is vfi_filterinterp_blend_backward (both directions, the blend weigh
 a frame requires grad).  Each takes its autograd Function only when grad mode is on and an input requires grad; otherwise
 it is the plain forward launch, with no grad_fn.  `forward_flownets_upsample` and `FlowProject_from_quarter` are
 differentiable in the same way, so the loss reaches the quarter-resolution flow of the flow network: one backward call of
-the library for all time offsets (vfi_flow_upsample4_backward, vfi_[depth]flowprojection_backward_up4).  The rest
-(`FilterInterpolate_ctx_all`, the frame glue) is inference only."""
+the library for all time offsets (vfi_flow_upsample4_backward, vfi_[depth]flowprojection_backward_up4).
+`FilterInterpolate_ctx_all` and `FilterInterpolate_ctx` train the context network: the context tensors get the image
+gradient of every time offset from one call per direction (vfi_filterinterp_backward_ori_image_multi), and flows and
+filter get none, because the reference detaches them on this path.  The rest (the frame glue) is inference only."""
 import math
 
 import torch
@@ -329,18 +331,70 @@ def FilterInterpolate(ref0, ref2, offset, filter, filter_size2, time_offset):
     return _filter_interpolate_launch(ref0, ref2, offset[0], offset[1], filter[0], filter[1], w0, w2)
 
 
+def _ctx_warp_launch(ctx, offsets, filt):
+    # (outputs share the input's layout, strided views included: empty_like would densify a channel slice)
+    outs = [torch.empty_strided(ctx.shape, ctx.stride(), dtype=ctx.dtype, device=ctx.device) for _ in offsets]
+    _check(cabi.filterinterp_forward_ori_multi(ctx, list(offsets), filt, outs), "filterinterp_forward_ori_multi")
+    return outs
+
+
+class _FilterInterpolateCtx(torch.autograd.Function):
+    """One direction of `FilterInterpolate_ctx` for a list of time offsets: the forward is the one multi-flow launch, the
+    backward ONE vfi_filterinterp_backward_ori_image_multi call over the outputs that received a gradient.  The context
+    tensor's gradient does not depend on its values, so only the flows and the filter are saved.  Flows and filter get no
+    gradient (the reference detaches them)."""
+
+    @staticmethod
+    def forward(ctx, image, filt, *offsets):
+        outs = _ctx_warp_launch(image, offsets, filt)
+        ctx.save_for_backward(filt, *offsets)
+        ctx.image_layout = (image.shape, image.stride())
+        ctx.set_materialize_grads(False)                   # (an unused time offset is an absent flow, not a tensor of zeros)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        filt, offsets = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        none = (None,) * (2 + len(offsets))
+        live = [i for i, g in enumerate(grads) if g is not None]
+        if not live or not ctx.needs_input_grad[0]:
+            return none
+        gs = _grad_layout([grads[i] for i in live])
+        shape, stride = ctx.image_layout
+        gimg = torch.empty_strided(shape, stride, dtype=torch.float32, device=gs[0].device)      # (written in full)
+        _check(cabi.filterinterp_backward_ori_image_multi([offsets[i] for i in live], filt, gs, gimg),
+               "filterinterp_backward_ori_image_multi")
+        return (gimg,) + none[1:]
+
+
+def _ctx_warp(image, offsets, filt):
+    """one direction: the Function when the context tensor can train, today's plain launch otherwise"""
+    if _wants_grad(image):
+        return list(_FilterInterpolateCtx.apply(image, filt, *offsets))
+    return _ctx_warp_launch(image, offsets, filt)
+
+
 def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
     """`DAIN_slowmotion.FilterInterpolate_ctx` (networks/DAIN_slowmotion.py:311-317) for every time offset of a step at
     once (the loop at :167-183 calls it once per t with the same context tensors and filters): offsets[d][t] is the
     projected flow of direction d at time offset t.  Returns [(ctx0_offset_t, ctx2_offset_t) for t], each pair what
-    the reference's call returns -- from one launch per direction that stages every image window once."""
-    nt = len(offsets[0])
-    # (outputs share the input's layout, strided views included: empty_like would densify a channel slice)
-    out0 = [torch.empty_strided(ctx0.shape, ctx0.stride(), dtype=ctx0.dtype, device=ctx0.device) for _ in range(nt)]
-    out2 = [torch.empty_strided(ctx2.shape, ctx2.stride(), dtype=ctx2.dtype, device=ctx2.device) for _ in range(nt)]
-    _check(cabi.filterinterp_forward_ori_multi(ctx0, list(offsets[0]), filter[0], out0), "filterinterp_forward_ori_multi")
-    _check(cabi.filterinterp_forward_ori_multi(ctx2, list(offsets[1]), filter[1], out2), "filterinterp_forward_ori_multi")
+    the reference's call returns -- from one launch per direction that stages every image window once.
+    Differentiable towards the context tensors when grad mode is on and ctx0 or ctx2 requires grad: a direction's context
+    tensor gets the sum over the time offsets of FilterInterpolationModule's image gradient, from ONE call of the library
+    over the outputs the loss used (reproducible bit for bit).  Offsets and filter get NO gradient, whether or not they
+    require grad: the reference passes `offset[d].detach()` and `filter[d].detach()` on this path.  Otherwise (inference,
+    or no context tensor requiring grad) the plain forward launches, with no grad_fn."""
+    out0 = _ctx_warp(ctx0, list(offsets[0]), filter[0])
+    out2 = _ctx_warp(ctx2, list(offsets[1]), filter[1])
     return list(zip(out0, out2))
+
+
+def FilterInterpolate_ctx(ctx0, ctx2, offset, filter):
+    """`DAIN.FilterInterpolate_ctx` (networks/DAIN.py:544-552): (ctx0_offset, ctx2_offset) for one time offset,
+    offset = [flow of direction 0, flow of direction 1].  Differentiable exactly as `FilterInterpolate_ctx_all` is:
+    towards the context tensors only."""
+    return FilterInterpolate_ctx_all(ctx0, ctx2, [[offset[0]], [offset[1]]], filter)[0]
 
 
 class _Warp(torch.autograd.Function):
