@@ -298,6 +298,31 @@ int vfi_correlation_backward(const float* input1, const float* input2, const flo
                              int pad_size, int kernel_size, int max_displacement,
                              int stride1, int stride2,
                              vfi_stream_t stream);
+/* The backward of vfi_correlation_forward_pair: two vfi_correlation_backward calls of equal shape -- items a and b, the
+ * same pyramid level of a frame pair's two flow networks -- with any subset of their four gradients.
+ *   Layout: contiguous NCHW float32, as the other correlation entries; `batch` is per item.
+ *   Result: every requested gradient equals the same-named output of vfi_correlation_backward on that item bit for bit
+ *     (the reference's order: 32 partial sums over tc = l, l+32, ..., then the partials added in sequence).
+ *   Every requested gradient is WRITTEN in full; the caller does not zero it.
+ *   Any of the four gradinput* may be NULL: it is not computed, and no workgroup is launched for it.  An item with both
+ *     outputs NULL may have NULL gradoutput and NULL inputs; otherwise its input1, input2 and gradoutput must all be
+ *     non-NULL.  All four outputs NULL (and a valid shape): VFI_OK, nothing launched.
+ *   Inputs may alias each other (at the top level (input1_b, input2_b) is often (input2_a, input1_a)).  Two equal non-NULL
+ *     output pointers return VFI_ERR_SHAPE, as vfi_correlation_forward_pair refuses output_a == output_b.
+ *   stride1 != 1 returns VFI_ERR_SHAPE, and so does everything else vfi_correlation_backward refuses (a shape that is
+ *     not positive, invalid parameters, no output pixel).  Every check runs before the first launch.
+ *   PWC-Net's configuration (pad 4, kernel 1, max displacement 4, strides 1): ONE launch for all requested gradients,
+ *     unless gradients x batch x channel groups exceeds a grid's z (65535).  Then, and for any other configuration, one
+ *     launch per requested gradient -- the same bits.
+ *   Nothing is allocated and no workspace is used: the call is legal inside a stream capture.  float32 only. */
+int vfi_correlation_backward_pair(const float* input1_a, const float* input2_a, const float* gradoutput_a,
+                                  float* gradinput1_a, float* gradinput2_a,
+                                  const float* input1_b, const float* input2_b, const float* gradoutput_b,
+                                  float* gradinput1_b, float* gradinput2_b,
+                                  int batch, int channel, int h, int w,
+                                  int pad_size, int kernel_size, int max_displacement,
+                                  int stride1, int stride2,
+                                  vfi_stream_t stream);
 /* The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541):
  * all five tensors IEEE half, dense NCHW, stride1 == 1 as for vfi_correlation_backward (same terms, windows and skips).
  * at::Half arithmetic rounds to half after every operation: each term p = half(gradOutput * value); 32 partials

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vfi_correlation_forward_pair": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_forward_f16": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_backward_pair": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_f16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     # glue either side of the ops
     "vfi_flow_upsample4": [_p, _p, _i, _i, _i, _i, _f, _f, Strides, Strides, _p],
@@ -572,6 +573,33 @@ def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_
     _corr_call("vfi_correlation_backward", "vfi_correlation_backward_f16", (input1, input2, gradoutput, g1, g2), b, c, h, w,
                pad_size, kernel_size, max_displacement, stride1, stride2)
     return g1, g2
+
+
+def correlation_backward_pair(a1, a2, ga, b1, b2, gb, pad_size, kernel_size, max_displacement, stride1, stride2,
+                              want=(True, True, True, True)):
+    """(correlation_backward(a1, a2, ga, ...), correlation_backward(b1, b2, gb, ...)) from ONE vfi_correlation_backward_pair
+    call: float32, equal shapes.  Returns (grad a1, grad a2, grad b1, grad b2), each written in full and bit-equal to the
+    single call's; None where `want` says so or where that item's gradoutput is None (such a gradient costs nothing)."""
+    inputs = (a1, a2, b1, b2)
+    b, c, h, w = a1.shape
+    gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    if len(want) != 4 or any(tuple(t.shape) != tuple(a1.shape) for t in inputs) or \
+            any(g is not None and tuple(g.shape) != gshape for g in (ga, gb)):
+        raise RuntimeError("correlation_backward_pair: the four inputs must have one shape and the gradoutputs the output dimensions")
+    for t in inputs + tuple(g for g in (ga, gb) if g is not None):
+        _dev(t)
+    a1, a2, b1, b2 = (t.contiguous() for t in inputs)
+    ga, gb = (None if g is None else g.contiguous() for g in (ga, gb))
+    grads = [torch.empty_like(t) if want[i] and (ga, gb)[i // 2] is not None else None for i, t in enumerate((a1, a2, b1, b2))]
+    if all(g is None for g in grads):
+        return tuple(grads)
+    with torch.cuda.device(a1.device):
+        err = lib().vfi_correlation_backward_pair(_ptr(a1), _ptr(a2), _opt(ga), _opt(grads[0]), _opt(grads[1]),
+                                                  _ptr(b1), _ptr(b2), _opt(gb), _opt(grads[2]), _opt(grads[3]), b, c, h, w,
+                                                  pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1))
+    if _finish(err) != 0:
+        raise RuntimeError("correlation_backward_pair: the binding returned %d" % err)
+    return tuple(grads)
 
 
 # ---------------------------------------------------------------- glue either side of the ops (SURVEY 8f)

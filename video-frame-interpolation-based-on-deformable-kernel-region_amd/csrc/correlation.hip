@@ -792,15 +792,16 @@ __global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__ha
 // tc) live in registers for all channels, and per channel the workgroup (64x4 pixels) stages the other map's window
 // (tile + 4 halo, zero padded) in LDS, double-buffered.  The sum runs in the reference's order -- 32 partial sums over
 // tc = l, l + 32, l + 64, added in sequence (correlation_cuda_kernel.cu:162-239, 255-332) -- so the result is corr_backward's
-// and the oracle's bit for bit.
+// and the oracle's bit for bit.  The body is one function: corr_backward_k1 below is one gradient per launch, and
+// corr_backward_k1_pair runs one instance or the other per workgroup.
+typedef float CorrBwdWindow[2][CorrBwdTile::LH][CorrBwdTile::LW];
+
 template <bool SECOND>
-__global__ __launch_bounds__(256) void corr_backward_k1(
-    const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
-    int channel, int h, int w, int groups, int ch_per_group) {
+__device__ __forceinline__ void corr_backward_k1_body(
+    CorrBwdWindow& win, const CorrBwdTile& t, const float* __restrict__ other, const float* __restrict__ gout,
+    float* __restrict__ gin, int channel, int h, int w) {
     typedef CorrBwdTile T;
     constexpr int MD = T::MD, D = T::D, OC = T::OC;
-    __shared__ float win[2][T::LH][T::LW];
-    const T t(channel, groups, ch_per_group);
     const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
     const int bx = t.x0 + px, by = t.y0 + py;
     const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
@@ -846,6 +847,30 @@ __global__ __launch_bounds__(256) void corr_backward_k1(
         }
         if (in) gin[((int64_t)n * channel + c) * plane + (int64_t)by * w + bx] = r / nelems;
     }
+}
+
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward_k1(
+    const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
+    int channel, int h, int w, int groups, int ch_per_group) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group);
+    corr_backward_k1_body<SECOND>(win, t, other, gout, gin, channel, h, w);
+}
+
+// Up to four gradients of two calls of equal shape in ONE launch (vfi_correlation_backward_pair: both gradients of the same
+// pyramid level of a frame pair's two flow networks).  A workgroup's role -- which item, first or second gradient -- comes
+// from blockIdx.z once (CorrBwdTile), so it is uniform: its three pointers are scalar loads from the argument block at the
+// role's index, and one scalar branch picks the instance of the body.  Nothing inside the channel loop knows of roles, and a
+// gradient's bits are those of its own corr_backward_k1 launch (channel groups only partition the channels).
+__global__ __launch_bounds__(256) void corr_backward_k1_pair(CorrBwdRoles roles, int channel, int h, int w, int groups, int ch_per_group) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group, roles.per_role);
+    const float* __restrict__ other = roles.r[t.role].other;
+    const float* __restrict__ gout = roles.r[t.role].gout;
+    float* __restrict__ gin = roles.r[t.role].gin;
+    if (roles.r[t.role].second) corr_backward_k1_body<true>(win, t, other, gout, gin, channel, h, w);
+    else corr_backward_k1_body<false>(win, t, other, gout, gin, channel, h, w);
 }
 
 // PWC-Net's configuration (k == 1, strides 1, pad == md == 4), modelled on corr_backward_k1: a workgroup owns 64x4 pixels and
@@ -984,16 +1009,6 @@ static int corr_backward_groups(int tiles, int batch, int channel, int* ch_per_g
     return (int64_t)batch * groups <= 65535 ? groups : 0;
 }
 
-// both gradients: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
-template <class K, class T, class... Rest>
-static int corr_launch_both(K first, K second, dim3 grid, dim3 block, hipStream_t st, const T* input1, const T* input2, const T* gradoutput,
-                            T* gradinput1, T* gradinput2, Rest... rest) {
-    hipLaunchKernelGGL(first, grid, block, 0, st, input2, gradoutput, gradinput1, rest...);
-    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    hipLaunchKernelGGL(second, grid, block, 0, st, input1, gradoutput, gradinput2, rest...);
-    return launch_status();
-}
-
 // one call, or two calls of equal shape (nitems == 2) in one launch
 static int correlation_forward_items(const float* const* in1s, const float* const* in2s, float* const* outs, int nitems, int per,
                                      int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
@@ -1116,7 +1131,41 @@ extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input
     return launch_status();
 }
 
-// float, or the reference's at::Half instantiation
+// One gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1.  float, or the
+// reference's at::Half instantiation.  The callers have run corr_check.
+template <class T>
+static int corr_backward_one(bool second, const T* other, const T* gout, T* gin, int batch, int channel, int h, int w, int oc, int oh,
+                             int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st) {
+    constexpr bool HALF = std::is_same<T, __half>::value;
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
+        // PWC-Net's configuration: the pixel-owns-its-gradOutput kernels; channel groups over blockIdx.z fill the chip.
+        // (The half kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.)
+        int ch_per_group;
+        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
+        if (groups && (!HALF || (int64_t)81 * h * w * 2 < INT_MAX)) {
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
+            if constexpr (HALF)
+                hipLaunchKernelGGL(second ? corr_backward_k1_f16<true> : corr_backward_k1_f16<false>, grid, dim3(128), 0, st, other, gout,
+                                   gin, channel, h, w, groups, ch_per_group);
+            else
+                hipLaunchKernelGGL(second ? corr_backward_k1<true> : corr_backward_k1<false>, grid, dim3(256), 0, st, other, gout, gin,
+                                   channel, h, w, groups, ch_per_group);
+            return launch_status();
+        }
+    }
+    const int64_t total = (int64_t)batch * channel * h * w;
+    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if constexpr (HALF)
+        hipLaunchKernelGGL(second ? corr_backward_f16<true> : corr_backward_f16<false>, grid, block, 0, st, other, gout, gin, batch,
+                           channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    else
+        hipLaunchKernelGGL(second ? corr_backward<true> : corr_backward<false>, grid, block, 0, st, other, gout, gin, batch, channel,
+                           h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    return launch_status();
+}
+
+// both gradients: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
 template <class T>
 static int correlation_backward_any(const T* input1, const T* input2, const T* gradoutput, T* gradinput1, T* gradinput2, int batch,
                                     int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
@@ -1129,29 +1178,11 @@ static int correlation_backward_any(const T* input1, const T* input2, const T* g
     const int64_t total = (int64_t)batch * channel * h * w;
     if (HALF && (total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
-        // PWC-Net's configuration: the pixel-owns-its-gradOutput kernels; channel groups over blockIdx.z fill the chip.
-        // (The half kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.)
-        int ch_per_group;
-        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
-        if (groups && (!HALF || (int64_t)81 * h * w * 2 < INT_MAX)) {
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            if constexpr (HALF)
-                return corr_launch_both(corr_backward_k1_f16<false>, corr_backward_k1_f16<true>, grid, dim3(128), st, input1, input2,
-                                        gradoutput, gradinput1, gradinput2, channel, h, w, groups, ch_per_group);
-            else
-                return corr_launch_both(corr_backward_k1<false>, corr_backward_k1<true>, grid, dim3(256), st, input1, input2,
-                                        gradoutput, gradinput1, gradinput2, channel, h, w, groups, ch_per_group);
-        }
-    }
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if constexpr (HALF)
-        return corr_launch_both(corr_backward_f16<false>, corr_backward_f16<true>, grid, block, st, input1, input2, gradoutput, gradinput1,
-                                gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    else
-        return corr_launch_both(corr_backward<false>, corr_backward<true>, grid, block, st, input1, input2, gradoutput, gradinput1,
-                                gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    if (corr_backward_one(false, input2, gradoutput, gradinput1, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
+                          max_displacement, stride2, st) != VFI_OK)
+        return VFI_ERR_LAUNCH;
+    return corr_backward_one(true, input1, gradoutput, gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
+                             max_displacement, stride2, st);
 }
 
 extern "C" int vfi_correlation_backward(const float* input1, const float* input2, const float* gradoutput,
@@ -1160,6 +1191,54 @@ extern "C" int vfi_correlation_backward(const float* input1, const float* input2
                                          vfi_stream_t stream) {
     return correlation_backward_any(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
                                     max_displacement, stride1, stride2, stream);
+}
+
+// The backward of two calls of equal shape -- the same pyramid level of the two flow networks of a frame pair, whose forward
+// is vfi_correlation_forward_pair -- with any subset of the four gradients.  PWC-Net's configuration: the requested
+// gradients are the roles of ONE corr_backward_k1_pair launch, and the channel groups are sized on the whole launch
+// (tiles x batch x roles).  Any other configuration, or role x batch x groups beyond a grid's z: one launch per requested
+// gradient with the kernels vfi_correlation_backward uses.  Either way a gradient's bits are that entry's.
+extern "C" int vfi_correlation_backward_pair(
+    const float* input1_a, const float* input2_a, const float* gradoutput_a, float* gradinput1_a, float* gradinput2_a,
+    const float* input1_b, const float* input2_b, const float* gradoutput_b, float* gradinput1_b, float* gradinput2_b,
+    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+    vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (corr_check({}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, true, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    const float* in1[2] = {input1_a, input1_b};
+    const float* in2[2] = {input2_a, input2_b};
+    const float* go[2] = {gradoutput_a, gradoutput_b};
+    float* gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
+    CorrBwdRoles roles = {};
+    int nroles = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (!gi[i][0] && !gi[i][1]) continue;               // (nothing asked of this item: its inputs may be NULL)
+        if (!in1[i] || !in2[i] || !go[i]) return VFI_ERR_SHAPE;
+        for (int s = 0; s < 2; ++s) {
+            if (!gi[i][s]) continue;
+            for (int k = 0; k < nroles; ++k)
+                if (roles.r[k].gin == gi[i][s]) return VFI_ERR_SHAPE;
+            roles.r[nroles++] = {s ? in1[i] : in2[i], go[i], gi[i][s], s};      // gradInput1 reads input2, gradInput2 input1
+        }
+    }
+    if (nroles == 0) return VFI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {
+        int ch_per_group;
+        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch * nroles, channel, &ch_per_group);
+        if (groups) {
+            roles.per_role = batch * groups;
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, nroles * roles.per_role);
+            hipLaunchKernelGGL(corr_backward_k1_pair, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
+            return launch_status();
+        }
+    }
+    for (int k = 0; k < nroles; ++k)
+        if (corr_backward_one(roles.r[k].second != 0, roles.r[k].other, roles.r[k].gout, roles.r[k].gin, batch, channel, h, w, oc, oh,
+                              ow, pad_size, kernel_size, max_displacement, stride2, st) != VFI_OK)
+            return VFI_ERR_LAUNCH;
+    return VFI_OK;
 }
 
 extern "C" int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,

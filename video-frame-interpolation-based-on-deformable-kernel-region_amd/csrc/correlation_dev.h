@@ -1,6 +1,6 @@
 // correlation_dev.h -- the pieces the correlation kernels share (correlation.hip, warp_correlation.hip): which image of a
 // launch a workgroup works on, the staging plan in aligned units, the 32x4 tile with two pixels per lane, the mean of the
-// running sums, and the tile of the tiled backward kernels.  Internal to the library.
+// running sums, and the tile and the roles of the tiled backward kernels.  Internal to the library.
 #pragma once
 #include "vfi_common.h"
 
@@ -69,15 +69,25 @@ __device__ __forceinline__ void corr_store_mean(int channel, Store&& store) {
     else store([&](float v) { return v / nelems; });
 }
 
+// The gradients of one vfi_correlation_backward_pair launch: a role is one requested gradient of one item -- the map its
+// window is staged from, the item's gradOutput, where it goes, and which of the two gradients it is.  The host compacts the
+// requested ones (at most four) to the front; role i owns blockIdx.z in [i * per_role, (i + 1) * per_role).
+struct CorrBwdRole { const float* other; const float* gout; float* gin; int second; };
+struct CorrBwdRoles { CorrBwdRole r[4]; int per_role; };
+
 // The tile of the tiled backward kernels (PWC-Net's configuration: k == 1, strides 1, pad == md == 4): a workgroup owns 64x4
 // pixels of one image and one channel group, and stages the other map's window (tile + 4 halo, zero padded) per channel.
+// blockIdx.z is image x channel group, and in a launch of several roles (per_role = images x groups of one role; 0: the
+// launch has one role) role x image x channel group.  All of it is workgroup-uniform.
 struct CorrBwdTile {
     static constexpr int MD = 4, D = 2 * MD + 1, OC = D * D, TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;
-    int x0, y0, n, c_begin, c_end;
-    __device__ __forceinline__ CorrBwdTile(int channel, int groups, int ch_per_group) {
+    int role, x0, y0, n, c_begin, c_end;
+    __device__ __forceinline__ CorrBwdTile(int channel, int groups, int ch_per_group, int per_role = 0) {
         x0 = blockIdx.x * TW; y0 = blockIdx.y * TH;
-        n = blockIdx.z / groups;
-        c_begin = (blockIdx.z - n * groups) * ch_per_group;
+        role = per_role ? blockIdx.z / per_role : 0;
+        const unsigned z = blockIdx.z - role * per_role;
+        n = z / groups;
+        c_begin = (z - n * groups) * ch_per_group;
         c_end = min(channel, c_begin + ch_per_group);
     }
     // window element e: its row and column in the window and its position in the frame (outside it: the zero padding)

@@ -1,8 +1,9 @@
 """Host-side mirrors of the glue either side of the hot-path ops, on the fused entry
 points of libvfi_hip.so.  Same names and argument meaning as the reference's static helpers
 (`networks/DAIN_slowmotion.py:204-216, 301-335`, `PWCNet/PWCNet.py:159-199`,
-`demo_MiddleBury.py:280-318, 350-388`).  `warp` and `warp_corr` are differentiable (PWC-Net's glue, trained with
-the flow network: the backward is vfi_pwc_warp_backward, and for `warp_corr` also the correlation backward).
+`demo_MiddleBury.py:280-318, 350-388`).  `warp`, `warp_corr` and `corr_pair` are differentiable (PWC-Net's glue, trained
+with the flow network: the backward is vfi_pwc_warp_backward, for `warp_corr` also the correlation backward, and for
+`corr_pair` one vfi_correlation_backward_pair call for both networks).
 `FlowProject` / `FlowProject_directions` and `FilterInterpolate` are differentiable too, so DAIN's synthesis loss reaches
 the flow and filter networks (networks/DAIN.py:215-238): the projection's backward is the reference's per-item kernel,
 the blend's is vfi_filterinterp_blend_backward (both directions, the blend weights folded in, no image gradient unless
@@ -466,9 +467,33 @@ def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
     return cabi.correlation_forward(c1, warp(c2, flo, align_corners), 4, 1, 4, 1, 1)
 
 
+class _CorrPair(torch.autograd.Function):
+    """`corr_pair` with its backward: the forward is the one vfi_correlation_forward_pair launch, the backward ONE
+    vfi_correlation_backward_pair call for the gradients autograd needs -- each bit-equal to `_Corr`'s.  A cost volume
+    the loss did not use arrives as None (not as zeros), and its item's gradients are None at no cost."""
+
+    @staticmethod
+    def forward(ctx, c1_a, c2_a, c1_b, c2_b):
+        ctx.save_for_backward(c1_a, c2_a, c1_b, c2_b)
+        ctx.set_materialize_grads(False)
+        return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_a, grad_b):
+        c1_a, c2_a, c1_b, c2_b = ctx.saved_tensors
+        return cabi.correlation_backward_pair(c1_a, c2_a, grad_a, c1_b, c2_b, grad_b, 4, 1, 4, 1, 1,
+                                              want=tuple(ctx.needs_input_grad))
+
+
 def corr_pair(c1_a, c2_a, c1_b, c2_b):
     """`self.corr(c1, c2)` of the two flow networks of a frame pair at one pyramid level (PWCNet/PWCNet.py:230, 246, 267, 283,
-    300 for the (I0, I1) network and again for (I1, I0): networks/DAIN.py:196-202) in one launch; returns both cost volumes."""
+    300 for the (I0, I1) network and again for (I1, I0): networks/DAIN.py:196-202) in one launch; returns both cost volumes.
+    Differentiable when grad mode is on and one of the four inputs requires grad: the backward is then ONE call for the
+    gradients that are needed (each bit-equal to the single correlation's; reproducible).  Otherwise the plain forward
+    launch (no grad_fn)."""
+    if _wants_grad(c1_a, c2_a, c1_b, c2_b):
+        return _CorrPair.apply(c1_a, c2_a, c1_b, c2_b)
     return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
 
 
