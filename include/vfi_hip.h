@@ -323,6 +323,50 @@ int vfi_correlation_backward_pair(const float* input1_a, const float* input2_a, 
                                   int pad_size, int kernel_size, int max_displacement,
                                   int stride1, int stride2,
                                   vfi_stream_t stream);
+/* ---- the correlation with PWC-Net's LeakyReLU fused in (PWCNet/PWCNet.py:230-301: every `self.corr(...)` is followed by
+ * `self.leakyRELU(corr)` and a `torch.cat((corr, ...), 1)`).  float32 only.  Each entry is its unactivated twin with the
+ * same argument checks, the same kernels and the same kernel choice, plus:
+ *   forward:  y = v > 0 ? v : v * negative_slope applied to every mean v as it is stored -- one float multiplication, the
+ *     bits of torch.nn.functional.leaky_relu on the twin's output (NaN stays NaN, -0 becomes -0 * negative_slope).
+ *   backward: every gradOutput value g at output position p becomes g' = y[p] > 0 ? g : g * negative_slope as it is
+ *     loaded, y the SAVED ACTIVATED OUTPUT (its sign is the pre-activation's for any slope > 0); g' is rounded to float
+ *     before it is used, so each gradient equals the twin's fed g', bit for bit.
+ *   negative_slope must be finite and > 0: anything else returns VFI_ERR_SHAPE, in all four entries.
+ *   *_batch_stride: the distance in ELEMENTS between two images of that tensor.  The 81 (out_channels) planes of an image
+ *     stay contiguous, so `output` may be the first channels of a preallocated concatenation buffer, and `gradoutput` the
+ *     narrow() view that torch.cat's backward hands down.  A stride below out_channels * out_h * out_w returns
+ *     VFI_ERR_SHAPE.  An output stride that breaks the 16- or 8-byte alignment of a kernel's stores selects the kernel a
+ *     misaligned output pointer would select; the result does not depend on it.
+ *   The pair entries are ONE launch for both items (forward) and for every requested gradient (backward: NULL gradients
+ *     are skipped, an item with both gradients NULL may be all NULL), exactly as vfi_correlation_backward_pair. */
+int vfi_correlation_lrelu_forward(const float* input1, const float* input2, float* output, int64_t output_batch_stride,
+                                  int batch, int channel, int h, int w,
+                                  int pad_size, int kernel_size, int max_displacement,
+                                  int stride1, int stride2, float negative_slope,
+                                  vfi_stream_t stream);
+int vfi_correlation_lrelu_forward_pair(const float* input1_a, const float* input2_a, float* output_a, int64_t output_a_batch_stride,
+                                       const float* input1_b, const float* input2_b, float* output_b, int64_t output_b_batch_stride,
+                                       int batch, int channel, int h, int w,
+                                       int pad_size, int kernel_size, int max_displacement,
+                                       int stride1, int stride2, float negative_slope,
+                                       vfi_stream_t stream);
+int vfi_correlation_lrelu_backward(const float* input1, const float* input2, const float* y, int64_t y_batch_stride,
+                                   const float* gradoutput, int64_t gradoutput_batch_stride,
+                                   float* gradinput1, float* gradinput2,
+                                   int batch, int channel, int h, int w,
+                                   int pad_size, int kernel_size, int max_displacement,
+                                   int stride1, int stride2, float negative_slope,
+                                   vfi_stream_t stream);
+int vfi_correlation_lrelu_backward_pair(const float* input1_a, const float* input2_a, const float* y_a, int64_t y_a_batch_stride,
+                                        const float* gradoutput_a, int64_t gradoutput_a_batch_stride,
+                                        float* gradinput1_a, float* gradinput2_a,
+                                        const float* input1_b, const float* input2_b, const float* y_b, int64_t y_b_batch_stride,
+                                        const float* gradoutput_b, int64_t gradoutput_b_batch_stride,
+                                        float* gradinput1_b, float* gradinput2_b,
+                                        int batch, int channel, int h, int w,
+                                        int pad_size, int kernel_size, int max_displacement,
+                                        int stride1, int stride2, float negative_slope,
+                                        vfi_stream_t stream);
 /* The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541):
  * all five tensors IEEE half, dense NCHW, stride1 == 1 as for vfi_correlation_backward (same terms, windows and skips).
  * at::Half arithmetic rounds to half after every operation: each term p = half(gradOutput * value); 32 partials

@@ -16,6 +16,7 @@ from . import LIB_PATH
 _i = ctypes.c_int
 _f = ctypes.c_float
 _p = ctypes.c_void_p
+_l = ctypes.c_int64
 
 
 class Strides(ctypes.Structure):
@@ -61,6 +62,11 @@ SIGNATURES = {
     "vfi_correlation_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_pair": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_f16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_lrelu_forward": [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_lrelu_forward_pair": [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_lrelu_backward": [_p, _p, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_lrelu_backward_pair": [_p, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p,
+                                            _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     # glue either side of the ops
     "vfi_flow_upsample4": [_p, _p, _i, _i, _i, _i, _f, _f, Strides, Strides, _p],
     "vfi_flowprojection_forward_up4": [_p, _p, _p, _i, _i, _i, _f, _f, _i, Strides, Strides, Strides, _p],
@@ -599,6 +605,147 @@ def correlation_backward_pair(a1, a2, ga, b1, b2, gb, pad_size, kernel_size, max
                                                   pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1))
     if _finish(err) != 0:
         raise RuntimeError("correlation_backward_pair: the binding returned %d" % err)
+    return tuple(grads)
+
+
+# the correlation with PWC-Net's LeakyReLU fused in (vfi_correlation_lrelu_*): float32
+
+def _dense_planes(t):
+    """The planes of every image contiguous and the images at least an image apart: a contiguous NCHW tensor, or a
+    channel slice buf[:, k:k + C] of a larger one (a dimension of size 1 has no stride to speak of)."""
+    b, c, h, w = t.shape
+    s = t.stride()
+    return (w == 1 or s[3] == 1) and (h == 1 or s[2] == w) and (c == 1 or s[1] == h * w) and (b == 1 or s[0] >= c * h * w)
+
+
+def _planes(t):
+    """(t, its batch stride in elements), t made contiguous unless its layout is dense planes at any batch stride"""
+    if not _dense_planes(t):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.size(0) > 1 else t.size(1) * t.size(2) * t.size(3))
+
+
+def _slope(negative_slope):
+    s = ctypes.c_float(float(negative_slope)).value
+    if not (s > 0.0 and math.isfinite(s)):
+        raise RuntimeError("correlation_lrelu: negative_slope must be finite and > 0 (the backward reads the sign off the output)")
+    return s
+
+
+def _lrelu_out(out, shape, like, what):
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if tuple(out.shape) != tuple(shape):
+        raise RuntimeError("%s: out= must have the output dimensions %s" % (what, tuple(shape)))
+    if not _dense_planes(out):
+        raise RuntimeError("%s: out= must have dense planes (a channel slice of a contiguous NCHW buffer)" % what)
+    _dev(out)
+    return out
+
+
+def correlation_lrelu_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2, negative_slope, out=None):
+    """leaky_relu(correlation_forward(input1, input2, ...), negative_slope) from the correlation's own launch, bit for bit.
+    out=: where to write it -- a tensor of the output's shape whose planes are dense, such as buf[:, k:k + 81] of a
+    contiguous NCHW buffer; returned as it is."""
+    slope = _slope(negative_slope)
+    if tuple(input2.shape) != tuple(input1.shape):
+        raise RuntimeError("correlation_lrelu_forward: the two inputs must have one shape")
+    b, c, h, w = input1.shape
+    oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    if out is not None:
+        _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward")
+    for t in (input1, input2):
+        _dev(t)
+    input1, input2 = input1.contiguous(), input2.contiguous()
+    out = _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward")
+    with torch.cuda.device(input1.device):
+        err = lib().vfi_correlation_lrelu_forward(_ptr(input1), _ptr(input2), _ptr(out), _planes(out)[1], b, c, h, w, pad_size,
+                                                  kernel_size, max_displacement, stride1, stride2, slope, _stream(input1))
+    if _finish(err) != 0:
+        raise RuntimeError("correlation_lrelu_forward: the binding returned %d" % err)
+    return out
+
+
+def correlation_lrelu_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displacement, stride1, stride2, negative_slope,
+                                   out=None):
+    """(correlation_lrelu_forward(a1, a2, ...), correlation_lrelu_forward(b1, b2, ...)) from one launch: equal shapes.
+    out=: a pair of destinations (either may be None), each as correlation_lrelu_forward's."""
+    slope = _slope(negative_slope)
+    if any(tuple(t.shape) != tuple(a1.shape) for t in (a1, a2, b1, b2)):
+        raise RuntimeError("correlation_lrelu_forward_pair: the four inputs must have one shape")
+    b, c, h, w = a1.shape
+    oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    outs = tuple(out) if out is not None else (None, None)
+    if len(outs) != 2 or (outs[0] is not None and outs[0] is outs[1]):
+        raise RuntimeError("correlation_lrelu_forward_pair: out= is a pair of two different destinations")
+    for o in outs:
+        if o is not None:
+            _lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair")
+    for t in (a1, a2, b1, b2):
+        _dev(t)
+    a1, a2, b1, b2 = (t.contiguous() for t in (a1, a2, b1, b2))
+    outa, outb = (_lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair") for o in outs)
+    with torch.cuda.device(a1.device):
+        err = lib().vfi_correlation_lrelu_forward_pair(_ptr(a1), _ptr(a2), _ptr(outa), _planes(outa)[1], _ptr(b1), _ptr(b2),
+                                                       _ptr(outb), _planes(outb)[1], b, c, h, w, pad_size, kernel_size,
+                                                       max_displacement, stride1, stride2, slope, _stream(a1))
+    if _finish(err) != 0:
+        raise RuntimeError("correlation_lrelu_forward_pair: the binding returned %d" % err)
+    return outa, outb
+
+
+def correlation_lrelu_backward(input1, input2, y, gradoutput, pad_size, kernel_size, max_displacement, stride1, stride2,
+                               negative_slope):
+    """correlation_backward(input1, input2, where(y > 0, g, g * negative_slope), ...) from the correlation backward's own
+    launches: y is the saved output of correlation_lrelu_forward.  y and gradoutput are read where they lie when their
+    planes are dense, whatever their batch stride (the narrow() view of torch.cat's backward); otherwise copied."""
+    slope = _slope(negative_slope)
+    b, c, h, w = input1.shape
+    gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    if input2.shape != input1.shape or tuple(gradoutput.shape) != gshape or tuple(y.shape) != gshape:
+        raise RuntimeError("correlation_lrelu_backward: input2 / y / gradoutput do not match input1's shape and the output dimensions")
+    for t in (input1, input2, y, gradoutput):
+        _dev(t)
+    input1, input2 = input1.contiguous(), input2.contiguous()
+    (y, ys), (gradoutput, gs) = _planes(y), _planes(gradoutput)
+    g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
+    with torch.cuda.device(input1.device):
+        err = lib().vfi_correlation_lrelu_backward(_ptr(input1), _ptr(input2), _ptr(y), ys, _ptr(gradoutput), gs, _ptr(g1), _ptr(g2),
+                                                   b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope,
+                                                   _stream(input1))
+    if _finish(err) != 0:
+        raise RuntimeError("correlation_lrelu_backward: the binding returned %d" % err)
+    return g1, g2
+
+
+def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, kernel_size, max_displacement, stride1, stride2,
+                                    negative_slope, want=(True, True, True, True)):
+    """(correlation_lrelu_backward(a1, a2, ya, ga, ...), correlation_lrelu_backward(b1, b2, yb, gb, ...)) from ONE
+    vfi_correlation_lrelu_backward_pair call.  Returns (grad a1, grad a2, grad b1, grad b2), each written in full and
+    bit-equal to the single call's; None where `want` says so or where that item's gradoutput is None."""
+    slope = _slope(negative_slope)
+    inputs = (a1, a2, b1, b2)
+    b, c, h, w = a1.shape
+    gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    if len(want) != 4 or any(tuple(t.shape) != tuple(a1.shape) for t in inputs) or \
+            any(g is not None and (tuple(g.shape) != gshape or y is None or tuple(y.shape) != gshape) for y, g in ((ya, ga), (yb, gb))):
+        raise RuntimeError("correlation_lrelu_backward_pair: the four inputs must have one shape, and y and the gradoutputs "
+                           "the output dimensions")
+    for t in inputs + tuple(t for y, g in ((ya, ga), (yb, gb)) if g is not None for t in (y, g)):
+        _dev(t)
+    a1, a2, b1, b2 = (t.contiguous() for t in inputs)
+    (ya, yas), (ga, gas) = ((None, 0), (None, 0)) if ga is None else (_planes(ya), _planes(ga))
+    (yb, ybs), (gb, gbs) = ((None, 0), (None, 0)) if gb is None else (_planes(yb), _planes(gb))
+    grads = [torch.empty_like(t) if want[i] and (ga, gb)[i // 2] is not None else None for i, t in enumerate((a1, a2, b1, b2))]
+    if all(g is None for g in grads):
+        return tuple(grads)
+    with torch.cuda.device(a1.device):
+        err = lib().vfi_correlation_lrelu_backward_pair(
+            _ptr(a1), _ptr(a2), _opt(ya), yas, _opt(ga), gas, _opt(grads[0]), _opt(grads[1]),
+            _ptr(b1), _ptr(b2), _opt(yb), ybs, _opt(gb), gbs, _opt(grads[2]), _opt(grads[3]),
+            b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope, _stream(a1))
+    if _finish(err) != 0:
+        raise RuntimeError("correlation_lrelu_backward_pair: the binding returned %d" % err)
     return tuple(grads)
 
 

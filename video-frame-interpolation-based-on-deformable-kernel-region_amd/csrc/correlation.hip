@@ -20,6 +20,7 @@
 #include "correlation_dev.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <initializer_list>
 #include <type_traits>
 
@@ -35,9 +36,9 @@ __device__ __forceinline__ float padded_at(const float* __restrict__ f, int h, i
 
 // k == 1, stride1 == stride2 == 1.  `org` = md - pad: output pixel (oy, ox) is
 // centred on input pixel (oy + org, ox + org).
-template <int MD, int CORR_TW, int CORR_TH>
+template <int MD, int CORR_TW, int CORR_TH, class Epi>
 __global__ __launch_bounds__(CORR_TW * CORR_TH) void corr_forward_k1(
-    CorrItems items, int channel, int h, int w, int oh, int ow, int org) {
+    CorrItems items, int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     constexpr int D = 2 * MD + 1;
     constexpr int LW = CORR_TW + 2 * MD, LH = CORR_TH + 2 * MD;
     constexpr int NI = (LH + CORR_TH - 1) / CORR_TH, NJ = (LW + CORR_TW - 1) / CORR_TW;
@@ -122,16 +123,16 @@ __global__ __launch_bounds__(CORR_TW * CORR_TH) void corr_forward_k1(
     }
     if (ox < ow && oy < oh) {
         const float nelems = (float)channel;
-        float* o = out + (int64_t)b * (D * D) * oh * ow + (int64_t)oy * ow + ox;
+        float* o = out + epi.plane(im.item, b, D * D, 0, oh, ow) + (int64_t)oy * ow + ox;
 #pragma unroll
-        for (int k = 0; k < D * D; ++k) o[(int64_t)k * oh * ow] = acc[k] / nelems;
+        for (int k = 0; k < D * D; ++k) o[(int64_t)k * oh * ow] = epi(acc[k] / nelems);
     }
 }
 
 // k == 1, strides 1, small frames: tile of 16x4 output pixels, threadIdx.y = displacement row tj.
-template <int MD>
+template <int MD, class Epi>
 __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows(
-    CorrItems items, int channel, int h, int w, int oh, int ow, int org) {
+    CorrItems items, int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     constexpr int D = 2 * MD + 1;
     constexpr int TW = 16, TH = 4, LW = TW + 2 * MD, LH = TH + 2 * MD;
     constexpr int NT = 64 * D, NE = CORR_CC_ROWS * LH * LW;      // threads, staged elements per chunk
@@ -212,9 +213,9 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows(
     }
     if (ox < ow && oy < oh) {
         const float nelems = (float)channel;
-        float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox;
+        float* o = out + epi.plane(im.item, b, D * D, tj * D, oh, ow) + (int64_t)oy * ow + ox;
 #pragma unroll
-        for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = acc[ti] / nelems;
+        for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = epi(acc[ti] / nelems);
     }
 }
 
@@ -225,9 +226,9 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows(
 // tiled kernels at one workgroup per CU); per channel a lane reads the 10 values its two 9-wide
 // displacement rows share as five aligned ds_read_b64 for 18 multiply-adds.  Same sequential
 // channel order.
-template <int MD>
+template <int MD, class Epi>
 __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
-    CorrItems items, int channel, int h, int w, int oh, int ow, int org) {
+    CorrItems items, int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     typedef CorrTile2<MD> T;                                                    // LW = 40: 10 aligned 16-byte units
     constexpr int D = T::D, TW = T::TW, TH = T::TH;
     typedef float v2f __attribute__((ext_vector_type(2)));
@@ -302,16 +303,16 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
     corr_store_mean(channel, [&](auto mean) {
         if (oy < oh && ox + 1 < ow && (ow & 1) == 0) {
             // the lane's two pixels as one 8-byte store: a wave writes whole 128-byte row segments
-            float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox;
+            float* o = out + epi.plane(im.item, b, D * D, tj * D, oh, ow) + (int64_t)oy * ow + ox;
 #pragma unroll
-            for (int ti = 0; ti < D; ++ti) *reinterpret_cast<v2f*>(o + (int64_t)ti * oh * ow) = v2f{mean(acc[0][ti]), mean(acc[1][ti])};
+            for (int ti = 0; ti < D; ++ti) *reinterpret_cast<v2f*>(o + (int64_t)ti * oh * ow) = v2f{epi(mean(acc[0][ti])), epi(mean(acc[1][ti]))};
         } else {
 #pragma unroll
             for (int q = 0; q < 2; ++q)
                 if (ox + q < ow && oy < oh) {
-                    float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox + q;
+                    float* o = out + epi.plane(im.item, b, D * D, tj * D, oh, ow) + (int64_t)oy * ow + ox + q;
 #pragma unroll
-                    for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = mean(acc[q][ti]);
+                    for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow] = epi(mean(acc[q][ti]));
                 }
         }
     });
@@ -337,9 +338,10 @@ __global__ __launch_bounds__(64 * (2 * MD + 1)) void corr_forward_k1_rows2(
 // drains vmcnt before an LDS read it can see next to an LDS-DMA target (filterinterp_lds.hip), which would wait for the chunk
 // in flight.  Same tile, same lanes, same order of the multiply-adds: the same bits.
 #define CORR_QUAD_LDS_FLOATS (2 * (4 * 6 * 18 + 4 * 4 * 16) * 4)          // two buffers of 432 window units + 256 first-map units
-template <int MD>
+template <int MD, class Epi>
 __device__ __forceinline__ void corr_quad_body(
-    const CorrItems& items, int channel, int h, int w, int oh, int ow, int org, int tiles_x, int tiles_y, int ntiles, float* lds) {
+    const CorrItems& items, int channel, int h, int w, int oh, int ow, int org, int tiles_x, int tiles_y, int ntiles, float* lds,
+    const Epi& epi) {
     constexpr int D = 2 * MD + 1, G = 3;
     constexpr int CCQ = 4;
     constexpr int TW = 64, TH = 4, LW = TW + 2 * MD, LH = TH + G - 1;
@@ -433,33 +435,35 @@ __device__ __forceinline__ void corr_quad_body(
 #undef CORR_CHANNEL_TERMS
     static_assert(CCQ == 4, "four channels per chunk");
     if (oy >= oh) return;
-    float* o = out + ((int64_t)b * (D * D) + tj * D) * oh * ow + (int64_t)oy * ow + ox;
+    float* o = out + epi.plane(im.item, b, D * D, tj * D, oh, ow) + (int64_t)oy * ow + ox;
     corr_store_mean(channel, [&](auto mean) {
         if (ox + 3 < ow && (ow & 3) == 0) {
 #pragma unroll
             for (int ti = 0; ti < D; ++ti)
-                *reinterpret_cast<v4f*>(o + (int64_t)ti * oh * ow) = v4f{mean(acc[0][ti]), mean(acc[1][ti]), mean(acc[2][ti]), mean(acc[3][ti])};
+                *reinterpret_cast<v4f*>(o + (int64_t)ti * oh * ow) =
+                    v4f{epi(mean(acc[0][ti])), epi(mean(acc[1][ti])), epi(mean(acc[2][ti])), epi(mean(acc[3][ti]))};
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 if (ox + q < ow) {
 #pragma unroll
-                    for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow + q] = mean(acc[q][ti]);
+                    for (int ti = 0; ti < D; ++ti) o[(int64_t)ti * oh * ow + q] = epi(mean(acc[q][ti]));
                 }
         }
     });
 }
 
 // (the body is a device function: its inline assembly must not be instantiated by the host pass)
-template <int MD>
+template <int MD, class Epi>
 __global__ __launch_bounds__(192, 5) void corr_forward_k1_quad(
-    CorrItems items, int channel, int h, int w, int oh, int ow, int org, int tiles_x, int tiles_y, int ntiles) {
+    CorrItems items, int channel, int h, int w, int oh, int ow, int org, int tiles_x, int tiles_y, int ntiles, Epi epi) {
     __shared__ __attribute__((aligned(16))) float lds[CORR_QUAD_LDS_FLOATS];  // ONE array (see above)
-    corr_quad_body<MD>(items, channel, h, w, oh, ow, org, tiles_x, tiles_y, ntiles, lds);
+    corr_quad_body<MD>(items, channel, h, w, oh, ow, org, tiles_x, tiles_y, ntiles, lds, epi);
 }
 
 // (explicit: hipcc 7.2 leaves the host stub of a kernel template undefined when its only launch sits in a branch it folds away)
-template __global__ void corr_forward_k1_quad<4>(CorrItems, int, int, int, int, int, int, int, int, int);
+template __global__ void corr_forward_k1_quad<4, CorrPlain>(CorrItems, int, int, int, int, int, int, int, int, int, CorrPlain);
+template __global__ void corr_forward_k1_quad<4, CorrLrelu>(CorrItems, int, int, int, int, int, int, int, int, int, CorrLrelu);
 
 // k == 1, strides 1, tiny frames (the coarsest pyramid levels: a few hundred pixels, up to 196
 // channels): one thread per output element, x fastest, so a wave reads 64 consecutive pixels of each
@@ -471,9 +475,9 @@ template __global__ void corr_forward_k1_quad<4>(CorrItems, int, int, int, int, 
 // NaN, then NaN.  Such a lane runs the same loop: its outside tap is read at the inside tap's pixel (a valid address) and
 // `keep` clears what was read.  (A loop of its own for these lanes would run in nearly every wave, after the other one; and
 // reading the inside tap's own address twice instead doubled this kernel's time at 196 x 18 x 31.  Both measured: DESIGN.md 4.3.)
-template <int MD>
+template <int MD, class Epi>
 __global__ __launch_bounds__(256) void corr_forward_k1_flat(
-    CorrItems items, int batch, int channel, int h, int w, int oh, int ow, int org) {
+    CorrItems items, int batch, int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     constexpr int D = 2 * MD + 1;
     const int64_t total = (int64_t)batch * D * D * oh * ow;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -510,14 +514,16 @@ __global__ __launch_bounds__(256) void corr_forward_k1_flat(
         }
         for (; c < channel; ++c) acc = fmaf(pa[(int64_t)c * plane], tap(c), acc);
     }
-    out[gid - (int64_t)im.item * items.per * D * D * oh * ow] = acc / (float)channel;
+    if constexpr (Epi::DENSE) out[gid - (int64_t)im.item * items.per * D * D * oh * ow] = epi(acc / (float)channel);
+    else out[epi.plane(im.item, b, D * D, tc, oh, ow) + (int64_t)oy * ow + ox] = epi(acc / (float)channel);
 }
 
-// any kernel size / strides: one thread per output element, sequential channel order
+// any kernel size / strides: one thread per output element, sequential channel order (one item per launch: epi's item 0)
+template <class Epi>
 __global__ __launch_bounds__(256) void corr_forward_generic(
     const float* __restrict__ in1, const float* __restrict__ in2, float* __restrict__ out,
     int batch, int channel, int h, int w, int oc, int oh, int ow,
-    int pad, int kr, int md, int s1, int s2, int dr) {
+    int pad, int kr, int md, int s1, int s2, int dr, Epi epi) {
     const int64_t total = (int64_t)batch * oc * oh * ow;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
@@ -539,7 +545,8 @@ __global__ __launch_bounds__(256) void corr_forward_generic(
                 acc = fmaf(padded_at(f1 + (int64_t)c * plane, h, w, y1 + j, x1 + i),
                            padded_at(f2 + (int64_t)c * plane, h, w, y2 + j, x2 + i), acc);
     const int k = 2 * kr + 1;
-    out[gid] = acc / (float)(k * k * channel);
+    if constexpr (Epi::DENSE) out[gid] = epi(acc / (float)(k * k * channel));
+    else out[epi.plane(0, b, oc, tc, oh, ow) + (int64_t)oy * ow + ox] = epi(acc / (float)(k * k * channel));
 }
 
 // The at::Half instantiation for PWC-Net's configuration, tiled like corr_forward_k1_rows2: 32x4 output pixels per
@@ -720,10 +727,12 @@ struct CorrF16 {
 // backward, stride1 == 1, any pad / k / md / stride2 (correlation_cuda_kernel.cu:151-334).  One thread per gradient
 // element; the reference's reduction order (32 partial sums over tc = l, l+32, ..., then a sequential sum of the
 // partials) is kept.  A term whose other-map tap lies in the zero padding is not skipped: it adds g * 0 in A's arithmetic.
-template <class A, bool SECOND>
+// MASK (float only): every gradOutput value goes through LeakyReLU's derivative as it is loaded (CorrGrad).
+template <class A, bool SECOND, bool MASK = false>
 __device__ __forceinline__ void corr_backward_body(
     const typename A::T* __restrict__ other, const typename A::T* __restrict__ gout, typename A::T* __restrict__ gin,
-    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr) {
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr,
+    const CorrGrad<MASK>& act = CorrGrad<false>{}) {
     typedef typename A::T T;
     const int64_t total = (int64_t)batch * channel * h * w;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -735,7 +744,8 @@ __device__ __forceinline__ void corr_backward_body(
     const int dsz = 2 * dr + 1;
     const int y = by + pad, x = bx + pad;                   // padded coordinates
     const T* of = other + ((int64_t)n * channel + c) * h * w;
-    const T* go = gout + (int64_t)n * oc * oh * ow;
+    const T* go = MASK ? gout + (int64_t)n * act.gstride : gout + (int64_t)n * oc * oh * ow;
+    const float* yo = MASK ? act.y + (int64_t)n * act.ystride : nullptr;
     const float nelems = A::count((2 * kr + 1) * (2 * kr + 1) * channel);
     bool any = SECOND;
     if constexpr (!SECOND) {
@@ -766,7 +776,10 @@ __device__ __forceinline__ void corr_backward_body(
             ymin = max(0, ymin); ymax = min(oh - 1, ymax);
             const T* g = go + (int64_t)tc * oh * ow;
             for (int j = ymin; j <= ymax; ++j)
-                for (int i = xmin; i <= xmax; ++i) s = A::term(s, g[(int64_t)j * ow + i], val);
+                for (int i = xmin; i <= xmax; ++i) {
+                    if constexpr (MASK) s = A::term(s, act(g[(int64_t)j * ow + i], yo[(int64_t)tc * oh * ow + (int64_t)j * ow + i]), val);
+                    else s = A::term(s, g[(int64_t)j * ow + i], val);
+                }
         }
         r = A::add(r, s);
     }
@@ -778,6 +791,11 @@ __device__ __forceinline__ void corr_backward_body(
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward(CORR_BACKWARD_ARGS(float)) {
     corr_backward_body<CorrF32, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr);
+}
+// the same through LeakyReLU's derivative (vfi_correlation_lrelu_backward*, any configuration)
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_lrelu_backward(CORR_BACKWARD_ARGS(float), CorrGrad<true> act) {
+    corr_backward_body<CorrF32, SECOND, true>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, act);
 }
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__half)) {
@@ -796,10 +814,12 @@ __global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__ha
 // corr_backward_k1_pair runs one instance or the other per workgroup.
 typedef float CorrBwdWindow[2][CorrBwdTile::LH][CorrBwdTile::LW];
 
-template <bool SECOND>
+// MASK: the 81 values go through LeakyReLU's derivative as they are loaded (CorrGrad: 81 more loads per pixel and channel
+// group, outside the channel loop); the channel loop is the same code either way.
+template <bool SECOND, bool MASK = false>
 __device__ __forceinline__ void corr_backward_k1_body(
     CorrBwdWindow& win, const CorrBwdTile& t, const float* __restrict__ other, const float* __restrict__ gout,
-    float* __restrict__ gin, int channel, int h, int w) {
+    float* __restrict__ gin, int channel, int h, int w, const CorrGrad<MASK>& act = CorrGrad<false>{}) {
     typedef CorrBwdTile T;
     constexpr int MD = T::MD, D = T::D, OC = T::OC;
     const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
@@ -807,14 +827,25 @@ __device__ __forceinline__ void corr_backward_k1_body(
     const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
     const bool in = bx < w && by < h;
     const int64_t plane = (int64_t)h * w;
-    const float* go = gout + (int64_t)n * OC * plane;
+    const float* go = MASK ? gout + (int64_t)n * act.gstride : gout + (int64_t)n * OC * plane;
+    const float* yo = MASK ? act.y + (int64_t)n * act.ystride : nullptr;
 
     // the pixel's 81 gradOutput values (zero where the reference skips the term: gradInput2 near the frame's border)
     float g[OC];
 #pragma unroll
     for (int tc = 0; tc < OC; ++tc) {
         const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
-        g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? go[(int64_t)tc * plane + (int64_t)gy * w + gx] : 0.0f;
+        if constexpr (MASK) {
+            // (a skipped term loads element 0 of its image -- a valid address -- and drops it: loads under a branch go out one
+            //  at a time, each waited for; these go out a displacement row of gradOutput and y together)
+            const bool ok = in && gy >= 0 && gy < h && gx >= 0 && gx < w;
+            const int64_t at = ok ? (int64_t)tc * plane + (int64_t)gy * w + gx : 0;
+            const float gv = go[at], yv = yo[at];
+            g[tc] = act(ok ? gv : 0.0f, ok ? yv : 0.0f);
+            if (tc % D == D - 1) __builtin_amdgcn_sched_barrier(0);
+        } else {
+            g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? go[(int64_t)tc * plane + (int64_t)gy * w + gx] : 0.0f;
+        }
     }
     // (a term the reference skips -- gradInput2, displaced position outside the frame -- reads the other map at that same
     //  position: the zero padding of the staged window, so the skipped term is fma(0, 0, s) = s)
@@ -871,6 +902,29 @@ __global__ __launch_bounds__(256) void corr_backward_k1_pair(CorrBwdRoles roles,
     float* __restrict__ gin = roles.r[t.role].gin;
     if (roles.r[t.role].second) corr_backward_k1_body<true>(win, t, other, gout, gin, channel, h, w);
     else corr_backward_k1_body<false>(win, t, other, gout, gin, channel, h, w);
+}
+
+// The two kernels above with the mask (vfi_correlation_lrelu_backward, ..._pair): kernels of their own, so the plain ones
+// are what they were.  A role's y and strides are scalar loads at the role's index, like its pointers.
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_lrelu_backward_k1(
+    const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
+    int channel, int h, int w, int groups, int ch_per_group, CorrGrad<true> act) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group);
+    corr_backward_k1_body<SECOND, true>(win, t, other, gout, gin, channel, h, w, act);
+}
+
+__global__ __launch_bounds__(256) void corr_lrelu_backward_k1_pair(CorrBwdRoles roles, CorrBwdMasks masks, int channel, int h, int w,
+                                                                   int groups, int ch_per_group) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group, roles.per_role);
+    const float* __restrict__ other = roles.r[t.role].other;
+    const float* __restrict__ gout = roles.r[t.role].gout;
+    float* __restrict__ gin = roles.r[t.role].gin;
+    const CorrGrad<true> act = {masks.y[t.role], masks.ystride[t.role], masks.gstride[t.role], masks.slope};
+    if (roles.r[t.role].second) corr_backward_k1_body<true, true>(win, t, other, gout, gin, channel, h, w, act);
+    else corr_backward_k1_body<false, true>(win, t, other, gout, gin, channel, h, w, act);
 }
 
 // PWC-Net's configuration (k == 1, strides 1, pad == md == 4), modelled on corr_backward_k1: a workgroup owns 64x4 pixels and
@@ -1009,10 +1063,23 @@ static int corr_backward_groups(int tiles, int batch, int channel, int* ch_per_g
     return (int64_t)batch * groups <= 65535 ? groups : 0;
 }
 
+// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
+static bool corr_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
+
+// What an epilogue adds to the bits the alignment tests look at: an image stride that breaks a kernel's store alignment
+// counts exactly as a misaligned base pointer does.  Whether the strides are valid for an output of oc x oh x ow planes.
+static uintptr_t corr_stride_bits(const CorrPlain&, int) { return 0; }
+static uintptr_t corr_stride_bits(const CorrLrelu& e, int item) { return (uintptr_t)e.stride[item] * sizeof(float); }
+static bool corr_epilogue_ok(const CorrPlain&, int, int64_t) { return true; }
+static bool corr_epilogue_ok(const CorrLrelu& e, int nitems, int64_t image) {
+    return corr_slope_ok(e.slope) && e.stride[0] >= image && e.stride[nitems - 1] >= image;
+}
+
 // one call, or two calls of equal shape (nitems == 2) in one launch
+template <class Epi>
 static int correlation_forward_items(const float* const* in1s, const float* const* in2s, float* const* outs, int nitems, int per,
                                      int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
-                                     int stride1, int stride2, vfi_stream_t stream) {
+                                     int stride1, int stride2, vfi_stream_t stream, const Epi& epi) {
     int oc, oh, ow;
     if (nitems < 1 || nitems > 2) return VFI_ERR_SHAPE;
     const int last = nitems - 1;
@@ -1020,6 +1087,7 @@ static int correlation_forward_items(const float* const* in1s, const float* cons
                    max_displacement, stride1, stride2, false, &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
     if (nitems == 2 && outs[0] == outs[1]) return VFI_ERR_SHAPE;
+    if (!corr_epilogue_ok(epi, nitems, (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int batch = nitems * per;                          // images of the launch
     CorrItems items;
@@ -1028,7 +1096,7 @@ static int correlation_forward_items(const float* const* in1s, const float* cons
         const int k = i < nitems ? i : 0;
         items.in1[i] = in1s[k]; items.in2[i] = in2s[k]; items.out[i] = outs[k];
         in_bits |= reinterpret_cast<uintptr_t>(in1s[k]) | reinterpret_cast<uintptr_t>(in2s[k]);
-        out_bits |= reinterpret_cast<uintptr_t>(outs[k]);
+        out_bits |= reinterpret_cast<uintptr_t>(outs[k]) | corr_stride_bits(epi, k);
     }
     items.per = per;
     const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
@@ -1041,37 +1109,39 @@ static int correlation_forward_items(const float* const* in1s, const float* cons
                              (int64_t)h * w * 4 * (CORR_CC_ROWS + 1) < INT_MAX;      // (a chunk of planes through one buffer descriptor)
         if (small_tiles < corr_flat_threshold * nitems) {
             const int64_t total = (int64_t)batch * oc * oh * ow;
-            hipLaunchKernelGGL(corr_forward_k1_flat<4>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, items,
-                               batch, channel, h, w, oh, ow, max_displacement - pad_size);
+            hipLaunchKernelGGL((corr_forward_k1_flat<4, Epi>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, items,
+                               batch, channel, h, w, oh, ow, max_displacement - pad_size, epi);
         } else if (aligned && (out_bits & 15) == 0 &&
                    (int64_t)((ow + 63) / 64) * ((oh + 3) / 4) * batch >= corr_quad_threshold * nitems) {
             const int tiles_x = (ow + 63) / 64, tiles_y = (oh + 3) / 4;
             const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
             if (nt > (1 << 26)) return VFI_ERR_SHAPE;
             const unsigned wgs = (unsigned)((nt + 7) / 8) * 8 * 3;                 // whole groups of 8 XCDs x 3 displacement-row groups
-            hipLaunchKernelGGL(corr_forward_k1_quad<4>, dim3(wgs), dim3(64, 3, 1), 0, st, items,
-                               channel, h, w, oh, ow, max_displacement - pad_size, tiles_x, tiles_y, (int)nt);
+            hipLaunchKernelGGL((corr_forward_k1_quad<4, Epi>), dim3(wgs), dim3(64, 3, 1), 0, st, items,
+                               channel, h, w, oh, ow, max_displacement - pad_size, tiles_x, tiles_y, (int)nt, epi);
         } else if (aligned) {
             const dim3 grid((ow + 31) / 32, (oh + 3) / 4, batch);
-            hipLaunchKernelGGL(corr_forward_k1_rows2<4>, grid, dim3(64, 9, 1), 0, st, items,
-                               channel, h, w, oh, ow, max_displacement - pad_size);
+            hipLaunchKernelGGL((corr_forward_k1_rows2<4, Epi>), grid, dim3(64, 9, 1), 0, st, items,
+                               channel, h, w, oh, ow, max_displacement - pad_size, epi);
         } else if (big_tiles >= corr_big_threshold * nitems) {
             const dim3 grid((ow + 31) / 32, (oh + 7) / 8, batch);
-            hipLaunchKernelGGL((corr_forward_k1<4, 32, 8>), grid, dim3(32, 8, 1), 0, st, items,
-                               channel, h, w, oh, ow, max_displacement - pad_size);
+            hipLaunchKernelGGL((corr_forward_k1<4, 32, 8, Epi>), grid, dim3(32, 8, 1), 0, st, items,
+                               channel, h, w, oh, ow, max_displacement - pad_size, epi);
         } else {
             const dim3 grid((ow + 15) / 16, (oh + 3) / 4, batch);
-            hipLaunchKernelGGL(corr_forward_k1_rows<4>, grid, dim3(64, 9, 1), 0, st, items,
-                               channel, h, w, oh, ow, max_displacement - pad_size);
+            hipLaunchKernelGGL((corr_forward_k1_rows<4, Epi>), grid, dim3(64, 9, 1), 0, st, items,
+                               channel, h, w, oh, ow, max_displacement - pad_size, epi);
         }
         return launch_status();
     }
     // any other configuration: the generic kernel, one launch per item
     for (int i = 0; i < nitems; ++i) {
         const int64_t total = (int64_t)per * oc * oh * ow;
-        hipLaunchKernelGGL(corr_forward_generic, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in1s[i],
+        Epi one = epi;
+        if constexpr (!Epi::DENSE) one.stride[0] = epi.stride[i];      // (the generic kernel runs one item per launch)
+        hipLaunchKernelGGL(corr_forward_generic<Epi>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in1s[i],
                            in2s[i], outs[i], per, channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride1,
-                           stride2, dr);
+                           stride2, dr, one);
         if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     }
     return VFI_OK;
@@ -1082,7 +1152,18 @@ extern "C" int vfi_correlation_forward(const float* input1, const float* input2,
                                         int stride1, int stride2, vfi_stream_t stream) {
     if (batch <= 0 || !input1 || !input2 || !output) return VFI_ERR_SHAPE;
     return correlation_forward_items(&input1, &input2, &output, 1, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                                     stride1, stride2, stream);
+                                     stride1, stride2, stream, CorrPlain{});
+}
+
+// vfi_correlation_forward with PWC-Net's LeakyReLU applied to every mean as it is stored, into an output whose images lie
+// output_batch_stride elements apart: the same kernels with the epilogue compiled in.
+extern "C" int vfi_correlation_lrelu_forward(const float* input1, const float* input2, float* output, int64_t output_batch_stride,
+                                              int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                                              int max_displacement, int stride1, int stride2, float negative_slope,
+                                              vfi_stream_t stream) {
+    if (batch <= 0 || !input1 || !input2 || !output) return VFI_ERR_SHAPE;
+    return correlation_forward_items(&input1, &input2, &output, 1, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                                     stride1, stride2, stream, CorrLrelu{{output_batch_stride, output_batch_stride}, negative_slope});
 }
 
 // Two correlation calls of equal shape in ONE launch -- the same pyramid level of the two flow networks PWCDCNet runs for a
@@ -1098,7 +1179,22 @@ extern "C" int vfi_correlation_forward_pair(const float* input1_a, const float* 
     const float* in2s[2] = {input2_a, input2_b};
     float* outs[2] = {output_a, output_b};
     return correlation_forward_items(in1s, in2s, outs, 2, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                                     stride1, stride2, stream);
+                                     stride1, stride2, stream, CorrPlain{});
+}
+
+extern "C" int vfi_correlation_lrelu_forward_pair(const float* input1_a, const float* input2_a, float* output_a,
+                                                   int64_t output_a_batch_stride,
+                                                   const float* input1_b, const float* input2_b, float* output_b,
+                                                   int64_t output_b_batch_stride,
+                                                   int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                                                   int max_displacement, int stride1, int stride2, float negative_slope,
+                                                   vfi_stream_t stream) {
+    if (batch <= 0) return VFI_ERR_SHAPE;
+    const float* in1s[2] = {input1_a, input1_b};
+    const float* in2s[2] = {input2_a, input2_b};
+    float* outs[2] = {output_a, output_b};
+    return correlation_forward_items(in1s, in2s, outs, 2, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                                     stride1, stride2, stream, CorrLrelu{{output_a_batch_stride, output_b_batch_stride}, negative_slope});
 }
 
 extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input2, void* output, int batch, int channel,
@@ -1131,12 +1227,20 @@ extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input
     return launch_status();
 }
 
+// a mask the entries accept: y present, a valid slope, images at least their own planes apart
+static bool corr_grad_ok(const CorrGrad<true>& a, int64_t image) {
+    return a.y && corr_slope_ok(a.slope) && a.ystride >= image && a.gstride >= image;
+}
+
 // One gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1.  float, or the
-// reference's at::Half instantiation.  The callers have run corr_check.
+// reference's at::Half instantiation.  `act` (float only): gradOutput goes through LeakyReLU's derivative as it is loaded --
+// the same launches of the masked kernels.  The callers have run corr_check.
 template <class T>
 static int corr_backward_one(bool second, const T* other, const T* gout, T* gin, int batch, int channel, int h, int w, int oc, int oh,
-                             int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st) {
+                             int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st,
+                             const CorrGrad<true>* act = nullptr) {
     constexpr bool HALF = std::is_same<T, __half>::value;
+    if (HALF && act) return VFI_ERR_SHAPE;
     if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
         // PWC-Net's configuration: the pixel-owns-its-gradOutput kernels; channel groups over blockIdx.z fill the chip.
         // (The half kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.)
@@ -1147,6 +1251,9 @@ static int corr_backward_one(bool second, const T* other, const T* gout, T* gin,
             if constexpr (HALF)
                 hipLaunchKernelGGL(second ? corr_backward_k1_f16<true> : corr_backward_k1_f16<false>, grid, dim3(128), 0, st, other, gout,
                                    gin, channel, h, w, groups, ch_per_group);
+            else if (act)
+                hipLaunchKernelGGL(second ? corr_lrelu_backward_k1<true> : corr_lrelu_backward_k1<false>, grid, dim3(256), 0, st, other,
+                                   gout, gin, channel, h, w, groups, ch_per_group, *act);
             else
                 hipLaunchKernelGGL(second ? corr_backward_k1<true> : corr_backward_k1<false>, grid, dim3(256), 0, st, other, gout, gin,
                                    channel, h, w, groups, ch_per_group);
@@ -1159,6 +1266,9 @@ static int corr_backward_one(bool second, const T* other, const T* gout, T* gin,
     if constexpr (HALF)
         hipLaunchKernelGGL(second ? corr_backward_f16<true> : corr_backward_f16<false>, grid, block, 0, st, other, gout, gin, batch,
                            channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
+    else if (act)
+        hipLaunchKernelGGL(second ? corr_lrelu_backward<true> : corr_lrelu_backward<false>, grid, block, 0, st, other, gout, gin, batch,
+                           channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr, *act);
     else
         hipLaunchKernelGGL(second ? corr_backward<true> : corr_backward<false>, grid, block, 0, st, other, gout, gin, batch, channel,
                            h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
@@ -1169,20 +1279,21 @@ static int corr_backward_one(bool second, const T* other, const T* gout, T* gin,
 template <class T>
 static int correlation_backward_any(const T* input1, const T* input2, const T* gradoutput, T* gradinput1, T* gradinput2, int batch,
                                     int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
-                                    int stride2, vfi_stream_t stream) {
+                                    int stride2, vfi_stream_t stream, const CorrGrad<true>* act = nullptr) {
     constexpr bool HALF = std::is_same<T, __half>::value;
     int oc, oh, ow;
     if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
                    stride1, stride2, true, &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
+    if (act && !corr_grad_ok(*act, (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
     const int64_t total = (int64_t)batch * channel * h * w;
     if (HALF && (total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     if (corr_backward_one(false, input2, gradoutput, gradinput1, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
-                          max_displacement, stride2, st) != VFI_OK)
+                          max_displacement, stride2, st, act) != VFI_OK)
         return VFI_ERR_LAUNCH;
     return corr_backward_one(true, input1, gradoutput, gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
-                             max_displacement, stride2, st);
+                             max_displacement, stride2, st, act);
 }
 
 extern "C" int vfi_correlation_backward(const float* input1, const float* input2, const float* gradoutput,
@@ -1193,35 +1304,48 @@ extern "C" int vfi_correlation_backward(const float* input1, const float* input2
                                     max_displacement, stride1, stride2, stream);
 }
 
+// vfi_correlation_backward of gradOutput masked by LeakyReLU's derivative: the same two launches of the masked kernels.
+extern "C" int vfi_correlation_lrelu_backward(const float* input1, const float* input2, const float* y, int64_t y_batch_stride,
+                                               const float* gradoutput, int64_t gradoutput_batch_stride, float* gradinput1,
+                                               float* gradinput2, int batch, int channel, int h, int w, int pad_size,
+                                               int kernel_size, int max_displacement, int stride1, int stride2,
+                                               float negative_slope, vfi_stream_t stream) {
+    const CorrGrad<true> act = {y, y_batch_stride, gradoutput_batch_stride, negative_slope};
+    return correlation_backward_any(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                    max_displacement, stride1, stride2, stream, &act);
+}
+
 // The backward of two calls of equal shape -- the same pyramid level of the two flow networks of a frame pair, whose forward
 // is vfi_correlation_forward_pair -- with any subset of the four gradients.  PWC-Net's configuration: the requested
 // gradients are the roles of ONE corr_backward_k1_pair launch, and the channel groups are sized on the whole launch
 // (tiles x batch x roles).  Any other configuration, or role x batch x groups beyond a grid's z: one launch per requested
 // gradient with the kernels vfi_correlation_backward uses.  Either way a gradient's bits are that entry's.
-extern "C" int vfi_correlation_backward_pair(
-    const float* input1_a, const float* input2_a, const float* gradoutput_a, float* gradinput1_a, float* gradinput2_a,
-    const float* input1_b, const float* input2_b, const float* gradoutput_b, float* gradinput1_b, float* gradinput2_b,
-    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
-    vfi_stream_t stream) {
+// `acts` (or NULL): the two items' masks -- vfi_correlation_lrelu_backward_pair, the same compaction and launches with the
+// masked kernels; a role carries its item's mask.
+static int correlation_backward_pair_any(
+    const float* const (&in1)[2], const float* const (&in2)[2], const float* const (&go)[2], float* const (&gi)[2][2],
+    const CorrGrad<true>* acts, int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
+    int stride1, int stride2, vfi_stream_t stream) {
     int oc, oh, ow;
     if (corr_check({}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, true, &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
-    const float* in1[2] = {input1_a, input1_b};
-    const float* in2[2] = {input2_a, input2_b};
-    const float* go[2] = {gradoutput_a, gradoutput_b};
-    float* gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
+    if (acts && !corr_slope_ok(acts[0].slope)) return VFI_ERR_SHAPE;
     CorrBwdRoles roles = {};
+    CorrBwdMasks masks = {};
     int nroles = 0;
     for (int i = 0; i < 2; ++i) {
         if (!gi[i][0] && !gi[i][1]) continue;               // (nothing asked of this item: its inputs may be NULL)
         if (!in1[i] || !in2[i] || !go[i]) return VFI_ERR_SHAPE;
+        if (acts && !corr_grad_ok(acts[i], (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
         for (int s = 0; s < 2; ++s) {
             if (!gi[i][s]) continue;
             for (int k = 0; k < nroles; ++k)
                 if (roles.r[k].gin == gi[i][s]) return VFI_ERR_SHAPE;
+            if (acts) { masks.y[nroles] = acts[i].y; masks.ystride[nroles] = acts[i].ystride; masks.gstride[nroles] = acts[i].gstride; }
             roles.r[nroles++] = {s ? in1[i] : in2[i], go[i], gi[i][s], s};      // gradInput1 reads input2, gradInput2 input1
         }
     }
+    if (acts) masks.slope = acts[0].slope;
     if (nroles == 0) return VFI_OK;
     hipStream_t st = (hipStream_t)stream;
     if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {
@@ -1230,15 +1354,48 @@ extern "C" int vfi_correlation_backward_pair(
         if (groups) {
             roles.per_role = batch * groups;
             const dim3 grid((w + 63) / 64, (h + 3) / 4, nroles * roles.per_role);
-            hipLaunchKernelGGL(corr_backward_k1_pair, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
+            if (acts) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair, grid, dim3(256), 0, st, roles, masks, channel, h, w, groups, ch_per_group);
+            else hipLaunchKernelGGL(corr_backward_k1_pair, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
             return launch_status();
         }
     }
-    for (int k = 0; k < nroles; ++k)
+    for (int k = 0; k < nroles; ++k) {
+        const CorrGrad<true> act = {masks.y[k], masks.ystride[k], masks.gstride[k], masks.slope};
         if (corr_backward_one(roles.r[k].second != 0, roles.r[k].other, roles.r[k].gout, roles.r[k].gin, batch, channel, h, w, oc, oh,
-                              ow, pad_size, kernel_size, max_displacement, stride2, st) != VFI_OK)
+                              ow, pad_size, kernel_size, max_displacement, stride2, st, acts ? &act : nullptr) != VFI_OK)
             return VFI_ERR_LAUNCH;
+    }
     return VFI_OK;
+}
+
+extern "C" int vfi_correlation_backward_pair(
+    const float* input1_a, const float* input2_a, const float* gradoutput_a, float* gradinput1_a, float* gradinput2_a,
+    const float* input1_b, const float* input2_b, const float* gradoutput_b, float* gradinput1_b, float* gradinput2_b,
+    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+    vfi_stream_t stream) {
+    const float* const in1[2] = {input1_a, input1_b};
+    const float* const in2[2] = {input2_a, input2_b};
+    const float* const go[2] = {gradoutput_a, gradoutput_b};
+    float* const gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
+    return correlation_backward_pair_any(in1, in2, go, gi, nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                                         stride1, stride2, stream);
+}
+
+extern "C" int vfi_correlation_lrelu_backward_pair(
+    const float* input1_a, const float* input2_a, const float* y_a, int64_t y_a_batch_stride, const float* gradoutput_a,
+    int64_t gradoutput_a_batch_stride, float* gradinput1_a, float* gradinput2_a,
+    const float* input1_b, const float* input2_b, const float* y_b, int64_t y_b_batch_stride, const float* gradoutput_b,
+    int64_t gradoutput_b_batch_stride, float* gradinput1_b, float* gradinput2_b,
+    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+    float negative_slope, vfi_stream_t stream) {
+    const float* const in1[2] = {input1_a, input1_b};
+    const float* const in2[2] = {input2_a, input2_b};
+    const float* const go[2] = {gradoutput_a, gradoutput_b};
+    float* const gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
+    const CorrGrad<true> acts[2] = {{y_a, y_a_batch_stride, gradoutput_a_batch_stride, negative_slope},
+                                    {y_b, y_b_batch_stride, gradoutput_b_batch_stride, negative_slope}};
+    return correlation_backward_pair_any(in1, in2, go, gi, acts, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                                         stride1, stride2, stream);
 }
 
 extern "C" int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,

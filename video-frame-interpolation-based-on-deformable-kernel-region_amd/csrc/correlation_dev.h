@@ -69,6 +69,46 @@ __device__ __forceinline__ void corr_store_mean(int channel, Store&& store) {
     else store([&](float v) { return v / nelems; });
 }
 
+// What a float forward kernel does with a mean as it stores it, and where plane k of image b begins in the output: a
+// compile-time choice, so the plain instances are the kernels they were.  CorrPlain: the mean as it is, dense images.
+// CorrLrelu: PWC-Net's LeakyReLU on the mean, y = v > 0 ? v : v * slope -- ONE multiplication of the value the plain kernel
+// stores (NaN stays NaN, -0 becomes -0 * slope: torch's leaky_relu in float) -- into an output whose images lie
+// stride[item] elements apart while the planes of an image stay contiguous (the first channels of a concatenation buffer).
+struct CorrPlain {
+    static constexpr bool DENSE = true;
+    __device__ __forceinline__ float operator()(float v) const { return v; }
+    __device__ __forceinline__ int64_t plane(int, int b, int oc, int k, int oh, int ow) const { return ((int64_t)b * oc + k) * oh * ow; }
+};
+struct CorrLrelu {
+    static constexpr bool DENSE = false;
+    int64_t stride[2];
+    float slope;
+    __device__ __forceinline__ float operator()(float v) const { return v > 0.0f ? v : v * slope; }
+    __device__ __forceinline__ int64_t plane(int item, int b, int, int k, int oh, int ow) const {
+        return (int64_t)b * stride[item] + (int64_t)k * oh * ow;
+    }
+};
+
+// What a float backward kernel does with a gradOutput value as it loads it, for one gradient (workgroup-uniform scalars).
+// MASK == false: nothing, dense gradOutput.  MASK == true: LeakyReLU's derivative through the saved ACTIVATED output y (its
+// sign is the pre-activation's for any slope > 0): g' = y > 0 ? g : g * slope, rounded to float before the term that uses
+// it, so the gradient is the plain kernel's fed g'.  Images of y and of gradOutput lie ystride / gstride elements apart,
+// the planes of an image contiguous (gradOutput: the narrow() view that torch.cat's backward hands down).
+template <bool MASK_>
+struct CorrGrad {
+    static constexpr bool MASK = MASK_;
+    const float* y;
+    int64_t ystride, gstride;
+    float slope;
+    // value g whose output position holds yv
+    __device__ __forceinline__ float operator()(float g, float yv) const {
+        if constexpr (MASK_) return yv > 0.0f ? g : g * slope;      // (a skipped term: 0 * slope = +0, slope finite and positive)
+        else return g;
+    }
+};
+// the masks of a vfi_correlation_lrelu_backward_pair launch, by role (CorrBwdRoles)
+struct CorrBwdMasks { const float* y[4]; int64_t ystride[4], gstride[4]; float slope; };
+
 // The gradients of one vfi_correlation_backward_pair launch: a role is one requested gradient of one item -- the map its
 // window is staged from, the item's gradOutput, where it goes, and which of the two gradients it is.  The host compacts the
 // requested ones (at most four) to the front; role i owns blockIdx.z in [i * per_role, (i + 1) * per_role).

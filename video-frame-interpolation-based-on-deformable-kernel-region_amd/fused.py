@@ -3,7 +3,10 @@ points of libvfi_hip.so.  Same names and argument meaning as the reference's sta
 (`networks/DAIN_slowmotion.py:204-216, 301-335`, `PWCNet/PWCNet.py:159-199`,
 `demo_MiddleBury.py:280-318, 350-388`).  `warp`, `warp_corr` and `corr_pair` are differentiable (PWC-Net's glue, trained
 with the flow network: the backward is vfi_pwc_warp_backward, for `warp_corr` also the correlation backward, and for
-`corr_pair` one vfi_correlation_backward_pair call for both networks).
+`corr_pair` one vfi_correlation_backward_pair call for both networks).  `corr_lrelu`, `warp_corr_lrelu` and
+`corr_pair_lrelu` are their twins with PWC-Net's LeakyReLU inside the correlation's launch, forward and backward
+(vfi_correlation_lrelu_*): in inference they can write into a channel slice of the concatenation buffer, in training the
+backward masks the gradient as it loads it and reads torch.cat's strided gradient where it lies.
 `FlowProject` / `FlowProject_directions` and `FilterInterpolate` are differentiable too, so DAIN's synthesis loss reaches
 the flow and filter networks (networks/DAIN.py:215-238): the projection's backward is the reference's per-item kernel,
 the blend's is vfi_filterinterp_blend_backward (both directions, the blend weights folded in, no image gradient unless
@@ -495,6 +498,84 @@ def corr_pair(c1_a, c2_a, c1_b, c2_b):
     if _wants_grad(c1_a, c2_a, c1_b, c2_b):
         return _CorrPair.apply(c1_a, c2_a, c1_b, c2_b)
     return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
+
+
+class _CorrLrelu(torch.autograd.Function):
+    """`_Corr` with PWC-Net's LeakyReLU in the correlation's own launch.  The saved tensor is the activated output y; the
+    backward is one vfi_correlation_lrelu_backward call that masks the gradient as it loads it and reads a strided
+    gradient (the narrow() view of torch.cat's backward) where it lies."""
+
+    @staticmethod
+    def forward(ctx, c1, c2, slope):
+        y = cabi.correlation_lrelu_forward(c1, c2, 4, 1, 4, 1, 1, slope)
+        ctx.save_for_backward(c1, c2, y)
+        ctx.slope = slope
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        c1, c2, y = ctx.saved_tensors
+        g1, g2 = cabi.correlation_lrelu_backward(c1, c2, y, grad_out, 4, 1, 4, 1, 1, ctx.slope)
+        return (g1 if ctx.needs_input_grad[0] else None), (g2 if ctx.needs_input_grad[1] else None), None
+
+
+class _CorrPairLrelu(torch.autograd.Function):
+    """`_CorrPair` with the LeakyReLU fused into both directions: one forward launch, ONE
+    vfi_correlation_lrelu_backward_pair call for the gradients autograd needs.  A cost volume the loss did not use arrives
+    as None, and its item's gradients are None at no cost."""
+
+    @staticmethod
+    def forward(ctx, c1_a, c2_a, c1_b, c2_b, slope):
+        y_a, y_b = cabi.correlation_lrelu_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1, slope)
+        ctx.save_for_backward(c1_a, c2_a, c1_b, c2_b, y_a, y_b)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)
+        return y_a, y_b
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_a, grad_b):
+        c1_a, c2_a, c1_b, c2_b, y_a, y_b = ctx.saved_tensors
+        return cabi.correlation_lrelu_backward_pair(c1_a, c2_a, y_a, grad_a, c1_b, c2_b, y_b, grad_b, 4, 1, 4, 1, 1, ctx.slope,
+                                                    want=tuple(ctx.needs_input_grad[:4])) + (None,)
+
+
+def _no_out_in_grad_mode(out, what):
+    if out is not None:
+        raise RuntimeError("%s: out= is for inference; under autograd the result is the tensor the backward saves" % what)
+
+
+def corr_lrelu(c1, c2, negative_slope=0.1, out=None):
+    """`self.leakyRELU(self.corr(c1, c2))` of PWCDCNet.forward (PWCNet/PWCNet.py:230-231) from the correlation's launch:
+    the bits of F.leaky_relu on the correlation's output.  Differentiable when grad mode is on and an input requires grad
+    (one backward call, which masks the gradient as it loads it and takes torch.cat's strided gradient without a copy).
+    Otherwise the plain launch, and out= may name where to write: buf[:, k:k + 81] of the contiguous NCHW buffer the
+    reference would get from `torch.cat((corr, ...), 1)`."""
+    if _wants_grad(c1, c2):
+        _no_out_in_grad_mode(out, "corr_lrelu")
+        return _CorrLrelu.apply(c1, c2, float(negative_slope))
+    return cabi.correlation_lrelu_forward(c1, c2, 4, 1, 4, 1, 1, negative_slope, out=out)
+
+
+def warp_corr_lrelu(c1, c2, flo, align_corners=True, negative_slope=0.1, out=None):
+    """`self.leakyRELU(self.corr(c1, self.warp(c2, flo)))` (PWCNet/PWCNet.py:244-248 ...): `warp`, then `corr_lrelu`.
+    Differentiable as `warp_corr` is; in inference out= as `corr_lrelu`'s."""
+    if _wants_grad(c1, c2, flo):
+        _no_out_in_grad_mode(out, "warp_corr_lrelu")
+        return _CorrLrelu.apply(c1, warp(c2, flo, align_corners), float(negative_slope))
+    return cabi.correlation_lrelu_forward(c1, warp(c2, flo, align_corners), 4, 1, 4, 1, 1, negative_slope, out=out)
+
+
+def corr_pair_lrelu(c1_a, c2_a, c1_b, c2_b, negative_slope=0.1, out=None):
+    """`corr_pair` followed by the reference's LeakyReLU on both cost volumes, from the one launch.  Differentiable when
+    grad mode is on and one of the four inputs requires grad: ONE backward call for the gradients that are needed, each
+    bit-equal to `F.leaky_relu(corr_pair(...))`'s.  Otherwise the plain launch; out= is then a pair of destinations
+    (either may be None), each as `corr_lrelu`'s."""
+    if _wants_grad(c1_a, c2_a, c1_b, c2_b):
+        _no_out_in_grad_mode(out, "corr_pair_lrelu")
+        return _CorrPairLrelu.apply(c1_a, c2_a, c1_b, c2_b, float(negative_slope))
+    return cabi.correlation_lrelu_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1, negative_slope, out=out)
 
 
 class _PartLoss(torch.autograd.Function):
