@@ -78,6 +78,23 @@ int vfi_filterinterp_forward_ori_multi(const float* input1, const float* const* 
                                        vfi_strides s1, vfi_strides s2, vfi_strides s3,
                                        vfi_stream_t stream);
 
+/* The same call with a destination layout of its own: outputs[t] holds, bit for bit, what
+ * vfi_filterinterp_forward_ori_multi writes, addressed with s_out instead of s1.  For a caller that needs the warps inside a
+ * wider tensor -- the input of the reference's rectifyNet is torch.cat((cur_output, ref0, ref2, offsets, filters, ctx0, ctx2),
+ * dim=1), networks/DAIN_slowmotion.py:177-182 -- and would otherwise copy every one of them once more: outputs[t] is then
+ * the first element of a channel slice of that buffer.
+ * Contract of s_out: w stride 1; s_out.h == s1.h (a pixel's offset inside a plane is shared by the load and the store:
+ * any other row stride returns VFI_ERR_SHAPE, it is not served by a slower kernel); s_out.b and s_out.c are free.  A
+ * contiguous [B, C', h, w] buffer meets it whenever input1 is contiguous or itself a channel slice of such a tensor.
+ * Every store is one float: outputs[t] needs 4-byte alignment only.  The kernel and the window class a tile takes depend on
+ * the inputs alone (same kernels, same pairing of the flows, any nflows >= 1).  The destinations must not overlap input1,
+ * the flows, input3 or each other: documented, not checked, as for the entry above.  s_out == s1 is that entry. */
+int vfi_filterinterp_forward_ori_multi_to(const float* input1, const float* const* flows, const float* input3,
+                                          float* const* outputs, int nflows,
+                                          int batch, int channel, int h, int w, int filter_channels,
+                                          vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides s_out,
+                                          vfi_stream_t stream);
+
 /* The backward of that call as the context path needs it (networks/DAIN.py:544-552, networks/DAIN_slowmotion.py:311-317
  * detach flow and filter): gradinput1 = the sum over t < nflows of the IMAGE gradient of
  * vfi_filterinterp_forward_ori(., flows[t], input3) for gradoutputs[t].  The image itself is not an argument: its gradient
@@ -455,7 +472,10 @@ int vfi_depthflowprojection_backward_up4(const float* flow_q, const float* const
 /* FilterInterpolate (networks/DAIN_slowmotion.py:324-335, DAIN.py:560-573): out0 = A1(ref0, flow0,
  * filt0), out2 = A1(ref2, flow2, filt2), blend = out0 * w0 + out2 * w2 (products rounded
  * separately, as torch's three elementwise ops).  out0 / out2 may be NULL.  ref0/ref2, flow0/flow2
- * and filt0/filt2 share strides pairwise; blend/out0/out2 share s_out. */
+ * and filt0/filt2 share strides pairwise; blend/out0/out2 share s_out, which may be any layout with w
+ * stride 1 (the three may be channel slices of one wider buffer).  filter_channels == 16 with both
+ * out0 and out2 given and s_out.h == s_ref.h runs the LDS-staged kernels, anything else the per-pixel
+ * gather: the same bits either way. */
 int vfi_filterinterp_blend_forward(const float* ref0, const float* ref2,
                                    const float* flow0, const float* flow2,
                                    const float* filt0, const float* filt2,

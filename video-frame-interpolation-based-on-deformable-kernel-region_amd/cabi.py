@@ -32,6 +32,7 @@ SIGNATURES = {
     "vfi_filterinterp_backward_ori": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_f16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_forward_ori_multi_to": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_backward_ori_image_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_defor": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                        Strides, _p],
@@ -194,6 +195,34 @@ def filterinterp_forward_ori_multi(input1, flows, input3, outputs):
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_filterinterp_forward_ori_multi(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1),
                                                                 _st(input1), _st(flows[0]), _st(input3), _stream(input1)))
+
+
+def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs):
+    """filterinterp_forward_ori_multi into destinations with a layout of their own: outputs[t] (input1's shape; typically
+    buf_t[:, k:k + C] of a wider contiguous buffer) receives the same bits.  The destinations share one layout with w
+    stride 1 and input1's row stride -- anything else is refused here, before the call; batch and channel strides are
+    free.  They must not overlap input1 or each other (not checked)."""
+    n = len(flows)
+    if n == 0 or len(outputs) != n:
+        return 1
+    for fl, out in zip(flows, outputs):
+        if _fi_checks(input1, fl, input3, None) is None or not _same_strides(fl, flows[0]):
+            return 1
+        if out.dim() != 4 or out.shape != input1.shape or out.stride(3) != 1 or not _same_strides(out, outputs[0]):
+            return 1
+        # (the row stride of a one-row tensor addresses nothing)
+        if input1.size(2) != 1 and out.stride(2) != input1.stride(2):
+            return 1
+    for t in (input3, *flows, *outputs):
+        _dev(t)
+    b, c, h, w = input1.shape
+    so = _st(outputs[0])
+    so.h = input1.stride(2)
+    fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
+    op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outputs])
+    with torch.cuda.device(_dev(input1)):
+        return _finish(lib().vfi_filterinterp_forward_ori_multi_to(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1),
+                                                                   _st(input1), _st(flows[0]), _st(input3), so, _stream(input1)))
 
 
 def filterinterp_forward_ori_f16(input1, input2, input3, output, direct=False):

@@ -33,11 +33,14 @@ FiSplit fi_channel_split(int ntiles, int channel, double prologue) {
 
 // ------------------------------------------------------------------ forward, _ori
 
-template <bool FS4>
+// DST = vfi_strides (fi_dst, filterinterp_dev.h): out is addressed with so's batch and channel strides; no DST: with s1's
+template <bool FS4, class... DST>
 __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     float* __restrict__ out, int channel, int h, int w, int fs,
-    vfi_strides s1, vfi_strides s2, vfi_strides s3) {
+    vfi_strides s1, vfi_strides s2, vfi_strides s3, DST... so) {
+    constexpr bool TO = sizeof...(DST) != 0;
+    const int64_t ob = fi_dst(s1, so...).b, oc = fi_dst(s1, so...).c;
     const int x = blockIdx.x * VFI_TX + threadIdx.x;
     const int y = blockIdx.y * VFI_TY + threadIdx.y;
     if (x >= w || y >= h) return;
@@ -47,9 +50,9 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct(
     const float x2 = (float)x + fx;
     const float y2 = (float)y + fy;
     const float* img = in1 + (int64_t)b * s1.b;
-    float* dst = out + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
+    float* dst = out + (int64_t)b * ob + (int64_t)y * s1.h + x;
     if (!fi_valid(fx, fy, x2, y2, w, h)) {                  // (fi_point changes this kernel's code)
-        fi_copy_through(img + (int64_t)y * s1.h + x, dst, 0, channel, s1.c);
+        fi_copy_through_to<TO>(img + (int64_t)y * s1.h + x, dst, 0, channel, s1.c, oc);
         return;
     }
     const FiGeom g = fi_cell(FiPoint{true, x2, y2});
@@ -62,12 +65,12 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_forward_ori_direct(
         float f[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) f[k] = fpx[(int64_t)k * s3.c];
-        fi4_channels_direct(img, dst, 0, channel, s1.c, (int)s1.h, h, w, L, T, f, alpha, beta);
+        fi4_channels_direct<TO>(img, dst, 0, channel, s1.c, oc, (int)s1.h, h, w, L, T, f, alpha, beta);
     } else {
         for (int c = 0; c < channel; ++c) {
             float q[4];
             quadrants_generic(img + (int64_t)c * s1.c, fpx, s3.c, (int)s1.h, h, w, fs, L, T, ix, iy, q);
-            dst[(int64_t)c * s1.c] = blend4(alpha, beta, q[0], q[1], q[2], q[3]);
+            dst[(int64_t)c * oc] = blend4(alpha, beta, q[0], q[1], q[2], q[3]);
         }
     }
 }
@@ -749,40 +752,53 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_backward_defor(
 
 using namespace vfi;
 
+int vfi::launch_fi_ori_direct(const float* input1, const float* input2, const float* input3, float* output, int batch,
+                              int channel, int h, int w, int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
+                              vfi_strides so, vfi_stream_t stream) {
+    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
+    if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
+    if (so.h != s1.h) return VFI_ERR_SHAPE;                  // one in-plane offset per pixel for loads and stores
+    const int fs = fi_filter_size(filter_channels);
+    const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
+    hipStream_t st = (hipStream_t)stream;
+    const bool to = so.b != s1.b || so.c != s1.c;           // (a destination laid out as input1: the instances without a second set of strides)
+#define FI_LAUNCH(KERNEL, ...) hipLaunchKernelGGL(KERNEL, grid, block, 0, st, input1, input2, input3, output, \
+        channel, h, w, fs, s1, s2, s3, ##__VA_ARGS__)
+    if (fs == 4) { if (to) FI_LAUNCH((fi_forward_ori_direct<true, vfi_strides>), so); else FI_LAUNCH(fi_forward_ori_direct<true>); }
+    else { if (to) FI_LAUNCH((fi_forward_ori_direct<false, vfi_strides>), so); else FI_LAUNCH(fi_forward_ori_direct<false>); }
+#undef FI_LAUNCH
+    return launch_status();
+}
+
 extern "C" int vfi_filterinterp_forward_ori_direct(const float* input1, const float* input2, const float* input3,
                                                     float* output, int batch, int channel, int h, int w,
                                                     int filter_channels, vfi_strides s1, vfi_strides s2,
                                                     vfi_strides s3, vfi_stream_t stream) {
+    return launch_fi_ori_direct(input1, input2, input3, output, batch, channel, h, w, filter_channels, s1, s2, s3, s1, stream);
+}
+
+int vfi::fi_forward_ori_to(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                           int h, int w, int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so,
+                           vfi_stream_t stream) {
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
     if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
+    if (so.h != s1.h) return VFI_ERR_SHAPE;
     const int fs = fi_filter_size(filter_channels);
-    const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
-    hipStream_t st = (hipStream_t)stream;
-    if (fs == 4)
-        hipLaunchKernelGGL(fi_forward_ori_direct<true>, grid, block, 0, st, input1, input2, input3, output,
-                           channel, h, w, fs, s1, s2, s3);
-    else
-        hipLaunchKernelGGL(fi_forward_ori_direct<false>, grid, block, 0, st, input1, input2, input3, output,
-                           channel, h, w, fs, s1, s2, s3);
-    return launch_status();
+    if (fs == 4) {
+        const int r = launch_fi_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, so, stream);
+        if (r != FI_DECLINED) return r;
+    } else if (fs * fs == filter_channels) {
+        const int r = launch_fi_ori_lds_n(input1, input2, input3, output, batch, channel, h, w, fs, s1, s2, s3, so, stream);
+        if (r != FI_DECLINED) return r;
+    }
+    return launch_fi_ori_direct(input1, input2, input3, output, batch, channel, h, w, filter_channels, s1, s2, s3, so, stream);
 }
 
 extern "C" int vfi_filterinterp_forward_ori(const float* input1, const float* input2, const float* input3,
                                              float* output, int batch, int channel, int h, int w,
                                              int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
                                              vfi_stream_t stream) {
-    if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
-    if (!input1 || !input2 || !input3 || !output) return VFI_ERR_SHAPE;
-    const int fs = fi_filter_size(filter_channels);
-    if (fs == 4) {
-        const int r = launch_fi_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream);
-        if (r != FI_DECLINED) return r;
-    } else if (fs * fs == filter_channels) {
-        const int r = launch_fi_ori_lds_n(input1, input2, input3, output, batch, channel, h, w, fs, s1, s2, s3, stream);
-        if (r != FI_DECLINED) return r;
-    }
-    return vfi_filterinterp_forward_ori_direct(input1, input2, input3, output, batch, channel, h, w,
-                                               filter_channels, s1, s2, s3, stream);
+    return fi_forward_ori_to(input1, input2, input3, output, batch, channel, h, w, filter_channels, s1, s2, s3, s1, stream);
 }
 
 extern "C" int vfi_filterinterp_backward_ori(const float* input1, const float* input2, const float* input3,

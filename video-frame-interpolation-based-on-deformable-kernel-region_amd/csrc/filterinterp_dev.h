@@ -70,6 +70,29 @@ template <typename E>
 __device__ __forceinline__ void fi_copy_through(const E* src, E* dst, unsigned pix, int c0, int c1, int64_t cs) {
     for (int c = c0; c < c1; ++c) dst[(int64_t)c * cs + pix] = src[(int64_t)c * cs + pix];
 }
+// ... and, TO, into a destination whose planes are cso_to apart (the *_to entry points: the output is a channel slice of a
+// wider buffer; its rows are as far apart as the source's, so the pixel's offset inside a plane is the same on both sides).
+// !TO: cso_to is not looked at and the function is the one above.  (TO is a template parameter of every helper that takes
+// the two strides, not a second value that happens to be equal: a helper is optimised before it is inlined, and with two
+// strides it comes out as other code even where its caller passes the same value twice.)
+// FI_CSO, the destination's plane distance inside such a helper, is spelled as this expression wherever it is used: a local
+// variable holding it, captured by the channel loops' lambdas, changed the dense blend instance and the multi-flow kernel.
+#define FI_CSO (TO ? cso_to : cs)
+template <bool TO, typename E>
+__device__ __forceinline__ void fi_copy_through_to(const E* src, E* dst, int c0, int c1, int64_t cs, int64_t cso_to) {
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * FI_CSO] = src[(int64_t)c * cs];
+}
+template <bool TO, typename E>
+__device__ __forceinline__ void fi_copy_through_to(const E* src, E* dst, unsigned pix, int c0, int c1, int64_t cs, int64_t cso_to) {
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * FI_CSO + pix] = src[(int64_t)c * cs + pix];
+}
+
+// Where a forward kernel of the _ori family writes.  Its last parameters are a pack `DST... so`: empty in the dense instances
+// (the output is laid out as input1 -- their parameter lists and their code are what they were before a destination could
+// have a layout of its own), one vfi_strides in the *_to instances.  Contract: so.h == s1.h, so that a pixel's offset
+// inside a plane is one register shared by the load and the store; batch and channel strides are free.
+__device__ __forceinline__ const vfi_strides& fi_dst(const vfi_strides& s1) { return s1; }
+__device__ __forceinline__ const vfi_strides& fi_dst(const vfi_strides&, const vfi_strides& so) { return so; }
 
 // One pixel's 4x4 window, fs == 4: every quadrant is 2x2.  v = the 16 image
 // taps (row major), f = the 16 filter taps.  Accumulation order inside each
@@ -219,9 +242,10 @@ __device__ __forceinline__ float fi4_value(const float* __restrict__ p, const un
     return blend4(alpha, beta, TL, TR, BL, BR);
 }
 
-// channel loop of one valid pixel gathering straight from global memory
+// channel loop of one valid pixel gathering straight from global memory; TO: the destination's planes are cso_to apart
+template <bool TO>
 __device__ __forceinline__ void fi4_channels_direct(const float* __restrict__ img, float* __restrict__ dst,
-                                                    int c0, int c1, int64_t cs, int hs, int h, int w,
+                                                    int c0, int c1, int64_t cs, int64_t cso_to, int hs, int h, int w,
                                                     int L, int T, const float (&f)[16], float alpha, float beta) {
     // unsigned 32-bit element offsets from a wave-uniform plane pointer: the loads take the
     // scalar-base + vector-offset form, one VGPR per address
@@ -231,7 +255,7 @@ __device__ __forceinline__ void fi4_channels_direct(const float* __restrict__ im
         ro[k] = (unsigned)(clampi(T + k, 0, h - 1) * hs);
         co[k] = (unsigned)clampi(L + k, 0, w - 1);
     }
-    for (int c = c0; c < c1; ++c) dst[(int64_t)c * cs] = fi4_value(img + (int64_t)c * cs, ro, co, f, alpha, beta);
+    for (int c = c0; c < c1; ++c) dst[(int64_t)c * FI_CSO] = fi4_value(img + (int64_t)c * cs, ro, co, f, alpha, beta);
 }
 
 // quadrant sums for a runtime filter size, rows outer / columns inner per quadrant

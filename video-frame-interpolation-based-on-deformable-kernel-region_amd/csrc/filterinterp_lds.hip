@@ -68,8 +68,8 @@ struct FiPixel {
 struct FiBlend { const float* other; float* out; float w0, w2; };
 
 // Channel loop of one workgroup: K staged elements per thread and channel, ring of R slots.
-template <int K, bool BLEND>
-__device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
+template <int K, bool BLEND, bool TO>
+__device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs, int64_t cso_to,
                                                 int c_begin, int c_end, int tid, const FiWindow& win,
                                                 const FiPixel (&px)[FI_PX], float* __restrict__ ring, const FiBlend& bl) {
     constexpr int R = (FI_RING_FLOATS / (K * FI_THREADS)) < FI_RMAX ? (FI_RING_FLOATS / (K * FI_THREADS)) : FI_RMAX;
@@ -113,14 +113,14 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
         if constexpr (BLEND) {
             // (a load inside the counted-vmcnt loop drains the ring -- harmless here: a frame's three windows
             //  were all issued before the loop)
-            const float* bi = bl.other + (int64_t)c * cs;
+            const float* bi = bl.other + (int64_t)c * FI_CSO;
             const float q0 = bi[px[p].pix] * bl.w0, q2 = val * bl.w2;
-            float* bo = bl.out + (int64_t)c * cs;               // (wave-uniform plane pointer + 32-bit pixel offset)
+            float* bo = bl.out + (int64_t)c * FI_CSO;              // (wave-uniform plane pointer + 32-bit pixel offset)
             bo[px[p].pix] = q0 + q2;
         }
     };
     auto compute = [&](int c, int slot) {
-        float* o = out + (int64_t)c * cs;
+        float* o = out + (int64_t)c * FI_CSO;
         const float* base = ring + slot * NP;
         {
 #pragma unroll
@@ -161,10 +161,10 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
         if (px[p].inimg && !px[p].valid)
             for (int c = c_begin; c < c_end; ++c) {
                 const float val = img[(int64_t)c * cs + px[p].pix];
-                out[(int64_t)c * cs + px[p].pix] = val;
+                out[(int64_t)c * FI_CSO + px[p].pix] = val;
                 if constexpr (BLEND) {
-                    const float q0 = bl.other[(int64_t)c * cs + px[p].pix] * bl.w0, q2 = val * bl.w2;
-                    bl.out[(int64_t)c * cs + px[p].pix] = q0 + q2;
+                    const float q0 = bl.other[(int64_t)c * FI_CSO + px[p].pix] * bl.w0, q2 = val * bl.w2;
+                    bl.out[(int64_t)c * FI_CSO + px[p].pix] = q0 + q2;
                 }
             }
 }
@@ -188,8 +188,12 @@ __device__ __forceinline__ void fi_run_channels(const float* __restrict__ img, f
 //    quarter of the DMA instructions.  Same window contents, same tap reads, same bits.  With the 64,000-byte ring of round 3
 //    the coarser units cost two ring slots and the launch 4-8 %; with 81,920 bytes (K = 2 units: four slots) it gains
 //    1.5-3 % on the smooth field and 5 % on the quarter field (profiles/EXPERIMENTS.md).
-template <int K, bool B64, bool DMA16 = false>
-__device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
+//  * TO: the results go to planes cso_to apart (a channel slice of a wider buffer) instead of cs.  The dense instances do not
+//    look at cso_to and compile to what they were; a TO instance keeps a second running plane pointer and gives up the single output
+//    descriptor of the 16-byte-staging instances (its scalar offset would need 4 * cso_to + a plane within 2^31 bytes, which
+//    nobody promises of the destination): a descriptor per output plane, as the 4-byte-staging instances build anyway.
+template <int K, bool B64, bool DMA16 = false, bool TO = false>
+__device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ img, float* __restrict__ out, int64_t cs, int64_t cso_to,
                                                      int c_begin, int c_end, int tid, const FiWindow& win,
                                                      const FiPixel (&px)[FI_PX], float* __restrict__ ring) {
     typedef float v2f __attribute__((ext_vector_type(2)));
@@ -234,7 +238,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         }
     const int last = c_end - 1;
     const float* pdma = img + (int64_t)c_begin * cs;            // plane the next window is staged from
-    float* pout = out + (int64_t)c_begin * cs;                  // plane the next results go to
+    float* pout = out + (int64_t)c_begin * FI_CSO;                 // plane the next results go to
     // 16-byte-staging instances: ONE descriptor per tensor, the plane in the instruction's scalar offset -- one scalar add per
     // channel and tensor instead of a 64-bit pointer add and a descriptor rebuild (a fifth of the loop's scalar instructions;
     // 2 % of the C=196 launch).  The descriptor spans 2^31 - 1 bytes from its base; when the next plane would end beyond that
@@ -242,6 +246,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     // offset with num_records - soffset: a lane whose offset is 0x80000000 is dropped whatever the plane.  (Host: bit 29
     // promises 4 * cs + plane_bytes < 2^31.)
     constexpr bool ONE = DMA16;
+    constexpr bool ONE_OUT = ONE && !TO;
     auto din = buffer_rsrc(pdma, 0x7fffffff);
     auto dout = buffer_rsrc(pout, 0x7fffffff);
     const int cs4 = (int)(cs * 4);
@@ -346,7 +351,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
                 bot = __builtin_elementwise_fma(d[7], F[p][7], bot);
                 val = blend4(px[p].alpha, px[p].beta, top.x, top.y, bot.x, bot.y);
             }
-            if constexpr (ONE) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout, 0);
+            if constexpr (ONE_OUT) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout, 0);
             else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), oplane, soff[p], 0, 0);
         };
         using I0 = std::integral_constant<int, 0>;
@@ -360,8 +365,8 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             if constexpr (p + 1 < FI_PX) reads(std::integral_constant<int, p + 1>{}, I1{});
             if constexpr (p + 2 < FI_PX) reads(std::integral_constant<int, p + 2>{}, I0{});
         });
-        if constexpr (ONE) { next_out(); return; }
-        pout += cs;
+        if constexpr (ONE_OUT) { next_out(); return; }
+        pout += FI_CSO;
     };
     // Two pixels, 4-byte reads: the pipeline is skewed by one pixel across the barrier.  In channel c a wave issues pixel 0's
     // reads, multiplies pixel 1 of channel c - 1 (its taps were read before the barrier and wait in registers), issues pixel
@@ -412,7 +417,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             bot = __builtin_elementwise_fma(d[7], F[p][7], bot);
             val = blend4(px[p].alpha, px[p].beta, top.x, top.y, bot.x, bot.y);
         }
-        if constexpr (ONE) {
+        if constexpr (ONE_OUT) {
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), dout, soff[p], sout - (p ? cs4 : 0), 0);
         } else {
             const auto oplane = buffer_rsrc(plane_ptr, plane_bytes);
@@ -421,7 +426,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
     };
     auto compute_skewed = [&](unsigned so, bool first) {
         rd_all(qa, 0, so);
-        if (!first) fma_store(qb, 1, pout - cs);            // pixel 1 of the previous channel
+        if (!first) fma_store(qb, 1, pout - FI_CSO);           // pixel 1 of the previous channel
         // (at most 15 LDS reads outstanding)
         if constexpr (B64) asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");
         rd_all(qb, 1, so);
@@ -429,8 +434,8 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
         fma_store(qa, 0, pout);
         // pixel 1's taps are in registers before the barrier: the slot may be overwritten after it
         arrived_s(qb, std::integral_constant<int, 0>{});
-        if constexpr (ONE) { next_out(); return; }
-        pout += cs;
+        if constexpr (ONE_OUT) { next_out(); return; }
+        pout += FI_CSO;
     };
     // prologue: the first D windows
     const int n0 = min(D, c_end - c_begin);
@@ -459,7 +464,7 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
             }
             freed = slot; slot = (slot + SLOT == RING) ? 0u : slot + SLOT;
         }
-        fma_store(qb, 1, pout - cs);                            // pixel 1 of the last channel
+        fma_store(qb, 1, pout - FI_CSO);                           // pixel 1 of the last channel
     }
     for (; c + D <= last; ++c) {                                // steady state: window c + D exists
         issue(freed);
@@ -480,17 +485,22 @@ __device__ __forceinline__ void fi_run_channels_lean(const float* __restrict__ i
 #undef FI_READ64
 #pragma unroll
     for (int p = 0; p < FI_PX; ++p)                             // copy-through of the (rare) invalid pixels (:2814-2818)
-        if (px[p].inimg && !px[p].valid) fi_copy_through(img, out, px[p].pix, c_begin, c_end, cs);
+        if (px[p].inimg && !px[p].valid) fi_copy_through_to<TO>(img, out, px[p].pix, c_begin, c_end, cs, FI_CSO);
 }
 
 // two 512-thread workgroups per CU (4 waves per SIMD): at most 128 VGPRs.
 // aligned16 (set by the host): width, strides and base of in1 are multiples of 16 bytes, and two planes lie within 2^31 bytes.
-template <bool BLEND>
+// DST = vfi_strides (fi_dst, filterinterp_dev.h): out and the blend epilogue's other / out are addressed with so's batch and
+// channel strides; no DST: with s1's.
+template <bool BLEND, class... DST>
 __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     float* __restrict__ out, int channel, int h, int w,
     vfi_strides s1, vfi_strides s2, vfi_strides s3,
-    int tiles_x, int tiles_y, int ntiles, int ch_per_group, int aligned16, FiBlend blend) {
+    int tiles_x, int tiles_y, int ntiles, int ch_per_group, int aligned16, FiBlend blend, DST... so) {
+    constexpr bool TO = sizeof...(DST) != 0;
+    int64_t ob = s1.b, oc = s1.c;                           // the destination's batch and channel strides
+    if constexpr (TO) { ob = fi_dst(s1, so...).b; oc = fi_dst(s1, so...).c; }
     // ONE LDS array (a second __shared__ object beside an LDS-DMA target makes hipcc drain vmcnt
     // before LDS reads): 16-float header holding the bounding box, then the window ring
     __shared__ __attribute__((aligned(16))) float lds[FI_HDR + FI_RING_FLOATS];
@@ -577,8 +587,8 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     }
 
     const float* img = in1 + (int64_t)b * s1.b;
-    float* dst = out + (int64_t)b * s1.b;
-    const FiBlend bl{blend.other ? blend.other + (int64_t)b * s1.b : nullptr, blend.out ? blend.out + (int64_t)b * s1.b : nullptr,
+    float* dst = out + (int64_t)b * ob;
+    const FiBlend bl{blend.other ? blend.other + (int64_t)b * ob : nullptr, blend.out ? blend.out + (int64_t)b * ob : nullptr,
                      blend.w0, blend.w2};
 
     const int kmax = (n + FI_THREADS - 1) / FI_THREADS;     // workgroup-uniform
@@ -587,15 +597,15 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
 #pragma unroll
         for (int p = 0; p < FI_PX; ++p) {
             if (px[p].valid) {
-                fi4_channels_direct(img, dst + px[p].pix, c_begin, c_end, s1.c, (int)s1.h, h, w, L[p], T[p], px[p].f,
+                fi4_channels_direct<TO>(img, dst + px[p].pix, c_begin, c_end, s1.c, oc, (int)s1.h, h, w, L[p], T[p], px[p].f,
                                     px[p].alpha, px[p].beta);
             } else if (px[p].inimg) {
-                fi_copy_through(img, dst, px[p].pix, c_begin, c_end, s1.c);
+                fi_copy_through_to<TO>(img, dst, px[p].pix, c_begin, c_end, s1.c, oc);
             }
             if (BLEND && px[p].inimg)                           // (this thread wrote dst[...] itself: it reads its own stores)
                 for (int c = c_begin; c < c_end; ++c) {
-                    const float q0 = bl.other[(int64_t)c * s1.c + px[p].pix] * bl.w0, q2 = dst[(int64_t)c * s1.c + px[p].pix] * bl.w2;
-                    bl.out[(int64_t)c * s1.c + px[p].pix] = q0 + q2;
+                    const float q0 = bl.other[(int64_t)c * oc + px[p].pix] * bl.w0, q2 = dst[(int64_t)c * oc + px[p].pix] * bl.w2;
+                    bl.out[(int64_t)c * oc + px[p].pix] = q0 + q2;
                 }
         }
         return;
@@ -604,15 +614,15 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
     const FiWindow win{bx0, by0, bw, bh, pitch, h, w, (int)s1.h};
     float* ring = lds + FI_HDR;
 #define FI_RUN(K) if constexpr (lean) { \
-        if constexpr ((K) <= 10 * FI_KS) { if (use64) fi_run_channels_lean<K, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); } \
-        if (!use64) fi_run_channels_lean<K, false>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); \
-    } else fi_run_channels<K, BLEND>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, bl)
+        if constexpr ((K) <= 10 * FI_KS) { if (use64) fi_run_channels_lean<K, true, false, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring); } \
+        if (!use64) fi_run_channels_lean<K, false, false, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring); \
+    } else fi_run_channels<K, BLEND, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring, bl)
     if constexpr (lean) {
         // (units of four floats: two or three per thread cover the windows of smooth fields; larger ones stay on 4-byte staging)
         const int k16 = (n + 4 * FI_THREADS - 1) / (4 * FI_THREADS);
         if (can16 && k16 <= 3) {
-#define FI_RUN16(K) { if (use64) fi_run_channels_lean<K, true, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); \
-                      else fi_run_channels_lean<K, false, true>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring); }
+#define FI_RUN16(K) { if (use64) fi_run_channels_lean<K, true, true, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring); \
+                      else fi_run_channels_lean<K, false, true, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring); }
             if (k16 <= 1) FI_RUN16(1) else if (k16 == 2) FI_RUN16(2) else FI_RUN16(3)
 #undef FI_RUN16
             return;
@@ -632,17 +642,20 @@ __global__ __launch_bounds__(FI_THREADS, FI_WAVES) void fi_forward_ori_lds(
 }
 
 // (explicit: hipcc 7.2 has silently left the host stubs of implicitly instantiated flavours of this kernel undefined)
-template __global__ void fi_forward_ori_lds<true>(const float* __restrict__, const float* __restrict__, const float* __restrict__,
-    float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, FiBlend);
-template __global__ void fi_forward_ori_lds<false>(const float* __restrict__, const float* __restrict__, const float* __restrict__,
-    float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, FiBlend);
+#define FI_INSTANCE(BLEND, ...) template __global__ void fi_forward_ori_lds<BLEND, ##__VA_ARGS__>(const float* __restrict__, const float* __restrict__, \
+    const float* __restrict__, float* __restrict__, int, int, int, vfi_strides, vfi_strides, vfi_strides, int, int, int, int, int, FiBlend, ##__VA_ARGS__)
+FI_INSTANCE(true); FI_INSTANCE(false); FI_INSTANCE(true, vfi_strides); FI_INSTANCE(false, vfi_strides);
+#undef FI_INSTANCE
 
 }  // namespace vfi
 
 using namespace vfi;
 
 static int forward_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
-                           int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream, FiBlend blend) {
+                           int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream,
+                           FiBlend blend) {
+    // the destination's rows are input1's rows: one in-plane offset per pixel for loads and stores
+    if (so.h != s1.h) return VFI_ERR_SHAPE;
     // byte offsets inside a plane are 32-bit in the kernel
     if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;
     const int tiles_x = (w + FI_TW - 1) / FI_TW, tiles_y = (h + FI_TH - 1) / FI_TH;
@@ -660,23 +673,25 @@ static int forward_ori_lds(const float* input1, const float* input2, const float
     // (16-byte staging: rows of input1 on 16-byte boundaries; its single-descriptor addressing: two planes within 2^31 bytes)
     const int aligned16 = !(w & 3) && !(s1.h & 3) && !(s1.c & 3) && !(s1.b & 3) && !((uintptr_t)input1 & 15) &&
                           s1.c > 0 && 4 * s1.c + 4 * ((int64_t)(h - 1) * s1.h + w) < 0x7fffffffLL;
-    if (blend.out)
-        hipLaunchKernelGGL(fi_forward_ori_lds<true>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, aligned16, blend);
-    else
-        hipLaunchKernelGGL(fi_forward_ori_lds<false>, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, input2,
-                           input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, aligned16, blend);
+    // (every store of the kernel is a single dword: a destination needs the 4-byte alignment of a float and no more.  A
+    //  destination laid out as input1 takes the instances that have no second set of strides: the code they always were.)
+    const bool to = so.b != s1.b || so.c != s1.c;
+#define FI_LAUNCH(KERNEL, ...) hipLaunchKernelGGL(KERNEL, grid, dim3(FI_THREADS, 1, 1), 0, (hipStream_t)stream, input1, \
+        input2, input3, output, channel, h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, aligned16, blend, ##__VA_ARGS__)
+    if (blend.out) { if (to) FI_LAUNCH((fi_forward_ori_lds<true, vfi_strides>), so); else FI_LAUNCH(fi_forward_ori_lds<true>); }
+    else { if (to) FI_LAUNCH((fi_forward_ori_lds<false, vfi_strides>), so); else FI_LAUNCH(fi_forward_ori_lds<false>); }
+#undef FI_LAUNCH
     return launch_status();
 }
 
 int vfi::launch_fi_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
-                           int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream) {
-    return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream, FiBlend{nullptr, nullptr, 0.0f, 0.0f});
+                           int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream) {
+    return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, so, stream, FiBlend{nullptr, nullptr, 0.0f, 0.0f});
 }
 
 int vfi::launch_fi_ori_lds_blend(const float* input1, const float* input2, const float* input3, float* output, const float* other,
                                  float* blend, float w0, float w2, int batch, int channel, int h, int w, vfi_strides s1,
-                                 vfi_strides s2, vfi_strides s3, vfi_stream_t stream) {
+                                 vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream) {
     if (channel > FI_BLEND_MAXC || !other || !blend) return FI_DECLINED;
-    return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, stream, FiBlend{other, blend, w0, w2});
+    return forward_ori_lds(input1, input2, input3, output, batch, channel, h, w, s1, s2, s3, so, stream, FiBlend{other, blend, w0, w2});
 }

@@ -54,8 +54,8 @@ __device__ __forceinline__ float fn_value(const FnPixel<FS>& px, F&& fetch) {
     return blend4(px.alpha, px.beta, q[0], q[1], q[2], q[3]);
 }
 
-template <int FS, int K>
-__device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs,
+template <int FS, int K, bool TO>
+__device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, float* __restrict__ out, int64_t cs, int64_t cso_to,
                                                 int c_begin, int c_end, int tid, const FiWindow& win,
                                                 const FnPixel<FS>& px, float* __restrict__ ring, int R) {
     static_assert(3 * K <= 63, "vmcnt is a 6-bit counter");
@@ -82,7 +82,7 @@ __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, f
         if (!px.valid) return;
         const float* t = ring + slot * NP + px.lbase;
         const int pitch = win.pitch;
-        out[(int64_t)c * cs + px.pix] = fn_value<FS>(px, [&](int r, int k) { return t[r * pitch + k]; });
+        out[(int64_t)c * FI_CSO + px.pix] = fn_value<FS>(px, [&](int r, int k) { return t[r * pitch + k]; });
     };
     if (c_begin >= c_end) return;
     const int last = c_end - 1;
@@ -98,15 +98,18 @@ __device__ __forceinline__ void fn_run_channels(const float* __restrict__ img, f
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
-    if (px.inimg && !px.valid) fi_copy_through(img, out, px.pix, c_begin, c_end, cs);
+    if (px.inimg && !px.valid) fi_copy_through_to<TO>(img, out, px.pix, c_begin, c_end, cs, FI_CSO);
 }
 
-template <int FS>
+// DST = vfi_strides (fi_dst, filterinterp_dev.h): out is addressed with so's batch and channel strides; no DST: with s1's
+template <int FS, class... DST>
 __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     float* __restrict__ out, int channel, int h, int w,
     vfi_strides s1, vfi_strides s2, vfi_strides s3,
-    int tiles_x, int tiles_y, int ntiles, int ch_per_group) {
+    int tiles_x, int tiles_y, int ntiles, int ch_per_group, DST... so) {
+    constexpr bool TO = sizeof...(DST) != 0;
+    const int64_t ob = fi_dst(s1, so...).b, oc = fi_dst(s1, so...).c;
     __shared__ float lds[FN_HDR + FN_RING_FLOATS];          // one array: header (bounding box) + window ring
     int* box = reinterpret_cast<int*>(lds);
     const int tile = blockIdx.x;
@@ -154,7 +157,7 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
     }
 
     const float* img = in1 + (int64_t)b * s1.b;
-    float* dst = out + (int64_t)b * s1.b;
+    float* dst = out + (int64_t)b * ob;
     const int hs = (int)s1.h;
     const int kmax = (n + FN_THREADS - 1) / FN_THREADS;
     if (kmax > FN_KTOP) {
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
             const int plane_bytes = 4 * ((h - 1) * hs + w);
             for (int c = c_begin; c < c_end; ++c) {
                 const auto plane = buffer_rsrc(img + (int64_t)c * s1.c, plane_bytes);
-                dst[(int64_t)c * s1.c + px.pix] = fn_value<FS>(px, [&](int r, int k) {
+                dst[(int64_t)c * oc + px.pix] = fn_value<FS>(px, [&](int r, int k) {
                     int ty = T, tx = L;
                     asm volatile("" : "+v"(ty), "+v"(tx));  // tap addresses re-derived per channel, not hoisted (registers)
                     const unsigned o = 4u * (unsigned)(clampi(ty + r, 0, h - 1) * hs + clampi(tx + k, 0, w - 1));
@@ -171,13 +174,13 @@ __global__ __launch_bounds__(FN_THREADS, 4) void fi_forward_ori_lds_n(
                 });
             }
         } else if (px.inimg) {
-            fi_copy_through(img, dst, px.pix, c_begin, c_end, s1.c);
+            fi_copy_through_to<TO>(img, dst, px.pix, c_begin, c_end, s1.c, oc);
         }
         return;
     }
     const FiWindow win{bx0, by0, bw, bh, pitch, h, w, hs};
     float* ring = lds + FN_HDR;
-#define FN_RUN(K) fn_run_channels<FS, K>(img, dst, s1.c, c_begin, c_end, tid, win, px, ring, \
+#define FN_RUN(K) fn_run_channels<FS, K, TO>(img, dst, s1.c, oc, c_begin, c_end, tid, win, px, ring, \
                                          min(FN_RMAX, FN_RING_FLOATS / ((K) * FN_THREADS)))
     if (kmax <= 3) FN_RUN(3);
     else if (kmax == 4) FN_RUN(4);
@@ -196,8 +199,9 @@ using namespace vfi;
 
 int vfi::launch_fi_ori_lds_n(const float* input1, const float* input2, const float* input3, float* output, int batch,
                              int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                             vfi_stream_t stream) {
+                             vfi_strides so, vfi_stream_t stream) {
     if (!(fs == 2 || fs == 5 || fs == 6)) return FI_DECLINED;
+    if (so.h != s1.h) return VFI_ERR_SHAPE;                  // one in-plane offset per pixel for loads and stores
     if ((int64_t)h * s1.h * 4 > INT_MAX) return FI_DECLINED;  // byte offsets inside a plane are 32-bit
     const int tiles_x = (w + FN_TW - 1) / FN_TW, tiles_y = (h + FN_TH - 1) / FN_TH;
     const int64_t nt = (int64_t)tiles_x * tiles_y * batch;
@@ -207,14 +211,12 @@ int vfi::launch_fi_ori_lds_n(const float* input1, const float* input2, const flo
     const FiSplit split = fi_channel_split(ntiles, channel, 4.3 * (2 + fs * fs) / 18.0);
     const dim3 grid((unsigned)ntiles, (unsigned)split.groups, 1), block(FN_THREADS, 1, 1);
     hipStream_t st = (hipStream_t)stream;
-    if (fs == 2)
-        hipLaunchKernelGGL(fi_forward_ori_lds_n<2>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
-    else if (fs == 5)
-        hipLaunchKernelGGL(fi_forward_ori_lds_n<5>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
-    else
-        hipLaunchKernelGGL(fi_forward_ori_lds_n<6>, grid, block, 0, st, input1, input2, input3, output, channel, h, w,
-                           s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
+    const bool to = so.b != s1.b || so.c != s1.c;           // (a destination laid out as input1: the instances without a second set of strides)
+#define FN_LAUNCH(KERNEL, ...) hipLaunchKernelGGL(KERNEL, grid, block, 0, st, input1, input2, input3, output, channel, \
+        h, w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, ##__VA_ARGS__)
+    if (fs == 2) { if (to) FN_LAUNCH((fi_forward_ori_lds_n<2, vfi_strides>), so); else FN_LAUNCH(fi_forward_ori_lds_n<2>); }
+    else if (fs == 5) { if (to) FN_LAUNCH((fi_forward_ori_lds_n<5, vfi_strides>), so); else FN_LAUNCH(fi_forward_ori_lds_n<5>); }
+    else { if (to) FN_LAUNCH((fi_forward_ori_lds_n<6, vfi_strides>), so); else FN_LAUNCH(fi_forward_ori_lds_n<6>); }
+#undef FN_LAUNCH
     return launch_status();
 }

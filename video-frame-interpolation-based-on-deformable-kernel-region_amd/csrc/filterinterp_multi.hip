@@ -65,9 +65,11 @@ struct FmPixel {
 // take the row from the scalar offset operand -- S registers of addressing instead of one per staged dword (K = S KR = 9 ...
 // 18), which is what lets a window of 96 x 48 pairs live beside the evaluations' state in 128 registers.  Rows past the
 // window are staged through a descriptor of zero records: no memory traffic, and no address is formed from their offsets.
-template <int S, int KR>
-__device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, const FmPtrs& ptr, int64_t boff, int64_t cs,
-                                                int c_begin, int c_end, int tid, const FmWindow& win,
+// Destination: ooff = the element offset of this batch item inside every output tensor, FI_CSO (filterinterp_dev.h) = the distance of its planes;
+// the dense call passes the image's own (b * s1.b, cs).
+template <int S, int KR, bool TO>
+__device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, const FmPtrs& ptr, int64_t ooff, int64_t cs,
+                                                int64_t cso_to, int c_begin, int c_end, int tid, const FmWindow& win,
                                                 const FmPixel (&px)[FM_PX], float* __restrict__ ring) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     constexpr int K = S * KR;                               // staging instructions per wave and channel
@@ -115,7 +117,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
         }
     const int last = c_end - 1;
     const float* pdma = img + (int64_t)c_begin * cs;
-    int64_t oofs = boff + (int64_t)c_begin * cs;            // element offset of the output plane inside every output tensor
+    int64_t oofs = ooff + (int64_t)c_begin * FI_CSO;           // element offset of the output plane inside every output tensor
     auto issue = [&](int slot) {
         float* l = ring + slot * NP + wave * (64 * S);
 #pragma unroll
@@ -186,7 +188,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
             if constexpr (e + 1 < NE) reads(std::integral_constant<int, e + 1>{}, I1{});
             finish(E, top, bot);
         });
-        oofs += cs;
+        oofs += FI_CSO;
     };
 #undef FM_READ_ROW
     // The steady-state wait.  vmcnt counts the staging loads AND the NE result stores of every step, in issue order (one counter
@@ -237,7 +239,7 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
         for (int p = 0; p < FM_PX; ++p)
             if (px[p].inimg && !px[p].valid[t])
                 for (int cc = c_begin; cc < c_end; ++cc)
-                    ptr.out[t][boff + (int64_t)cc * cs + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
+                    ptr.out[t][ooff + (int64_t)cc * FI_CSO + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
 }
 
 // The same loop on a PLAIN window (one dword per element, tap rows as two ds_read2_b32: rounds 2-3) -- for tiles whose window
@@ -247,9 +249,9 @@ __device__ __forceinline__ void fm_run_channels(const float* __restrict__ img, c
 // multiply-add advances the left and the right quadrant sum) with one lgkmcnt wait per evaluation and the next evaluation's
 // first rows in flight under the current one's arithmetic, range-checked buffer stores.  An evaluation = one pixel under
 // one flow: 2 x FM_NT per thread and channel.
-template <int K>
-__device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ img, const FmPtrs& ptr, int64_t boff, int64_t cs,
-                                                int c_begin, int c_end, int tid, const FmWindow& win,
+template <int K, bool TO>
+__device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ img, const FmPtrs& ptr, int64_t ooff, int64_t cs,
+                                                int64_t cso_to, int c_begin, int c_end, int tid, const FmWindow& win,
                                                 const FmPixel (&px)[FM_PX], float* __restrict__ ring) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     constexpr int NP = K * FM_THREADS;
@@ -293,7 +295,7 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
         }
     const int last = c_end - 1;
     const float* pdma = img + (int64_t)c_begin * cs;
-    int64_t oofs = boff + (int64_t)c_begin * cs;            // element offset of the output plane inside every output tensor
+    int64_t oofs = ooff + (int64_t)c_begin * FI_CSO;           // element offset of the output plane inside every output tensor
     auto issue = [&](int slot) {
         const auto plane = buffer_rsrc(pdma, plane_bytes);
         float* l = ring + slot * NP + wave_first;
@@ -347,7 +349,7 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
                 reads(std::integral_constant<int, e + 1>{}, I0{}); reads(std::integral_constant<int, e + 1>{}, I1{});
             }
         });
-        oofs += cs;
+        oofs += FI_CSO;
     };
 #undef FM_READ2
     // (the steady-state wait counts the result stores in: see fm_run_channels)
@@ -393,12 +395,15 @@ __device__ __forceinline__ void fm_run_channels_plain(const float* __restrict__ 
         for (int p = 0; p < FM_PX; ++p)
             if (px[p].inimg && !px[p].valid[t])
                 for (int cc = c_begin; cc < c_end; ++cc)
-                    ptr.out[t][boff + (int64_t)cc * cs + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
+                    ptr.out[t][ooff + (int64_t)cc * FI_CSO + px[p].pix] = img[(int64_t)cc * cs + px[p].pix];
 }
 
+// DST = vfi_strides (fi_dst, filterinterp_dev.h): the outputs are addressed with so's batch and channel strides; no DST:
+// with s1's
+template <class... DST>
 __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
     const float* __restrict__ in1, FmPtrs ptr, const float* __restrict__ in3, int channel, int h, int w,
-    vfi_strides s1, vfi_strides s2, vfi_strides s3, int tiles_x, int tiles_y, int ntiles, int ch_per_group) {
+    vfi_strides s1, vfi_strides s2, vfi_strides s3, int tiles_x, int tiles_y, int ntiles, int ch_per_group, DST... so) {
     __shared__ __attribute__((aligned(16))) float lds[FM_HDR + FM_RING_FLOATS];
     int* box = reinterpret_cast<int*>(lds);
 
@@ -475,6 +480,9 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
         for (int t = 0; t < FM_NT; ++t) px[p].lbase[t] = (T[p][t] - by0) * pitch + (L[p][t] - bx0);
 
     const int64_t boff = (int64_t)b * s1.b;
+    constexpr bool TO = sizeof...(DST) != 0;
+    int64_t ooff = boff, oc = s1.c;
+    if constexpr (TO) { ooff = (int64_t)b * fi_dst(s1, so...).b; oc = fi_dst(s1, so...).c; }
     const float* img = in1 + boff;
     const int kmax = (n + FM_THREADS - 1) / FM_THREADS;
     if (kmax > FM_KTOP) {
@@ -483,12 +491,12 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
         for (int t = 0; t < FM_NT; ++t)
 #pragma unroll
             for (int p = 0; p < FM_PX; ++p) {
-                float* dst = ptr.out[t] + boff;
+                float* dst = ptr.out[t] + ooff;
                 if (px[p].valid[t]) {
-                    fi4_channels_direct(img, dst + px[p].pix, c_begin, c_end, s1.c, (int)s1.h, h, w, L[p][t], T[p][t], px[p].f,
+                    fi4_channels_direct<TO>(img, dst + px[p].pix, c_begin, c_end, s1.c, oc, (int)s1.h, h, w, L[p][t], T[p][t], px[p].f,
                                         px[p].alpha[t], px[p].beta[t]);
                 } else if (px[p].inimg) {
-                    fi_copy_through(img, dst, px[p].pix, c_begin, c_end, s1.c);
+                    fi_copy_through_to<TO>(img, dst, px[p].pix, c_begin, c_end, s1.c, oc);
                 }
             }
         return;
@@ -496,8 +504,8 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
 
     const FmWindow win{bx0, by0, paired ? bwp : bw, bh, pitch, h, w, (int)s1.h};
     float* ring = lds + FM_HDR;
-#define FM_RUN(S, KR) fm_run_channels<S, KR>(img, ptr, boff, s1.c, c_begin, c_end, tid, win, px, ring)
-#define FM_RUN_PLAIN(K) fm_run_channels_plain<K>(img, ptr, boff, s1.c, c_begin, c_end, tid, win, px, ring)
+#define FM_RUN(S, KR) fm_run_channels<S, KR, TO>(img, ptr, ooff, s1.c, oc, c_begin, c_end, tid, win, px, ring)
+#define FM_RUN_PLAIN(K) fm_run_channels_plain<K, TO>(img, ptr, ooff, s1.c, oc, c_begin, c_end, tid, win, px, ring)
     if (paired) {
         if (segs == 3) {
             if (rows8 == 3) FM_RUN(3, 3);
@@ -522,22 +530,23 @@ __global__ __launch_bounds__(FM_THREADS, 4) void fi_forward_ori_multi(
 
 using namespace vfi;
 
-extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const float* const* flows, const float* input3,
-                                                   float* const* outputs, int nflows, int batch, int channel, int h, int w,
-                                                   int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
-                                                   vfi_stream_t stream) {
+static int forward_ori_multi_to(const float* input1, const float* const* flows, const float* input3, float* const* outputs,
+                                int nflows, int batch, int channel, int h, int w, int filter_channels, vfi_strides s1,
+                                vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream) {
     if (nflows <= 0 || !flows || !outputs || batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0)
         return VFI_ERR_SHAPE;
     if (!input1 || !input3) return VFI_ERR_SHAPE;
     for (int t = 0; t < nflows; ++t)
         if (!flows[t] || !outputs[t]) return VFI_ERR_SHAPE;
+    // the destinations' rows are input1's rows: one in-plane offset per pixel for loads and stores (never a slower kernel)
+    if (so.h != s1.h) return VFI_ERR_SHAPE;
     // more flows than one launch takes: pairs, and an odd flow alone.  (Round 4: a three-flow launch was slower than 2 + 1 --
     // 3.01 against 2.78 ms at 1080p, C = 196: the union window of three time offsets cost it its ring depth.)
     if (nflows > FM_NT) {
         for (int t0 = 0; t0 < nflows; t0 += FM_NT) {
             const int n = nflows - t0 < FM_NT ? nflows - t0 : FM_NT;
-            const int err = vfi_filterinterp_forward_ori_multi(input1, flows + t0, input3, outputs + t0, n, batch, channel, h, w,
-                                                               filter_channels, s1, s2, s3, stream);
+            const int err = forward_ori_multi_to(input1, flows + t0, input3, outputs + t0, n, batch, channel, h, w,
+                                                 filter_channels, s1, s2, s3, so, stream);
             if (err != VFI_OK) return err;
         }
         return VFI_OK;
@@ -548,8 +557,8 @@ extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const flo
                         s2.c >= 0 && s3.c >= 0 && (s2.c + (int64_t)h * s2.h) * 4 <= INT_MAX && (15 * s3.c + (int64_t)h * s3.h) * 4 <= INT_MAX;
     if (!staged) {
         for (int t = 0; t < nflows; ++t) {
-            const int err = vfi_filterinterp_forward_ori(input1, flows[t], input3, outputs[t], batch, channel, h, w,
-                                                         filter_channels, s1, s2, s3, stream);
+            const int err = fi_forward_ori_to(input1, flows[t], input3, outputs[t], batch, channel, h, w, filter_channels,
+                                              s1, s2, s3, so, stream);
             if (err != VFI_OK) return err;
         }
         return VFI_OK;
@@ -563,7 +572,29 @@ extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const flo
     FmPtrs ptr;
     for (int t = 0; t < FM_NT; ++t) { ptr.flow[t] = flows[t]; ptr.out[t] = outputs[t]; }
     const dim3 grid((unsigned)fi_xcd_grid(ntiles), (unsigned)split.groups, 1), block(FM_THREADS, 1, 1);
-    hipLaunchKernelGGL(fi_forward_ori_multi, grid, block, 0, (hipStream_t)stream, input1, ptr, input3, channel, h, w, s1, s2, s3,
-                       tiles_x, tiles_y, ntiles, split.ch_per_group);
+    // (every store is a single dword: the destinations need a float's alignment and no more.  Destinations laid out as
+    //  input1 take the instance without a second set of strides: the code it always was.)
+    if (so.b != s1.b || so.c != s1.c)
+        hipLaunchKernelGGL(fi_forward_ori_multi<vfi_strides>, grid, block, 0, (hipStream_t)stream, input1, ptr, input3, channel, h,
+                           w, s1, s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group, so);
+    else
+        hipLaunchKernelGGL(fi_forward_ori_multi<>, grid, block, 0, (hipStream_t)stream, input1, ptr, input3, channel, h, w, s1,
+                           s2, s3, tiles_x, tiles_y, ntiles, split.ch_per_group);
     return launch_status();
+}
+
+extern "C" int vfi_filterinterp_forward_ori_multi(const float* input1, const float* const* flows, const float* input3,
+                                                   float* const* outputs, int nflows, int batch, int channel, int h, int w,
+                                                   int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
+                                                   vfi_stream_t stream) {
+    return forward_ori_multi_to(input1, flows, input3, outputs, nflows, batch, channel, h, w, filter_channels, s1, s2, s3, s1,
+                                stream);
+}
+
+extern "C" int vfi_filterinterp_forward_ori_multi_to(const float* input1, const float* const* flows, const float* input3,
+                                                      float* const* outputs, int nflows, int batch, int channel, int h, int w,
+                                                      int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3,
+                                                      vfi_strides s_out, vfi_stream_t stream) {
+    return forward_ori_multi_to(input1, flows, input3, outputs, nflows, batch, channel, h, w, filter_channels, s1, s2, s3, s_out,
+                                stream);
 }

@@ -20,17 +20,33 @@ static_assert(FI_DECLINED != VFI_OK && FI_DECLINED != VFI_ERR_SHAPE && FI_DECLIN
 struct FiSplit { int ch_per_group, groups; };
 FiSplit fi_channel_split(int ntiles, int channel, double prologue);
 
+// The _ori forward launchers address what they WRITE with `so`, a layout of its own: w stride 1, so.h == s1.h (a pixel's
+// offset inside a plane is one register shared by the load and the store; anything else is VFI_ERR_SHAPE, not a slower
+// kernel), batch and channel strides free -- a channel slice of a wider contiguous buffer.  What a launcher decides from
+// the input (16-byte staging, the 31-bit range checks, the window classes) does not look at the destination, and every
+// store is a single dword, so the destination needs a float's alignment only.  so = s1 is the dense call: it runs the
+// instances that carry no second set of strides.
+
 // filterinterp_lds.hip: _ori forward, fs == 4
 int launch_fi_ori_lds(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
-                      int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+                      int h, int w, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream);
 // filterinterp_lds.hip: the same kernel with the blend of DAIN.FilterInterpolate as its epilogue -- besides output it
-// writes blend = other * w0 + output * w2; other / blend have input1's strides; declines channel > FI_BLEND_MAXC
+// writes blend = other * w0 + output * w2; other / blend have output's strides; declines channel > FI_BLEND_MAXC
 int launch_fi_ori_lds_blend(const float* input1, const float* input2, const float* input3, float* output, const float* other,
                             float* blend, float w0, float w2, int batch, int channel, int h, int w, vfi_strides s1,
-                            vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+                            vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream);
 // filterinterp_lds_n.hip: _ori forward, fs 2, 5 and 6
 int launch_fi_ori_lds_n(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
-                        int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_stream_t stream);
+                        int h, int w, int fs, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so, vfi_stream_t stream);
+// filterinterp.hip: the direct gather, any filter size
+int launch_fi_ori_direct(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                         int h, int w, int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so,
+                         vfi_stream_t stream);
+// filterinterp.hip: vfi_filterinterp_forward_ori with a destination layout -- the staged kernel of the filter size, else the
+// direct gather; checks its arguments as the entry point does
+int fi_forward_ori_to(const float* input1, const float* input2, const float* input3, float* output, int batch, int channel,
+                      int h, int w, int filter_channels, vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides so,
+                      vfi_stream_t stream);
 // filterinterp_defor_lds.hip: forward of the deformable variants, fs 4 and 6
 int launch_fi_defor_lds(int variant, const float* input1, const float* input2, const float* input3, const float* input4,
                         float* output, int batch, int channel, int h, int w, int filter_size, vfi_strides s1, vfi_strides s2,

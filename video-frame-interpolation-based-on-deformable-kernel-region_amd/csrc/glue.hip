@@ -301,16 +301,16 @@ extern "C" int vfi_filterinterp_blend_forward(const float* ref0, const float* re
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0) return VFI_ERR_SHAPE;
     if (!ref0 || !ref2 || !flow0 || !flow2 || !filt0 || !filt2 || !blend) return VFI_ERR_SHAPE;
     const int fs = fi_filter_size(filter_channels);
-    if (filter_channels == 16 && out0 && out2 && s_out.b == s_ref.b && s_out.c == s_ref.c && s_out.h == s_ref.h) {
-        // the LDS-staged forward per side (faster than the direct gather even at C = 3; it writes with the
-        // input's strides), then the blend
-        int err = vfi_filterinterp_forward_ori(ref0, flow0, filt0, out0, batch, channel, h, w, 16, s_ref, s_flow, s_filt, stream);
+    if (filter_channels == 16 && out0 && out2 && s_out.h == s_ref.h) {
+        // the LDS-staged forward per side (faster than the direct gather even at C = 3; it writes rows as far apart as
+        // the input's, at any batch and channel stride: the outputs may be channel slices of a wider buffer), then the blend
+        int err = fi_forward_ori_to(ref0, flow0, filt0, out0, batch, channel, h, w, 16, s_ref, s_flow, s_filt, s_out, stream);
         if (err != VFI_OK) return err;
         // the blend as the second launch's epilogue (3-channel frames); else a launch of its own
         err = launch_fi_ori_lds_blend(ref2, flow2, filt2, out2, out0, blend, w0, w2, batch, channel, h, w, s_ref, s_flow, s_filt,
-                                      stream);
+                                      s_out, stream);
         if (err != FI_DECLINED) return err;
-        err = vfi_filterinterp_forward_ori(ref2, flow2, filt2, out2, batch, channel, h, w, 16, s_ref, s_flow, s_filt, stream);
+        err = fi_forward_ori_to(ref2, flow2, filt2, out2, batch, channel, h, w, 16, s_ref, s_flow, s_filt, s_out, stream);
         if (err != VFI_OK) return err;
         hipLaunchKernelGGL(fi_blend_only, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, (hipStream_t)stream, out0,
                            out2, blend, channel, h, w, w0, w2, s_out);

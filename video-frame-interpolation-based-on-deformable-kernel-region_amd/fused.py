@@ -14,6 +14,9 @@ a frame requires grad).  Each takes its autograd Function only when grad mode is
 it is the plain forward launch, with no grad_fn.  `forward_flownets_upsample` and `FlowProject_from_quarter` are
 differentiable in the same way, so the loss reaches the quarter-resolution flow of the flow network: one backward call of
 the library for all time offsets (vfi_flow_upsample4_backward, vfi_[depth]flowprojection_backward_up4).
+`rectify_inputs` is the end of the synthesis stage in one call: `FilterInterpolate`, `FilterInterpolate_ctx_all` and the `torch.cat`
+that builds rectifyNet's input, with the warps written straight into that input (vfi_filterinterp_forward_ori_multi_to) and one
+autograd Function over all time offsets.
 `FilterInterpolate_ctx_all` and `FilterInterpolate_ctx` train the context network: the context tensors get the image
 gradient of every time offset from one call per direction (vfi_filterinterp_backward_ori_image_multi), and flows and
 filter get none, because the reference detaches them on this path.  The rest (the frame glue) is inference only."""
@@ -399,6 +402,151 @@ def FilterInterpolate_ctx(ctx0, ctx2, offset, filter):
     offset = [flow of direction 0, flow of direction 1].  Differentiable exactly as `FilterInterpolate_ctx_all` is:
     towards the context tensors only."""
     return FilterInterpolate_ctx_all(ctx0, ctx2, [[offset[0]], [offset[1]]], filter)[0]
+
+
+# ---------------------------------------------------------------- the rectify network's input, written in place
+
+def rectify_channels(filter_size2, ctx_channels=None):
+    """Channel ranges of the tensor the reference concatenates for rectifyNet (networks/DAIN_slowmotion.py:177-181,
+    networks/DAIN.py:264-268), in its order: name -> (first, one past last), plus 'total'.  `cur_output`, `ref0`, `ref2` are
+    the blend and the two warped frames, `offset0/1` the projected flows, `filter0/1` the filters, `ctx0/2` the warped
+    context tensors (absent for ctx_channels None: DAIN's 45-channel input at filter_size2 == 16, 437 with 196)."""
+    m, at = {}, 0
+    for name, n in (("cur_output", 3), ("ref0", 3), ("ref2", 3), ("offset0", 2), ("offset1", 2), ("filter0", filter_size2),
+                    ("filter1", filter_size2)) + ((("ctx0", ctx_channels), ("ctx2", ctx_channels)) if ctx_channels else ()):
+        m[name] = (at, at + n)
+        at += n
+    m["total"] = at
+    return m
+
+
+def _ch(t, rng):
+    return t[:, rng[0]:rng[1]]
+
+
+def _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2):
+    """the T buffers, every channel written: the frames' kernel into 0-8, one multi-flow call per direction into the context
+    slices of all T buffers, copy_ for the flows and filters"""
+    if (ctx0 is None) != (ctx2 is None):
+        raise RuntimeError("rectify_inputs: ctx0 and ctx2 are given together or not at all")
+    b, c, h, w = ref0.shape
+    if c != 3 or len(off0) != len(time_offsets) or len(off2) != len(time_offsets):
+        raise RuntimeError("rectify_inputs: 3-channel frames and one flow per direction and time offset")
+    m = rectify_channels(filt0.size(1), None if ctx0 is None else ctx0.size(1))
+    bufs = [torch.empty((b, m["total"], h, w), device=ref0.device, dtype=torch.float32) for _ in time_offsets]
+    for buf, t, f0, f2 in zip(bufs, time_offsets, off0, off2):
+        _check(cabi.filterinterp_blend_forward(ref0, ref2, f0, f2, filt0, filt2, _ch(buf, m["cur_output"]), _ch(buf, m["ref0"]),
+                                               _ch(buf, m["ref2"]), float(1.0 - t), float(t)), "filterinterp_blend_forward")
+        for name, src in (("offset0", f0), ("offset1", f2), ("filter0", filt0), ("filter1", filt2)):
+            _ch(buf, m[name]).copy_(src)
+    for name, image, flows, filt in (("ctx0", ctx0, off0, filt0), ("ctx2", ctx2, off2, filt2)):
+        if image is not None:
+            _check(cabi.filterinterp_forward_ori_multi_to(image, list(flows), filt, [_ch(buf, m[name]) for buf in bufs]),
+                   "filterinterp_forward_ori_multi_to")
+    return bufs, m
+
+
+class _RectifyInputs(torch.autograd.Function):
+    """`rectify_inputs` over all time offsets: outputs are the T buffers, then T dense copies of their `cur_output` channels
+    (the loss uses those directly; as slices of the buffers they would each cost autograd a full-size zero gradient).
+    Saved: frames, flows and filters -- not the buffers, and not the context tensors (their gradient does not depend on
+    their values)."""
+
+    @staticmethod
+    def forward(ctx, ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, *offsets):
+        n = len(time_offsets)
+        off0, off2 = offsets[:n], offsets[n:]
+        bufs, m = _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2)
+        ctx.save_for_backward(ref0, ref2, filt0, filt2, *offsets)
+        ctx.time_offsets, ctx.map = tuple(time_offsets), m
+        ctx.ctx_layouts = [None if t is None else (t.shape, t.stride()) for t in (ctx0, ctx2)]
+        ctx.set_materialize_grads(False)                   # (an unused output is an absent term, not a tensor of zeros)
+        return (*bufs, *[_ch(buf, m["cur_output"]).clone() for buf in bufs])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        ref0, ref2, filt0, filt2 = ctx.saved_tensors[:4]
+        offsets = ctx.saved_tensors[4:]
+        n, m = len(ctx.time_offsets), ctx.map
+        off = (offsets[:n], offsets[n:])
+        g_buf, g_cur = grads[:n], grads[n:]
+        need = ctx.needs_input_grad
+        like = lambda t: torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)      # noqa: E731
+        # ---- frames, flows, filters: one blend backward per time offset that received a gradient; its flow and filter terms,
+        # then the slice of the buffer's gradient that passed through.  Sums run over t ascending, the kernel's term first.
+        terms = {"ref0": [], "ref2": [], "filt0": [], "filt2": []}
+        g_off = [[None] * n, [None] * n]
+        for t in range(n):
+            gb, gc = g_buf[t], g_cur[t]
+            if gb is None and gc is None:
+                continue
+            g_blend = gc if gb is None else (_ch(gb, m["cur_output"]) if gc is None else _ch(gb, m["cur_output"]) + gc)
+            g_blend, g_out0, g_out2 = _grad_layout([g_blend, None if gb is None else _ch(gb, m["ref0"]),
+                                                    None if gb is None else _ch(gb, m["ref2"])])
+            outs = [like(x) if nd else None for x, nd in
+                    ((ref0, need[0]), (ref2, need[1]), (off[0][t], need[7 + t]), (off[1][t], need[7 + n + t]), (filt0, need[2]),
+                     (filt2, need[3]))]
+            if any(o is not None for o in outs):
+                w0, w2 = float(1.0 - ctx.time_offsets[t]), float(ctx.time_offsets[t])
+                _check(cabi.filterinterp_blend_backward(ref0, ref2, off[0][t], off[1][t], filt0, filt2, g_blend, g_out0, g_out2,
+                                                        w0, w2, *outs), "filterinterp_blend_backward")
+            gr0, gr2, gf0, gf2, gk0, gk2 = outs
+            for d, gf in ((0, gf0), (1, gf2)):
+                if gf is not None:
+                    g_off[d][t] = gf if gb is None else gf + _ch(gb, m["offset%d" % d])
+            for key, kernel, through in (("ref0", gr0, None), ("ref2", gr2, None), ("filt0", gk0, "filter0"), ("filt2", gk2, "filter1")):
+                if kernel is not None:
+                    terms[key].append(kernel)
+                    if through is not None and gb is not None:
+                        terms[key].append(_ch(gb, m[through]))
+        total = {k: (_add_in_order(v) if v else None) for k, v in terms.items()}
+        # ---- context tensors: one image-only call per direction over the buffers that received a gradient, which reads the
+        # context channels of those gradients where they lie
+        g_ctx = [None, None]
+        live = [t for t in range(n) if g_buf[t] is not None]
+        for d, name in ((0, "ctx0"), (1, "ctx2")):
+            if ctx.ctx_layouts[d] is None or not need[4 + d] or not live:
+                continue
+            gs = _grad_layout([_ch(g_buf[t], m[name]) for t in live])
+            shape, stride = ctx.ctx_layouts[d]
+            g_ctx[d] = torch.empty_strided(shape, stride, dtype=torch.float32, device=gs[0].device)      # (written in full)
+            _check(cabi.filterinterp_backward_ori_image_multi([off[d][t] for t in live], (filt0, filt2)[d], gs, g_ctx[d]),
+                   "filterinterp_backward_ori_image_multi")
+        return (total["ref0"], total["ref2"], total["filt0"], total["filt2"], g_ctx[0], g_ctx[1], None, *g_off[0], *g_off[1])
+
+
+def rectify_inputs(ref0, ref2, offsets, filter, filter_size2, time_offsets, ctx0=None, ctx2=None):
+    """The end of the synthesis stage for every time offset of a step (networks/DAIN_slowmotion.py:167-182; without context
+    tensors networks/DAIN.py:255-269): `FilterInterpolate`, `FilterInterpolate_ctx` and the `torch.cat` that builds
+    rectifyNet's input, with the warps written straight into that input.  offsets[d][t] is the projected flow of direction
+    d at time offset t (as for `FilterInterpolate_ctx_all`), filter = [filter of direction 0, of direction 1].
+    Returns [(rectify_input_t, cur_output_t) for t in time_offsets]: rectify_input_t is one freshly allocated contiguous
+    [B, 13 + 2 filter_size2 (+ 2 Cctx), H, W] tensor in the reference's channel order (`rectify_channels`).  The blend and
+    the two warped frames are written into channels 0-8 by vfi_filterinterp_blend_forward, each direction's context warps for
+    all time offsets by one vfi_filterinterp_forward_ori_multi_to call; only the flows and filters (36 channels of 437) are
+    copied.
+    Bit-equal, forward: every channel equals `torch.cat` over `FilterInterpolate` and `FilterInterpolate_ctx_all`.
+    Inference (grad mode off, or no input requires grad): cur_output_t is the view rectify_input_t[:, :3].
+    Training: one autograd Function over all time offsets; cur_output_t is then a dense copy and an output of its own.
+    Frames, flows and filters get the gradient of the blend backward (one vfi_filterinterp_blend_backward per time offset,
+    fed grad_blend = grad(rectify_input_t)[:, 0:3] + grad(cur_output_t)) plus, for flows and filters, the channels of
+    grad(rectify_input_t) that passed through; a context tensor gets one vfi_filterinterp_backward_ori_image_multi call over
+    the context channels of the gradients, read in place.  As on the reference's path the context warps give flows and
+    filters no gradient.  An output the loss did not use is an absent term.
+    Bit-equal, backward: a flow's gradient is kernel term + passed-through slice; a filter's or frame's is the left-to-right
+    sum over t ascending of (kernel term of t, passed-through slice of t).  For one time offset each sum has at most two
+    terms, so every gradient equals autograd's through `torch.cat` over the functions above, bit for bit."""
+    assert filter[0].size(1) == filter_size2
+    time_offsets = [float(t) for t in time_offsets]
+    off0, off2 = list(offsets[0]), list(offsets[1])
+    tensors = [ref0, ref2, filter[0], filter[1], *off0, *off2] + [t for t in (ctx0, ctx2) if t is not None]
+    if _wants_grad(*tensors):
+        outs = _RectifyInputs.apply(ref0, ref2, filter[0], filter[1], ctx0, ctx2, tuple(time_offsets), *off0, *off2)
+        n = len(time_offsets)
+        return list(zip(outs[:n], outs[n:]))
+    bufs, m = _rectify_launch(ref0, ref2, filter[0], filter[1], ctx0, ctx2, time_offsets, off0, off2)
+    return [(buf, _ch(buf, m["cur_output"])) for buf in bufs]
 
 
 class _Warp(torch.autograd.Function):
