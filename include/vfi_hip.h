@@ -399,6 +399,41 @@ int vfi_correlation_backward_f16(const void* input1, const void* input2, const v
                                  int stride1, int stride2,
                                  vfi_stream_t stream);
 
+/* The cost volume on bfloat16 tensors -- the mixed-precision dtype of torch.autocast(dtype=torch.bfloat16).  All
+ * tensors dense NCHW bfloat16 at any 2-byte-aligned address; the argument checks of the _f16 entries (the backward
+ * refuses stride1 != 1).  Nothing is allocated, no workspace, no atomics: the calls are legal inside a stream capture,
+ * every output element is written, nothing else is touched, and the same inputs give the same bits run after run.
+ *
+ * Forward:  out = bf16_rne( (sum over the k x k window and the C channels of x1 * x2) / (float)(k*k*C) ).
+ * Every product is exact in float32 (two 8-bit significands); the sum is accumulated in float32; the mean is rounded to
+ * bfloat16 once, to nearest even.  A tap of the second map that lies in the zero padding is a product with +0 and is
+ * not skipped: inf * 0 is NaN there, as in the reference's physically padded rInput2.
+ *   - PWC-Net's configuration (kernel 1, strides 1, max displacement 4, any pad) from a tile count on:
+ *     the matrix cores, v_mfma_f32_16x16x32_bf16 over 32 channels per instruction.  The order of the float32 additions
+ *     inside an instruction is the hardware's, so the result is within
+ *         2^-8 |R| + (1 + 2^-8) (n + 2) 2^-23 A,   n = k*k*C, R the exact mean, A the same mean over |x1 * x2|,
+ *     of R, not a fixed bit pattern of a float32 chain.  Channel positions the kernel pads up to its K step of 32 hold
+ *     zero in BOTH operands.  bfloat16 SUBNORMAL inputs: the MFMA keeps them (measured on an MI355X, not taken from the
+ *     instruction set document: tools/bench_corr_bf16.py); no test depends on it.
+ *   - every other configuration, and PWC-Net levels below that tile count: one thread per output, bit for bit
+ *     bf16_rne(vfi_correlation_forward(float(x1), float(x2))) -- the float32 kernel's arithmetic in the same order.
+ *
+ * Backward: storage bfloat16, arithmetic that of vfi_correlation_backward term by term on the widened values (float32
+ * products, 32 partials over tc = l, l+32, ..., partials added in sequence, divided by (float)(k*k*C)), rounded to
+ * bfloat16 once: bit for bit bf16_rne(vfi_correlation_backward(float(x1), float(x2), float(g))), NaN positions
+ * included. */
+int vfi_correlation_forward_bf16(const void* input1, const void* input2, void* output,
+                                 int batch, int channel, int h, int w,
+                                 int pad_size, int kernel_size, int max_displacement,
+                                 int stride1, int stride2,
+                                 vfi_stream_t stream);
+int vfi_correlation_backward_bf16(const void* input1, const void* input2, const void* gradoutput,
+                                  void* gradinput1, void* gradinput2,
+                                  int batch, int channel, int h, int w,
+                                  int pad_size, int kernel_size, int max_displacement,
+                                  int stride1, int stride2,
+                                  vfi_stream_t stream);
+
 /* ==== glue either side of the ops above: the reference does these with torch
  * built-ins and Python; here each is one launch.  No reference binding exists for them: the
  * host-side mirrors are <pkg>/fused.py. ========================================================= */

@@ -63,6 +63,8 @@ SIGNATURES = {
     "vfi_correlation_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_pair": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_f16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_forward_bf16": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_backward_bf16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_lrelu_forward": [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_forward_pair": [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_backward": [_p, _p, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
@@ -100,6 +102,8 @@ INTERNAL_SIGNATURES = {
     "vfi_filterinterp_forward_ori_f16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_defor_general": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                                Strides, _p],
+    # (which kernel: 0 the MFMA kernel, 1 the generic kernel)
+    "vfi_correlation_forward_bf16_kernel": [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
 }
 
 _lib = None
@@ -554,29 +558,58 @@ def correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, strid
     return oc.value, oh.value, ow.value
 
 
-def _corr_call(f32_name, f16_name, tensors, *args):
-    """The float entry, or for float16 tensors the reference's at::Half instantiation (no conversion), on the tensors' stream."""
-    half = tensors[0].dtype == torch.float16
-    for t in (tensors if half else tensors[:1]):            # (the float path checks its first tensor, as it always has)
-        _dev(t, torch.float16 if half else torch.float32)
+_CORR_SUFFIX = {torch.float16: "_f16", torch.bfloat16: "_bf16"}     # the 2-byte dtypes with entries of their own
+
+
+def _corr_call(f32_name, tensors, *args):
+    """The float entry; for float16 tensors the reference's at::Half instantiation and for bfloat16 tensors the `_bf16` entry
+    (no conversion; every tensor is checked for dtype and device), on the tensors' stream."""
+    suffix = _CORR_SUFFIX.get(tensors[0].dtype)
+    for t in tensors:                                       # (a 2-byte tensor behind a float32 first one would be read past its end)
+        _dev(t, tensors[0].dtype if suffix else torch.float32)
     device = tensors[0].device
     with torch.cuda.device(device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        err = getattr(lib(), f16_name if half else f32_name)(*[_ptr(t) for t in tensors], *args, stream)
+        err = getattr(lib(), f32_name + (suffix or ""))(*[_ptr(t) for t in tensors], *args, stream)
     if err != 0:
         raise RuntimeError("CUDA call failed")
 
 
 def correlation_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2):
-    """Allocates and returns the output, as the reference binding resizes its `output` argument."""
+    """Allocates and returns the output, as the reference binding resizes its `output` argument.  float32, float16 (the
+    reference's at::Half arithmetic) or bfloat16 (exact products, float32 sums, one rounding: include/vfi_hip.h) -- the
+    output has the inputs' dtype."""
     input1, input2 = input1.contiguous(), input2.contiguous()
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
-    dtype = torch.float16 if input1.dtype == torch.float16 else torch.float32
+    dtype = input1.dtype if input1.dtype in _CORR_SUFFIX else torch.float32
     output = torch.empty((b, oc, oh, ow), dtype=dtype, device=input1.device)
-    _corr_call("vfi_correlation_forward", "vfi_correlation_forward_f16", (input1, input2, output), b, c, h, w, pad_size,
+    _corr_call("vfi_correlation_forward", (input1, input2, output), b, c, h, w, pad_size,
                kernel_size, max_displacement, stride1, stride2)
     return output
+
+
+def correlation_forward_bf16_kernel(which, input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2, out=None):
+    """correlation_forward on bfloat16 tensors through ONE of its two kernels whatever the tile count (internal: tests and
+    tools/bench_corr_bf16.py).  which: "mfma" (PWC-Net's configuration only) or "generic".  `out`: a dense bfloat16 tensor
+    (or view) of the output's shape to write into."""
+    input1, input2 = input1.contiguous(), input2.contiguous()
+    b, c, h, w = input1.shape
+    oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
+    if out is None:
+        out = torch.empty((b, oc, oh, ow), dtype=torch.bfloat16, device=input1.device)
+    if tuple(out.shape) != (b, oc, oh, ow) or not out.is_contiguous():
+        raise RuntimeError("correlation_forward_bf16_kernel: `out` must be a dense tensor of the output's shape")
+    for t in (input1, input2, out):
+        _dev(t, torch.bfloat16)
+    with torch.cuda.device(input1.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(input1.device).cuda_stream)
+        err = lib().vfi_correlation_forward_bf16_kernel({"mfma": 0, "generic": 1}[which], _ptr(input1), _ptr(input2),
+                                                        _ptr(out), b, c, h, w, pad_size, kernel_size, max_displacement, stride1,
+                                                        stride2, stream)
+    if err != 0:
+        raise RuntimeError("CUDA call failed")
+    return out
 
 
 def correlation_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displacement, stride1, stride2):
@@ -605,7 +638,7 @@ def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_
             tuple(gradoutput.shape) != (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2):
         raise RuntimeError("correlation_backward: input2 / gradoutput do not match input1's shape and the output dimensions")
     g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
-    _corr_call("vfi_correlation_backward", "vfi_correlation_backward_f16", (input1, input2, gradoutput, g1, g2), b, c, h, w,
+    _corr_call("vfi_correlation_backward", (input1, input2, gradoutput, g1, g2), b, c, h, w,
                pad_size, kernel_size, max_displacement, stride1, stride2)
     return g1, g2
 

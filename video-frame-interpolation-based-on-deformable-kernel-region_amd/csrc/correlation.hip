@@ -1043,7 +1043,7 @@ extern "C" int vfi_correlation_output_dims(int h, int w, int pad_size, int kerne
 // The checks every entry makes before it launches, in this order: a positive shape, no null tensor, valid parameters, and
 // at least one output pixel; the output dimensions come back.  (The reference's backward indexes gradInput rows by
 // blockIdx * stride1 and leaves the tensor for stride1 > 1: only stride1 == 1 is defined.)
-static int corr_check(std::initializer_list<const void*> tensors, int batch, int channel, int h, int w, int pad_size, int kernel_size,
+int vfi::corr_check(std::initializer_list<const void*> tensors, int batch, int channel, int h, int w, int pad_size, int kernel_size,
                       int max_displacement, int stride1, int stride2, bool backward, int* oc, int* oh, int* ow) {
     if (batch <= 0 || channel <= 0 || h <= 0 || w <= 0) return VFI_ERR_SHAPE;
     for (const void* t : tensors)
@@ -1056,7 +1056,7 @@ static int corr_check(std::initializer_list<const void*> tensors, int batch, int
 
 // The tiled backward kernels' split of the channels into groups over blockIdx.z, so that a small level fills the chip
 // (about 2048 workgroups); the group count comes back, 0 where batch * groups does not fit a grid.
-static int corr_backward_groups(int tiles, int batch, int channel, int* ch_per_group) {
+int vfi::corr_backward_groups(int tiles, int batch, int channel, int* ch_per_group) {
     int groups = (int)std::min<int64_t>(channel, std::max<int64_t>(1, (2048 + (int64_t)tiles * batch - 1) / ((int64_t)tiles * batch)));
     *ch_per_group = (channel + groups - 1) / groups;
     groups = (channel + *ch_per_group - 1) / *ch_per_group;

@@ -1,0 +1,487 @@
+// correlation_bf16.hip -- the cost volume on bfloat16 tensors (vfi_correlation_forward_bf16 / _backward_bf16).
+//
+// Storage is bfloat16, arithmetic float32.  A product of two bfloat16 values has 16 significand bits and is exact in
+// float32; the sums are float32; a result is rounded to bfloat16 once, to nearest even (v_cvt_pk_bf16_f32).
+//
+// Forward, PWC-Net's configuration (k == 1, strides 1, max displacement 4): the matrix cores.  For one output row y and one
+// displacement row tj the nine values of a pixel are the band x2 - x1 in [-4, 4] of
+//     C[x1][x2] = sum_c f1[c][y][x1] * f2[c][y + tj - 4][x2],
+// a 16-pixel block of x1 needs 24 columns x2, and two 16x16x32 MFMAs per 32 channels form them (9 of 32 products wanted).
+// Forward, anything else, and small PWC-Net levels: one thread per output, the float32 generic kernel's arithmetic.
+// Backward: the float32 kernels' arithmetic (correlation.hip: corr_backward, corr_backward_k1) on widened values.
+#include "correlation_dev.h"
+
+#include <climits>
+
+namespace vfi {
+
+typedef unsigned short bf16_t;                                  // the storage bits
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float bf16_widen(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
+// two floats to two bfloat16, round to nearest even, NaN stays NaN: one v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned bf16_pack_rne(float lo, float hi) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
+}
+__device__ __forceinline__ bf16_t bf16_rne(float v) { return (bf16_t)(bf16_pack_rne(v, 0.0f) & 0xffffu); }
+
+// ---------------------------------------------------------------------------------------------------------------- forward, MFMA
+//
+// A workgroup owns TW = 64 output pixels of TH = 2 output rows of one image; wave tj (of 9) owns displacement row tj.  Per
+// chunk of 32 channels the workgroup stages the first map's TH x 64 pixels and the second map's (TH + 8) x 80 window
+// (origin 4 left and 4 above the tile's centre pixels) in LDS TRANSPOSED, [row][pixel][32 channels]: a thread fetches the 8
+// channels of one pixel and one channel group with eight 2-byte buffer loads (a wave's lanes are 64 adjacent pixels of a
+// plane: 128-byte segments) and writes them as one 16-byte unit, which is exactly what a lane of
+// v_mfma_f32_16x16x32_bf16 holds: lane l has A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15],
+// j = 0..7.  A pixel's four units are 64 bytes; the unit of channel group g of pixel p sits in slot g ^ ((p >> 2) & 3), so
+// the 16 lanes of a quarter wave (16 adjacent pixels, one group) touch 16 different 16-byte bank groups in the staging
+// writes and in the operand reads alike.
+//
+// The loads go through a buffer descriptor that spans exactly the chunk's planes of the image: a pixel outside the frame
+// has an offset out of any range and a channel past the last one falls out of the descriptor's, and both arrive as +0 --
+// the zero padding (multiplied, not skipped: inf * 0 = NaN) and the zero fill of the K tail in BOTH operands.
+//
+// Per row and chunk a wave reads 4 A and 5 B operands and issues 8 MFMAs: pixel block m (16 pixels) against window blocks m
+// and m + 1.  Accumulator (lane l, register v) of block pair (m, m + s) is C[x1 = 16 m + 4 (l >> 4) + v][x2 = 16 (m + s) +
+// (l & 15)], displacement column ti = x2 - x1 (the window starts 4 to the left): the values with 0 <= ti <= 8 go to a
+// wave-private LDS array [row][ti][64 pixels] (laid over the window), and come back with a lane owning two adjacent
+// pixels: divide, one v_cvt_pk_bf16_f32, one 4-byte store -- a wave writes whole 128-byte segments of an output row per
+// plane (2-byte stores where a pair is not 4-byte aligned or is cut by the frame).
+template <int MT_, int TH_>
+struct CorrMfmaTile {
+    static constexpr int MD = 4, D = 2 * MD + 1, MT = MT_, TW = 16 * MT, TH = TH_, NB = MT + 1, BW = 16 * NB, LH = TH + 2 * MD;
+    static constexpr int KC = 32, KG = KC / 8, NT = 64 * D;                     // channels per chunk, 16-byte units per pixel, threads
+    static constexpr int A_UNITS = TH * TW * KG, B_UNITS = LH * BW * KG;
+    static constexpr int NPA = (A_UNITS + NT - 1) / NT, NPB = (B_UNITS + NT - 1) / NT;
+    static constexpr int TP = TW + 2;                                           // pitch of a row of the epilogue array, floats
+    static constexpr int LDS_BYTES = (A_UNITS + B_UNITS) * 16;
+    static_assert(D * TH * D * TP * 4 <= LDS_BYTES, "the epilogue arrays fit over the staged chunk");
+    static_assert(LDS_BYTES <= 64 * 1024, "static LDS");
+    static_assert(128 % TW == 0, "a wave's lanes are whole rows of pixel pairs");
+    // slot of pixel p's channel group g, in units
+    static __device__ __forceinline__ int unit(int p, int g) { return p * KG + (g ^ ((p >> 2) & (KG - 1))); }
+};
+
+template <class T>
+__device__ __forceinline__ void corr_mfma_bf16_body(
+    const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
+    int channel, int h, int w, int oh, int ow, int org, u32x4* lds) {
+    constexpr int D = T::D, TW = T::TW, TH = T::TH, MT = T::MT, NB = T::NB, BW = T::BW, LH = T::LH, KG = T::KG, NT = T::NT;
+    constexpr unsigned OUTSIDE = 0x80000000u;
+    const int lane = threadIdx.x, tj = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    const int tid = tj * 64 + lane;
+    const int ox0 = blockIdx.x * TW, oy0 = blockIdx.y * TH, b = blockIdx.z;
+    const int plane = h * w;
+    const unsigned plane2 = 2u * (unsigned)plane;
+    const bf16_t* f1 = in1 + (int64_t)b * channel * plane;
+    const bf16_t* f2 = in2 + (int64_t)b * channel * plane;
+    u32x4* lds_a = lds;
+    u32x4* lds_b = lds + T::A_UNITS;
+
+    // staging plan, the same for every chunk: unit e = tid + k * NT of the [KG][rows][pixels] block -> the byte offset of
+    // its first channel from the chunk's first plane, and its LDS slot
+    unsigned aoff[T::NPA], boff[T::NPB];
+    int aslot[T::NPA], bslot[T::NPB];
+#pragma unroll
+    for (int k = 0; k < T::NPA; ++k) {
+        const int e = tid + k * NT;
+        const int p = e % TW, r = (e / TW) % TH, g = e / (TW * TH);
+        const int gy = oy0 + r + org, gx = ox0 + p + org;
+        const bool ok = e < T::A_UNITS && gy >= 0 && gy < h && gx >= 0 && gx < w;
+        aoff[k] = ok ? 2u * (unsigned)(8 * g * plane + gy * w + gx) : OUTSIDE;
+        aslot[k] = e < T::A_UNITS ? r * TW * KG + T::unit(p, g) : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < T::NPB; ++k) {
+        const int e = tid + k * NT;
+        const int q = e % BW, r = (e / BW) % LH, g = e / (BW * LH);
+        const int gy = oy0 + r + org - T::MD, gx = ox0 + q + org - T::MD;
+        const bool ok = e < T::B_UNITS && gy >= 0 && gy < h && gx >= 0 && gx < w;
+        boff[k] = ok ? 2u * (unsigned)(8 * g * plane + gy * w + gx) : OUTSIDE;
+        bslot[k] = e < T::B_UNITS ? r * BW * KG + T::unit(q, g) : -1;
+    }
+
+    f32x4 acc[TH][MT][2];
+#pragma unroll
+    for (int r = 0; r < TH; ++r)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) { acc[r][m][0] = f32x4{0, 0, 0, 0}; acc[r][m][1] = f32x4{0, 0, 0, 0}; }
+
+    // a unit: the 8 channels of one pixel
+    auto fetch = [&](const __amdgpu_buffer_rsrc_t& d, unsigned off) {
+        unsigned v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            v[j] = __builtin_amdgcn_raw_buffer_load_b16(d, off == OUTSIDE ? OUTSIDE : off + (unsigned)j * plane2, 0, 0);
+        return u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
+    };
+    const int li = lane & 15, lg = lane >> 4;
+    const int opslot = T::unit(li, lg);                                          // (16 m + li has li's swizzle bits)
+
+    for (int c0 = 0; c0 < channel; c0 += T::KC) {
+        const int cn = min(T::KC, channel - c0);
+        const auto d1 = buffer_rsrc(f1 + (int64_t)c0 * plane, cn * (int)plane2);
+        const auto d2 = buffer_rsrc(f2 + (int64_t)c0 * plane, cn * (int)plane2);
+        // (SB units -- 8 SB loads -- in flight per thread at a time.  All of a chunk's at once was measured SLOWER, 47.6 us
+        //  against 42.8 at 32 x 288 x 496: the 2-byte loads' instruction count bounds the kernel, not their latency -- DESIGN.md 4.3a-4)
+        constexpr int SB = 2;
+        if (c0) __syncthreads();                                                 // the previous chunk has been read
+#pragma unroll
+        for (int k0 = 0; k0 < T::NPB; k0 += SB) {
+            u32x4 u[SB];
+#pragma unroll
+            for (int k = k0; k < k0 + SB && k < T::NPB; ++k) u[k - k0] = fetch(d2, boff[k]);
+#pragma unroll
+            for (int k = k0; k < k0 + SB && k < T::NPB; ++k)
+                if (bslot[k] >= 0) lds_b[bslot[k]] = u[k - k0];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int k = 0; k < T::NPA; ++k) {
+            const u32x4 u = fetch(d1, aoff[k]);
+            if (aslot[k] >= 0) lds_a[aslot[k]] = u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < TH; ++r) {
+            bf16x8 a[MT], bb[NB];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) a[m] = __builtin_bit_cast(bf16x8, lds_a[(r * TW + 16 * m) * KG + opslot]);
+#pragma unroll
+            for (int n = 0; n < NB; ++n) bb[n] = __builtin_bit_cast(bf16x8, lds_b[((r + tj) * BW + 16 * n) * KG + opslot]);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                acc[r][m][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], bb[m], acc[r][m][0], 0, 0, 0);
+                acc[r][m][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], bb[m + 1], acc[r][m][1], 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();                                                             // the window has been read: it becomes the epilogue arrays
+
+    float* t = reinterpret_cast<float*>(lds) + tj * (TH * D * T::TP);
+#pragma unroll
+    for (int r = 0; r < TH; ++r)
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int i = 4 * lg + v, ti = li - i + 16 * s;
+                    if (ti >= 0 && ti < D) t[(r * D + ti) * T::TP + 16 * m + i] = acc[r][m][s][v];
+                }
+    __syncthreads();
+
+    const float nelems = (float)channel;
+    // a lane owns one pixel pair; the wave's lanes are 128 / TW row segments (row r, displacement column ti) at a time
+    const int px = 2 * (lane % (TW / 2)), ox = ox0 + px;
+    const bool pair = ox + 1 < ow;
+    for (int u = lane / (TW / 2); u < TH * D; u += 128 / TW) {
+        const int r = u / D, ti = u - r * D;
+        const int oy = oy0 + r;
+        if (oy >= oh || ox >= ow) continue;
+        const f32x2 s = *reinterpret_cast<const f32x2*>(&t[u * T::TP + px]);
+        const unsigned two = bf16_pack_rne(s.x / nelems, s.y / nelems);
+        bf16_t* op = out + (((int64_t)b * (D * D) + tj * D + ti) * oh + oy) * ow + ox;
+        if (pair && (reinterpret_cast<uintptr_t>(op) & 3) == 0) {
+            *reinterpret_cast<unsigned*>(op) = two;
+        } else {
+            op[0] = (bf16_t)(two & 0xffffu);
+            if (pair) op[1] = (bf16_t)(two >> 16);
+        }
+    }
+}
+
+// (the body is a device function: the matrix-core builtin must not be instantiated by the host pass)
+template <class T>
+__global__ __launch_bounds__(T::NT) void corr_forward_k1_mfma_bf16(
+    const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
+    int channel, int h, int w, int oh, int ow, int org) {
+    __shared__ __attribute__((aligned(16))) u32x4 lds[T::LDS_BYTES / 16];
+    corr_mfma_bf16_body<T>(in1, in2, out, channel, h, w, oh, ow, org, lds);
+}
+typedef CorrMfmaTile<4, 2> CorrMfma;
+
+// ---------------------------------------------------------------------------------------------------------------- forward, generic
+//
+// Any kernel size / strides: one thread per output element, the arithmetic of corr_forward_generic (correlation.hip) on the
+// widened values -- window rows outer, columns inner, channels in sequence, acc = fmaf(a, b, acc), the mean by division --
+// rounded to bfloat16 once: bit for bit bf16_rne of the float32 entry on the widened maps.  A tap outside a map is the
+// padding's +0 and is multiplied; outside both maps the term is fmaf(0, 0, acc) = acc (acc starts at +0 and is never -0) and
+// is skipped.  With one tap inside, the lane runs the same loop: its outside tap is read at the inside tap's pixel (a valid
+// address) and cleared by `keep`; eight channels of loads in flight (corr_forward_k1_flat's way, which this kernel stands
+// in for at the small PWC-Net levels).
+__global__ __launch_bounds__(256) void corr_forward_generic_bf16(
+    const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1, int s2, int dr) {
+    const int64_t total = (int64_t)batch * oc * oh * ow;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int ox = (int)(gid % ow);
+    const int oy = (int)((gid / ow) % oh);
+    const int tc = (int)((gid / ((int64_t)ow * oh)) % oc);
+    const int b = (int)(gid / ((int64_t)ow * oh * oc));
+    const int dsz = 2 * dr + 1;
+    const int ti = tc % dsz - dr, tj = tc / dsz - dr;
+    const int y1 = oy * s1 + md - pad, x1 = ox * s1 + md - pad;     // padded -> input coordinates
+    const int y2 = y1 + tj * s2, x2 = x1 + ti * s2;
+    const int64_t plane = (int64_t)h * w;
+    const bf16_t* f1 = in1 + (int64_t)b * channel * plane;
+    const bf16_t* f2 = in2 + (int64_t)b * channel * plane;
+    float acc = 0.0f;
+    for (int j = -kr; j <= kr; ++j)
+        for (int i = -kr; i <= kr; ++i) {
+            const int ya = y1 + j, xa = x1 + i, yb = y2 + j, xb = x2 + i;
+            const bool oka = ya >= 0 && ya < h && xa >= 0 && xa < w, okb = yb >= 0 && yb < h && xb >= 0 && xb < w;
+            if (!oka && !okb) continue;
+            const int64_t ata = (int64_t)ya * w + xa, atb = (int64_t)yb * w + xb;
+            const bf16_t* pa = (oka ? f1 : f2) + (oka ? ata : atb);
+            const bf16_t* pb = (oka ? f2 : f1) + (okb ? atb : ata);
+            const bf16_t keep = (oka && okb) ? 0xffffu : 0u;
+            int c = 0;
+            for (; c + 8 <= channel; c += 8) {
+                bf16_t va[8], vb[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) { va[q] = pa[(int64_t)(c + q) * plane]; vb[q] = pb[(int64_t)(c + q) * plane] & keep; }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc = fmaf(bf16_widen(va[q]), bf16_widen(vb[q]), acc);
+            }
+            for (; c < channel; ++c) acc = fmaf(bf16_widen(pa[(int64_t)c * plane]), bf16_widen(pb[(int64_t)c * plane] & keep), acc);
+        }
+    const int k = 2 * kr + 1;
+    out[gid] = bf16_rne(acc / (float)(k * k * channel));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- backward
+//
+// corr_backward (correlation.hip) on bfloat16 storage: one thread per gradient element, float32 terms s = fmaf(g, v, s) in 32
+// partials over tc = l, l + 32, ..., the partials added in sequence, r / (float)(k*k*C), rounded to bfloat16 once.  A term
+// whose other-map tap lies in the zero padding is not skipped (g * 0: NaN for an infinite g).
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward_bf16(
+    const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr) {
+    const int64_t total = (int64_t)batch * channel * h * w;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int bx = (int)(gid % w);
+    const int by = (int)((gid / w) % h);
+    const int c = (int)((gid / ((int64_t)w * h)) % channel);
+    const int n = (int)(gid / ((int64_t)w * h * channel));
+    const int dsz = 2 * dr + 1;
+    const int y = by + pad, x = bx + pad;                   // padded coordinates
+    const bf16_t* of = other + ((int64_t)n * channel + c) * h * w;
+    const bf16_t* go = gout + (int64_t)n * oc * oh * ow;
+    const float nelems = (float)((2 * kr + 1) * (2 * kr + 1) * channel);
+    bool any = SECOND;
+    if constexpr (!SECOND) {
+        const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
+        any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
+    }
+    if (!any) {
+        gin[gid] = 0;                                       // +0: the binding zero-fills gradInput
+        return;
+    }
+    float r = 0.0f;
+    for (int l = 0; l < 32; ++l) {
+        float s = 0.0f;
+        for (int tc = l; tc < oc; tc += 32) {
+            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
+            int xmin, ymin, xmax, ymax, vy, vx;
+            if constexpr (SECOND) {
+                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
+                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
+                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
+                vy = y - j2 - pad; vx = x - i2 - pad;
+            } else {
+                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
+                vy = y + j2 - pad; vx = x + i2 - pad;
+            }
+            const float val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? bf16_widen(of[(int64_t)vy * w + vx]) : 0.0f;
+            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
+            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
+            const bf16_t* g = go + (int64_t)tc * oh * ow;
+            for (int j = ymin; j <= ymax; ++j)
+                for (int i = xmin; i <= xmax; ++i) s = fmaf(bf16_widen(g[(int64_t)j * ow + i]), val, s);
+        }
+        r += s;
+    }
+    gin[gid] = bf16_rne(r / nelems);
+}
+
+// corr_backward_k1 (correlation.hip) on bfloat16 storage, PWC-Net's configuration (k == 1, strides 1, pad == md == 4): a thread
+// owns one pixel of a 64x4 tile, its 81 gradOutput values widened into registers for all channels of the group; per channel
+// the workgroup stages the other map's 12x72 window, widened, in LDS (double-buffered, zero padded).  The same float32
+// terms in the same order as corr_backward_bf16, so the same bits.  (A term the reference skips -- gradInput2, displaced
+// position outside the frame -- has g = 0 and meets the window's zero padding: fma(0, 0, s) = s.)
+template <bool SECOND>
+__global__ __launch_bounds__(256) void corr_backward_k1_bf16(
+    const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
+    int channel, int h, int w, int groups, int ch_per_group) {
+    typedef CorrBwdTile T;
+    constexpr int MD = T::MD, D = T::D, OC = T::OC;
+    __shared__ float win[2][T::LH][T::LW];
+    const T t(channel, groups, ch_per_group);
+    const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
+    const int bx = t.x0 + px, by = t.y0 + py;
+    const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
+    const bool in = bx < w && by < h;
+    const int64_t plane = (int64_t)h * w;
+    const bf16_t* go = gout + (int64_t)n * OC * plane;
+
+    float g[OC];
+#pragma unroll
+    for (int tc = 0; tc < OC; ++tc) {
+        const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
+        g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? bf16_widen(go[(int64_t)tc * plane + (int64_t)gy * w + gx]) : 0.0f;
+    }
+
+    auto stage = [&](int c, int buf) {
+        const bf16_t* of = other + ((int64_t)n * channel + c) * plane;
+        for (int e = tid; e < T::LH * T::LW; e += 256) {
+            const T::Elem p = t.window(e);
+            win[buf][p.r][p.col] = (p.gy >= 0 && p.gy < h && p.gx >= 0 && p.gx < w) ? bf16_widen(of[(int64_t)p.gy * w + p.gx]) : 0.0f;
+        }
+    };
+    if (c_begin >= c_end) return;
+    stage(c_begin, 0);
+    const float nelems = (float)channel;
+    for (int c = c_begin; c < c_end; ++c) {
+        const int buf = (c - c_begin) & 1;
+        __syncthreads();                                    // window c has been written; window c - 1 has been read
+        if (c + 1 < c_end) stage(c + 1, buf ^ 1);
+        float r = 0.0f;
+#pragma unroll
+        for (int l = 0; l < 32; ++l) {
+            float s = 0.0f;
+#pragma unroll
+            for (int tc = l; tc < OC; tc += 32) {
+                const int tj = tc / D, ti = tc % D;
+                const float v = SECOND ? win[buf][py + 2 * MD - tj][px + 2 * MD - ti] : win[buf][py + tj][px + ti];
+                s = fmaf(g[tc], v, s);
+            }
+            r += s;
+        }
+        if (in) gin[((int64_t)n * channel + c) * plane + (int64_t)by * w + bx] = bf16_rne(r / nelems);
+    }
+}
+
+}  // namespace vfi
+
+using namespace vfi;
+
+// Number of 64x2 tiles of the MFMA forward kernel from which PWC-Net's configuration uses it; below it the level takes the
+// one-thread-per-output kernel.
+// Measured back to back, hot, MFMA vs generic (tools/bench_corr_bf16.py `choice` lines, profiles/corr_bf16_bench.txt): the
+// MFMA kernel is faster at the five levels of 48 tiles and more (48 tiles, B=3 64 x 32 x 56: 10.8 vs 12.6 us; 72 tiles,
+// 96 x 72 x 124: 12.7 vs 23.5), the generic kernel at the five of 24 and fewer (24 tiles, B=3 96 x 16 x 28: 12.4 vs 10.8;
+// 18 tiles, 128 x 36 x 62: 15.9 vs 12.0; 9 tiles, 196 x 18 x 31: 22.2 vs 10.9 -- its channel loop is long there, but a
+// launch this small is latency either way, and the MFMA kernel's chunk loop is seven dependent round trips).  Nothing was
+// measured between 24 and 48.
+static constexpr long long corr_bf16_mfma_threshold = 32;
+
+static bool corr_bf16_is_pwc(int kernel_size, int max_displacement, int stride1, int stride2) {
+    return kernel_size == 1 && stride1 == 1 && stride2 == 1 && max_displacement == 4;
+}
+
+// whether the MFMA kernel can take the frame: a chunk of 32 planes through one buffer descriptor, the grid's limits
+static bool corr_bf16_mfma_fits(int batch, int h, int w, int oh) {
+    return (int64_t)h * w * 2 * CorrMfma::KC < INT_MAX && batch <= 65535 && (oh + CorrMfma::TH - 1) / CorrMfma::TH <= 65535;
+}
+
+template <class T>
+static int corr_bf16_launch_mfma(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oh,
+                                 int ow, int org, hipStream_t st) {
+    const dim3 grid((ow + T::TW - 1) / T::TW, (oh + T::TH - 1) / T::TH, batch);
+    hipLaunchKernelGGL(corr_forward_k1_mfma_bf16<T>, grid, dim3(64, T::D, 1), 0, st, (const bf16_t*)input1, (const bf16_t*)input2,
+                       (bf16_t*)output, channel, h, w, oh, ow, org);
+    return launch_status();
+}
+
+static int corr_bf16_launch_generic(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oc,
+                                    int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+                                    hipStream_t st) {
+    const int64_t total = (int64_t)batch * oc * oh * ow;
+    if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
+    hipLaunchKernelGGL(corr_forward_generic_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)input1,
+                       (const bf16_t*)input2, (bf16_t*)output, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2,
+                       max_displacement, stride1, stride2, max_displacement / stride2);
+    return launch_status();
+}
+
+extern "C" int vfi_correlation_forward_bf16(const void* input1, const void* input2, void* output, int batch, int channel,
+                                             int h, int w, int pad_size, int kernel_size, int max_displacement,
+                                             int stride1, int stride2, vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
+                   &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) && corr_bf16_mfma_fits(batch, h, w, oh)) {
+        const int64_t mfma_tiles = (int64_t)((ow + CorrMfma::TW - 1) / CorrMfma::TW) * ((oh + CorrMfma::TH - 1) / CorrMfma::TH) * batch;
+        if (mfma_tiles >= corr_bf16_mfma_threshold) {
+            return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size,
+                                         (hipStream_t)stream);
+        }
+    }
+    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
+                                    stride1, stride2, (hipStream_t)stream);
+}
+
+// One kernel of vfi_correlation_forward_bf16 whatever the tile count (internal: the tests and tools/bench_corr_bf16.py run
+// both kernels on the same frames).  which: 0 the MFMA kernel (PWC-Net's configuration only), 1 the generic kernel.
+extern "C" int vfi_correlation_forward_bf16_kernel(int which, const void* input1, const void* input2, void* output, int batch,
+                                                    int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
+                                                    int stride1, int stride2, vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
+                   &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (which == 0) {
+        if (!corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) || !corr_bf16_mfma_fits(batch, h, w, oh)) return VFI_ERR_SHAPE;
+        return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size, (hipStream_t)stream);
+    }
+    if (which != 1) return VFI_ERR_SHAPE;
+    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
+                                    stride1, stride2, (hipStream_t)stream);
+}
+
+// one gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1
+static int corr_bf16_backward_one(bool second, const bf16_t* other, const bf16_t* gout, bf16_t* gin, int batch, int channel, int h, int w,
+                                  int oc, int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st) {
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
+        int ch_per_group;
+        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
+        if (groups) {
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
+            hipLaunchKernelGGL(second ? corr_backward_k1_bf16<true> : corr_backward_k1_bf16<false>, grid, dim3(256), 0, st, other, gout,
+                               gin, channel, h, w, groups, ch_per_group);
+            return launch_status();
+        }
+    }
+    const int64_t total = (int64_t)batch * channel * h * w;
+    if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
+    hipLaunchKernelGGL(second ? corr_backward_bf16<true> : corr_backward_bf16<false>, dim3((unsigned)((total + 255) / 256)), dim3(256),
+                       0, st, other, gout, gin, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2, max_displacement,
+                       stride2, max_displacement / stride2);
+    return launch_status();
+}
+
+extern "C" int vfi_correlation_backward_bf16(const void* input1, const void* input2, const void* gradoutput,
+                                              void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
+                                              int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+                                              vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                   stride1, stride2, true, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int err = corr_bf16_backward_one(false, (const bf16_t*)input2, (const bf16_t*)gradoutput, (bf16_t*)gradinput1, batch, channel, h, w,
+                                           oc, oh, ow, pad_size, kernel_size, max_displacement, stride2, st);
+    if (err != VFI_OK) return err;
+    return corr_bf16_backward_one(true, (const bf16_t*)input1, (const bf16_t*)gradoutput, (bf16_t*)gradinput2, batch, channel, h, w, oc,
+                                  oh, ow, pad_size, kernel_size, max_displacement, stride2, st);
+}

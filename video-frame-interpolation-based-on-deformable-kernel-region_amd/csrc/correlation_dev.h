@@ -4,6 +4,8 @@
 #pragma once
 #include "vfi_common.h"
 
+#include <initializer_list>
+
 namespace vfi {
 
 #define CORR_CC_ROWS 8   // channels staged per LDS fill by the wave-per-displacement-row kernels (16 measured the same: their chunk loop is LDS-bound, one workgroup per CU)
@@ -137,5 +139,11 @@ struct CorrBwdTile {
         return {r, col, y0 - MD + r, x0 - MD + col};
     }
 };
+
+// Host side, defined in correlation.hip and shared with correlation_bf16.hip: the checks every entry makes before it
+// launches, and the tiled backward kernels' split of the channels into groups.
+int corr_check(std::initializer_list<const void*> tensors, int batch, int channel, int h, int w, int pad_size, int kernel_size,
+               int max_displacement, int stride1, int stride2, bool backward, int* oc, int* oh, int* ow);
+int corr_backward_groups(int tiles, int batch, int channel, int* ch_per_group);
 
 }  // namespace vfi

@@ -31,7 +31,9 @@ struct StreamScope {
     vfi_stream_t stream;
     explicit StreamScope(const at::Tensor& t, bool allow_half = false) {
         TORCH_CHECK(t.is_cuda(), "expected a GPU tensor");
-        TORCH_CHECK(t.scalar_type() == at::kFloat || (allow_half && t.scalar_type() == at::kHalf), "expected float32 tensors");
+        // (allow_half: the correlation's two 2-byte dtypes, at::Half and bfloat16)
+        TORCH_CHECK(t.scalar_type() == at::kFloat || (allow_half && (t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16)),
+                    "expected float32 tensors");
         guard.set_device(t.device());
         stream = (vfi_stream_t)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.get_device()).stream();
     }
@@ -473,11 +475,13 @@ int correlation_forward(at::Tensor& input1, at::Tensor& input2, at::Tensor& rInp
     at::Tensor a = input1.contiguous(), b = input2.contiguous();   // the reference kernels assume dense NCHW
     StreamScope s(a, /*allow_half=*/true);
     int err;
-    if (a.scalar_type() == at::kHalf) {         // AT_DISPATCH_FLOATING_TYPES_AND_HALF (correlation_cuda_kernel.cu:386, 403)
-        TORCH_CHECK(b.scalar_type() == at::kHalf && output.scalar_type() == at::kHalf && a.is_cuda() && b.is_cuda() &&
-                    output.is_cuda(), "correlation_cuda.forward: half inputs need a half output on the GPU");
-        err = vfi_correlation_forward_f16(a.data_ptr(), b.data_ptr(), output.data_ptr(), batch, channel, h, w, pad_size,
-                                          kernel_size, max_displacement, stride1, stride2, s.stream);
+    const auto dt = a.scalar_type();
+    if (dt == at::kHalf || dt == at::kBFloat16) {   // kHalf: AT_DISPATCH_FLOATING_TYPES_AND_HALF (correlation_cuda_kernel.cu:386, 403); kBFloat16: the _bf16 entry
+        TORCH_CHECK(b.scalar_type() == dt && output.scalar_type() == dt && a.is_cuda() && b.is_cuda() && output.is_cuda(),
+                    "correlation_cuda.forward: half / bfloat16 inputs need an output of their dtype on the GPU");
+        err = (dt == at::kHalf ? vfi_correlation_forward_f16 : vfi_correlation_forward_bf16)(
+            a.data_ptr(), b.data_ptr(), output.data_ptr(), batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
+            stride2, s.stream);
     } else {
         err = vfi_correlation_forward(cptr(a), cptr(b), mptr(output), batch, channel, h, w, pad_size,
                                       kernel_size, max_displacement, stride1, stride2, s.stream);
@@ -499,14 +503,15 @@ int correlation_backward(at::Tensor& input1, at::Tensor& input2, at::Tensor& rIn
     at::Tensor a = input1.contiguous(), b = input2.contiguous(), g = gradOutput.contiguous();
     StreamScope s(a, /*allow_half=*/true);
     int err;
-    if (a.scalar_type() == at::kHalf) {         // AT_DISPATCH_FLOATING_TYPES_AND_HALF (correlation_cuda_kernel.cu:495-541)
-        TORCH_CHECK(b.scalar_type() == at::kHalf && g.scalar_type() == at::kHalf && gradInput1.scalar_type() == at::kHalf &&
-                    gradInput2.scalar_type() == at::kHalf && b.is_cuda() && g.is_cuda() && gradInput1.is_cuda() &&
+    const auto dt = a.scalar_type();
+    if (dt == at::kHalf || dt == at::kBFloat16) {   // kHalf: AT_DISPATCH_FLOATING_TYPES_AND_HALF (correlation_cuda_kernel.cu:495-541); kBFloat16: the _bf16 entry
+        TORCH_CHECK(b.scalar_type() == dt && g.scalar_type() == dt && gradInput1.scalar_type() == dt &&
+                    gradInput2.scalar_type() == dt && b.is_cuda() && g.is_cuda() && gradInput1.is_cuda() &&
                     gradInput2.is_cuda(),
-                    "correlation_cuda.backward: half input1 needs half input2, gradOutput, gradInput1 and gradInput2 on the GPU");
-        err = vfi_correlation_backward_f16(a.data_ptr(), b.data_ptr(), g.data_ptr(), gradInput1.data_ptr(),
-                                           gradInput2.data_ptr(), batch, channel, h, w, pad_size, kernel_size,
-                                           max_displacement, stride1, stride2, s.stream);
+                    "correlation_cuda.backward: half / bfloat16 input1 needs input2, gradOutput, gradInput1 and gradInput2 of its dtype on the GPU");
+        err = (dt == at::kHalf ? vfi_correlation_backward_f16 : vfi_correlation_backward_bf16)(
+            a.data_ptr(), b.data_ptr(), g.data_ptr(), gradInput1.data_ptr(), gradInput2.data_ptr(), batch, channel, h, w, pad_size,
+            kernel_size, max_displacement, stride1, stride2, s.stream);
     } else {
         err = vfi_correlation_backward(cptr(a), cptr(b), cptr(g), mptr(gradInput1), mptr(gradInput2), batch,
                                        channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,

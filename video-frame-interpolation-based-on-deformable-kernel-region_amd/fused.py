@@ -574,7 +574,8 @@ class _Warp(torch.autograd.Function):
 
 
 class _Corr(torch.autograd.Function):
-    """PWC-Net's correlation (pad 4, k 1, md 4, strides 1) on the C ABI, forward and backward."""
+    """PWC-Net's correlation (pad 4, k 1, md 4, strides 1) on the C ABI, forward and backward.  float32, float16 or
+    bfloat16 (all tensors of one dtype: `cabi.correlation_forward` / `correlation_backward` dispatch on it)."""
 
     @staticmethod
     def forward(ctx, c1, c2):
@@ -595,7 +596,8 @@ def _wants_grad(*tensors):
 
 def warp(x, flo, align_corners=True):
     """`PWCDCNet.warp`.  Differentiable when grad mode is on and x or flo requires grad; otherwise the plain forward
-    launch (no grad_fn)."""
+    launch (no grad_fn).  float32 only (anything else raises): torch's own grid_sample runs in float32 under autocast too,
+    so in a bfloat16 network cast the result back for the correlation, `warp(c2.float(), flo).to(c1.dtype)`."""
     if _wants_grad(x, flo):
         return _Warp.apply(x, flo, bool(align_corners))
     out = torch.empty_like(x)
@@ -610,7 +612,8 @@ def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
     MI355X at PWC-Net's sizes (0.33 vs 0.15 ms for the five levels of a 1080p pair): every tile re-forms the bilinear
     samples of its 4-pixel halo (3.75 x the taps), which costs more than the 2 x 18 MB round trip it saves.
     Differentiable when grad mode is on and an input requires grad: then the two-launch path (one_launch is ignored;
-    same bits), whose warped tensor the correlation backward needs."""
+    same bits), whose warped tensor the correlation backward needs.  float32 only, because `warp` is; the correlation half
+    alone takes bfloat16 and float16 (`_Corr.apply(c1, warp(c2.float(), flo).to(c1.dtype))`)."""
     if _wants_grad(c1, c2, flo):
         return _Corr.apply(c1, warp(c2, flo, align_corners))
     if one_launch:
@@ -642,7 +645,7 @@ def corr_pair(c1_a, c2_a, c1_b, c2_b):
     300 for the (I0, I1) network and again for (I1, I0): networks/DAIN.py:196-202) in one launch; returns both cost volumes.
     Differentiable when grad mode is on and one of the four inputs requires grad: the backward is then ONE call for the
     gradients that are needed (each bit-equal to the single correlation's; reproducible).  Otherwise the plain forward
-    launch (no grad_fn)."""
+    launch (no grad_fn).  float32 only: bfloat16 and float16 tensors raise (the single correlation takes them)."""
     if _wants_grad(c1_a, c2_a, c1_b, c2_b):
         return _CorrPair.apply(c1_a, c2_a, c1_b, c2_b)
     return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
@@ -699,7 +702,8 @@ def corr_lrelu(c1, c2, negative_slope=0.1, out=None):
     the bits of F.leaky_relu on the correlation's output.  Differentiable when grad mode is on and an input requires grad
     (one backward call, which masks the gradient as it loads it and takes torch.cat's strided gradient without a copy).
     Otherwise the plain launch, and out= may name where to write: buf[:, k:k + 81] of the contiguous NCHW buffer the
-    reference would get from `torch.cat((corr, ...), 1)`."""
+    reference would get from `torch.cat((corr, ...), 1)`.  float32 only, as `warp_corr_lrelu` and `corr_pair_lrelu` are:
+    bfloat16 and float16 tensors raise (use `_Corr` / `Correlation` and torch's leaky_relu)."""
     if _wants_grad(c1, c2):
         _no_out_in_grad_mode(out, "corr_lrelu")
         return _CorrLrelu.apply(c1, c2, float(negative_slope))
