@@ -341,7 +341,7 @@ int vfi_correlation_backward_pair(const float* input1_a, const float* input2_a, 
                                   int stride1, int stride2,
                                   vfi_stream_t stream);
 /* ---- the correlation with PWC-Net's LeakyReLU fused in (PWCNet/PWCNet.py:230-301: every `self.corr(...)` is followed by
- * `self.leakyRELU(corr)` and a `torch.cat((corr, ...), 1)`).  float32 only.  Each entry is its unactivated twin with the
+ * `self.leakyRELU(corr)` and a `torch.cat((corr, ...), 1)`).  float32 (the single entries' bfloat16 twins: further down).  Each entry is its unactivated twin with the
  * same argument checks, the same kernels and the same kernel choice, plus:
  *   forward:  y = v > 0 ? v : v * negative_slope applied to every mean v as it is stored -- one float multiplication, the
  *     bits of torch.nn.functional.leaky_relu on the twin's output (NaN stays NaN, -0 becomes -0 * negative_slope).
@@ -433,6 +433,31 @@ int vfi_correlation_backward_bf16(const void* input1, const void* input2, const 
                                   int pad_size, int kernel_size, int max_displacement,
                                   int stride1, int stride2,
                                   vfi_stream_t stream);
+
+/* The bfloat16 cost volume with PWC-Net's LeakyReLU fused in: vfi_correlation_forward_bf16 / _backward_bf16 with the same
+ * argument checks, the same kernels, the same kernel choice, plus the rules of the float32 lrelu entries above for
+ * negative_slope (finite and > 0, else VFI_ERR_SHAPE) and the batch strides (in ELEMENTS, the 81 planes of an image
+ * contiguous, a stride below out_channels * out_h * out_w is VFI_ERR_SHAPE).  No workspace, no atomics.
+ *   forward:  the bits of the composition it replaces, torch's leaky_relu on the bfloat16 cost volume: the mean is rounded
+ *     to bfloat16 FIRST; a value that is not positive is then multiplied by negative_slope in float32 and rounded again.
+ *     (One rounding of lrelu(mean) would differ from the unfused network in the last bit, and where a tiny positive mean
+ *     rounds to +0 the backward's mask -- the sign of the saved y -- would differ too.)  An output_batch_stride that is odd
+ *     puts every other image on a 2-byte boundary: the stores test their alignment one by one.
+ *   backward: every gradOutput value g becomes g' = y > 0 ? g : bf16_rne(float(g) * negative_slope) as it is loaded, in both
+ *     kernels and for both gradients; the result is vfi_correlation_backward_bf16 fed a materialised bfloat16 g', bit for
+ *     bit -- what torch autograd gives through leaky_relu on bfloat16.  y and gradoutput are read where they lie. */
+int vfi_correlation_lrelu_forward_bf16(const void* input1, const void* input2, void* output, int64_t output_batch_stride,
+                                       int batch, int channel, int h, int w,
+                                       int pad_size, int kernel_size, int max_displacement,
+                                       int stride1, int stride2, float negative_slope,
+                                       vfi_stream_t stream);
+int vfi_correlation_lrelu_backward_bf16(const void* input1, const void* input2, const void* y, int64_t y_batch_stride,
+                                        const void* gradoutput, int64_t gradoutput_batch_stride,
+                                        void* gradinput1, void* gradinput2,
+                                        int batch, int channel, int h, int w,
+                                        int pad_size, int kernel_size, int max_displacement,
+                                        int stride1, int stride2, float negative_slope,
+                                        vfi_stream_t stream);
 
 /* ==== glue either side of the ops above: the reference does these with torch
  * built-ins and Python; here each is one launch.  No reference binding exists for them: the
@@ -573,6 +598,29 @@ int vfi_pwc_warp_backward(const float* x, const float* flow, const float* grad_o
                           int batch, int channel, int h, int w, int align_corners,
                           vfi_strides sx, vfi_strides sf, vfi_strides sgo, vfi_strides sgx, vfi_strides sgf,
                           vfi_stream_t stream);
+
+/* PWCDCNet.warp on bfloat16 storage.  x, output, grad_output and grad_x are bfloat16; flow is float32, or bfloat16 when
+ * flow_is_bf16 != 0, and grad_flow has the flow's dtype.  Strides in elements with the float32 entries' rules (any batch /
+ * channel / row stride, w stride 1); any 2-byte-aligned address.  Values are widened on load (exact), the arithmetic is the
+ * float32 entries' in their order, and a result is rounded to bfloat16 once, to nearest even.
+ *   forward:  bit for bit bf16_rne(vfi_pwc_warp_forward(float(x), float(flow))).
+ *   backward: grad_x is WRITTEN in full, not added into (adding into bfloat16 would round twice): bf16_rne of what
+ *     vfi_pwc_warp_backward leaves in a zero-filled grad_x for the widened tensors, from the same fixed-point accumulator
+ *     (same scale, same addends, same integer sums, one conversion, one rounding).  grad_flow is WRITTEN: the float32
+ *     entry's ordered channel sum, rounded once where the flow is bfloat16.  Either gradient may be NULL (the other one is
+ *     bit-identical); both are bit-reproducible.  A call the accumulator sends to fp32 atomics (a NaN / Inf in grad_output,
+ *     or magnitudes that could overflow) adds in float32 library scratch and rounds once at the end -- NaN / Inf land in the
+ *     cells they poison in the float32 entry; no atomic touches bfloat16 storage.
+ * May allocate library scratch on its first call per stream (the backward). */
+int vfi_pwc_warp_forward_bf16(const void* x, const void* flow, int flow_is_bf16, void* output,
+                              int batch, int channel, int h, int w, int align_corners,
+                              vfi_strides sx, vfi_strides sf, vfi_strides so,
+                              vfi_stream_t stream);
+int vfi_pwc_warp_backward_bf16(const void* x, const void* flow, int flow_is_bf16, const void* grad_output,
+                               void* grad_x, void* grad_flow,
+                               int batch, int channel, int h, int w, int align_corners,
+                               vfi_strides sx, vfi_strides sf, vfi_strides sgo, vfi_strides sgx, vfi_strides sgf,
+                               vfi_stream_t stream);
 
 /* PWCDCNet's warp feeding its correlation layer (PWCNet/PWCNet.py:244-247, 266-267, 282-283, 299-300):
  * output[B,81,h,w] = correlation(input1, warp(input2, flow)) with pad 4, kernel 1, max displacement 4, strides 1 --

@@ -65,6 +65,8 @@ SIGNATURES = {
     "vfi_correlation_backward_f16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_forward_bf16": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "vfi_correlation_backward_bf16": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_lrelu_forward_bf16": [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_lrelu_backward_bf16": [_p, _p, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_forward": [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_forward_pair": [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_backward": [_p, _p, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
@@ -85,6 +87,8 @@ SIGNATURES = {
                                         _f, _f, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_forward": [_p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, Strides, _p],
+    "vfi_pwc_warp_forward_bf16": [_p, _p, _i, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
+    "vfi_pwc_warp_backward_bf16": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_correlation_forward": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, _p],
     "vfi_frame_u8_to_planar": [_p, _p, _i, _i, _i, _i, _i, _i, _i, Strides, _p],
     "vfi_planar_to_frame_u8": [_p, _p, _i, _i, _i, _i, _i, Strides, _p],
@@ -149,8 +153,8 @@ def _dev(t, dtype=torch.float32):
     return t.device
 
 
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(_dev(t)).cuda_stream)
+def _stream(t, dtype=torch.float32):
+    return ctypes.c_void_p(torch.cuda.current_stream(_dev(t, dtype)).cuda_stream)
 
 
 def _finish(err):
@@ -694,19 +698,30 @@ def _slope(negative_slope):
     return s
 
 
-def _lrelu_out(out, shape, like, what):
+def _lrelu_out(out, shape, like, what, dtype=torch.float32):
     if out is None:
-        return torch.empty(shape, device=like.device, dtype=torch.float32)
+        return torch.empty(shape, device=like.device, dtype=dtype)
     if tuple(out.shape) != tuple(shape):
         raise RuntimeError("%s: out= must have the output dimensions %s" % (what, tuple(shape)))
     if not _dense_planes(out):
         raise RuntimeError("%s: out= must have dense planes (a channel slice of a contiguous NCHW buffer)" % what)
-    _dev(out)
+    _dev(out, dtype)
     return out
+
+
+def _bf16_or_f32(first, *rest):
+    """The dtype a call with `_bf16` twins runs in -- bfloat16 when its first tensor is, float32 otherwise -- after checking
+    every tensor for it and for the device (float16 and a bfloat16 / float32 mix raise here, before any library call)."""
+    dtype = torch.bfloat16 if first.dtype == torch.bfloat16 else torch.float32
+    for t in (first, *rest):
+        _dev(t, dtype)
+    return dtype, ("_bf16" if dtype == torch.bfloat16 else "")
 
 
 def correlation_lrelu_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2, negative_slope, out=None):
     """leaky_relu(correlation_forward(input1, input2, ...), negative_slope) from the correlation's own launch, bit for bit.
+    float32, or bfloat16 (every tensor, out= included: vfi_correlation_lrelu_forward_bf16 -- torch's bfloat16 leaky_relu on the
+    bfloat16 cost volume, two roundings).
     out=: where to write it -- a tensor of the output's shape whose planes are dense, such as buf[:, k:k + 81] of a
     contiguous NCHW buffer; returned as it is."""
     slope = _slope(negative_slope)
@@ -714,15 +729,16 @@ def correlation_lrelu_forward(input1, input2, pad_size, kernel_size, max_displac
         raise RuntimeError("correlation_lrelu_forward: the two inputs must have one shape")
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
-    if out is not None:
-        _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward")
-    for t in (input1, input2):
-        _dev(t)
+    if out is not None:                                     # (its shape and layout first, then everybody's dtype and device)
+        _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward",
+                   torch.bfloat16 if input1.dtype == torch.bfloat16 else torch.float32)
+    dtype, suffix = _bf16_or_f32(input1, input2)
     input1, input2 = input1.contiguous(), input2.contiguous()
-    out = _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward")
+    out = _lrelu_out(out, (b, oc, oh, ow), input1, "correlation_lrelu_forward", dtype)
     with torch.cuda.device(input1.device):
-        err = lib().vfi_correlation_lrelu_forward(_ptr(input1), _ptr(input2), _ptr(out), _planes(out)[1], b, c, h, w, pad_size,
-                                                  kernel_size, max_displacement, stride1, stride2, slope, _stream(input1))
+        fn = getattr(lib(), "vfi_correlation_lrelu_forward" + suffix)
+        err = fn(_ptr(input1), _ptr(input2), _ptr(out), _planes(out)[1], b, c, h, w, pad_size,
+                 kernel_size, max_displacement, stride1, stride2, slope, _stream(input1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_lrelu_forward: the binding returned %d" % err)
     return out
@@ -760,21 +776,22 @@ def correlation_lrelu_backward(input1, input2, y, gradoutput, pad_size, kernel_s
                                negative_slope):
     """correlation_backward(input1, input2, where(y > 0, g, g * negative_slope), ...) from the correlation backward's own
     launches: y is the saved output of correlation_lrelu_forward.  y and gradoutput are read where they lie when their
-    planes are dense, whatever their batch stride (the narrow() view of torch.cat's backward); otherwise copied."""
+    planes are dense, whatever their batch stride (the narrow() view of torch.cat's backward); otherwise copied.  float32, or
+    bfloat16 for all four tensors (vfi_correlation_lrelu_backward_bf16: g * negative_slope is rounded to bfloat16, as a
+    materialised masked gradient would be)."""
     slope = _slope(negative_slope)
     b, c, h, w = input1.shape
     gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if input2.shape != input1.shape or tuple(gradoutput.shape) != gshape or tuple(y.shape) != gshape:
         raise RuntimeError("correlation_lrelu_backward: input2 / y / gradoutput do not match input1's shape and the output dimensions")
-    for t in (input1, input2, y, gradoutput):
-        _dev(t)
+    dtype, suffix = _bf16_or_f32(input1, input2, y, gradoutput)
     input1, input2 = input1.contiguous(), input2.contiguous()
     (y, ys), (gradoutput, gs) = _planes(y), _planes(gradoutput)
     g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
     with torch.cuda.device(input1.device):
-        err = lib().vfi_correlation_lrelu_backward(_ptr(input1), _ptr(input2), _ptr(y), ys, _ptr(gradoutput), gs, _ptr(g1), _ptr(g2),
-                                                   b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope,
-                                                   _stream(input1))
+        fn = getattr(lib(), "vfi_correlation_lrelu_backward" + suffix)
+        err = fn(_ptr(input1), _ptr(input2), _ptr(y), ys, _ptr(gradoutput), gs, _ptr(g1), _ptr(g2),
+                 b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope, _stream(input1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_lrelu_backward: the binding returned %d" % err)
     return g1, g2
@@ -983,34 +1000,54 @@ def filterinterp_blend_backward(ref0, ref2, flow0, flow2, filt0, filt2, grad_ble
             _st(grads[0]) if grads else _st(ref0), _stream(ref0)))
 
 
+def _warp_flow_dtype(x, flow):
+    """The flow's dtype in a warp call: float32 with a float32 x; float32 or bfloat16, independently, with a bfloat16 x."""
+    if x.dtype == torch.bfloat16 and flow.dtype == torch.bfloat16:
+        return torch.bfloat16
+    return torch.float32
+
+
 def pwc_warp_forward(x, flow, output, align_corners=True):
+    """float32, or bfloat16 x / output (vfi_pwc_warp_forward_bf16) with a float32 or a bfloat16 flow."""
     b, c, h, w = x.shape
     if not _nchw_ok(x, flow, output) or tuple(flow.shape) != (b, 2, h, w) or output.shape != x.shape:
         return 1
-    _dev(flow), _dev(output)
-    with torch.cuda.device(_dev(x)):
+    fdtype = _warp_flow_dtype(x, flow)
+    _dev(flow, fdtype)
+    dtype, suffix = _bf16_or_f32(x, output)
+    with torch.cuda.device(x.device):
+        if suffix:
+            return _finish(lib().vfi_pwc_warp_forward_bf16(_ptr(x), _ptr(flow), int(fdtype == torch.bfloat16), _ptr(output), b, c, h, w,
+                                                           int(bool(align_corners)), _st(x), _st(flow), _st(output),
+                                                           _stream(x, dtype)))
         return _finish(lib().vfi_pwc_warp_forward(_ptr(x), _ptr(flow), _ptr(output), b, c, h, w, int(bool(align_corners)),
                                                   _st(x), _st(flow), _st(output), _stream(x)))
 
 
 def pwc_warp_backward(x, flow, grad_output, grad_x=None, grad_flow=None, align_corners=True):
-    """grad_x (added into: zero-fill it) and / or grad_flow (written) of pwc_warp_forward; None = not computed."""
+    """grad_x and / or grad_flow (written) of pwc_warp_forward; None = not computed.  float32: grad_x is added into
+    (zero-fill it).  bfloat16 x / grad_output / grad_x (vfi_pwc_warp_backward_bf16): grad_x is WRITTEN in full; the flow is
+    float32 or bfloat16 and grad_flow has its dtype."""
     b, c, h, w = x.shape
     grads = [t for t in (grad_x, grad_flow) if t is not None]
     if not _nchw_ok(x, flow, grad_output, *grads) or tuple(flow.shape) != (b, 2, h, w) or grad_output.shape != x.shape:
         return 1
     if (grad_x is not None and grad_x.shape != x.shape) or (grad_flow is not None and grad_flow.shape != flow.shape):
         return 1
-    _dev(flow), _dev(grad_output)
-    for t in grads:
-        _dev(t)
+    fdtype = _warp_flow_dtype(x, flow)
+    _dev(flow, fdtype)
+    if grad_flow is not None:
+        _dev(grad_flow, fdtype)
+    dtype, suffix = _bf16_or_f32(x, grad_output, *([grad_x] if grad_x is not None else []))
     null = ctypes.c_void_p(0)
-    with torch.cuda.device(_dev(x)):
-        return _finish(lib().vfi_pwc_warp_backward(
-            _ptr(x), _ptr(flow), _ptr(grad_output), _ptr(grad_x) if grad_x is not None else null,
-            _ptr(grad_flow) if grad_flow is not None else null, b, c, h, w, int(bool(align_corners)), _st(x), _st(flow),
-            _st(grad_output), _st(grad_x) if grad_x is not None else _st(x),
-            _st(grad_flow) if grad_flow is not None else _st(flow), _stream(x)))
+    with torch.cuda.device(x.device):
+        tail = (_ptr(grad_output), _ptr(grad_x) if grad_x is not None else null,
+                _ptr(grad_flow) if grad_flow is not None else null, b, c, h, w, int(bool(align_corners)), _st(x), _st(flow),
+                _st(grad_output), _st(grad_x) if grad_x is not None else _st(x),
+                _st(grad_flow) if grad_flow is not None else _st(flow), _stream(x, dtype))
+        if suffix:
+            return _finish(lib().vfi_pwc_warp_backward_bf16(_ptr(x), _ptr(flow), int(fdtype == torch.bfloat16), *tail))
+        return _finish(lib().vfi_pwc_warp_backward(_ptr(x), _ptr(flow), *tail))
 
 
 def pwc_warp_correlation_forward(input1, input2, flow, align_corners=True):

@@ -9,25 +9,63 @@
 // a 16-pixel block of x1 needs 24 columns x2, and two 16x16x32 MFMAs per 32 channels form them (9 of 32 products wanted).
 // Forward, anything else, and small PWC-Net levels: one thread per output, the float32 generic kernel's arithmetic.
 // Backward: the float32 kernels' arithmetic (correlation.hip: corr_backward, corr_backward_k1) on widened values.
+//
+// The same with PWC-Net's LeakyReLU (vfi_correlation_lrelu_forward_bf16 / _backward_bf16): the kernels below take an epilogue
+// (forward: what is stored, and where an image begins) and a gradient mask (backward: what a gradOutput value becomes as it is
+// loaded); the plain entries instantiate them with the types that do nothing.
+#include "bf16.h"
 #include "correlation_dev.h"
 
+#include <cfloat>
 #include <climits>
 
 namespace vfi {
 
-typedef unsigned short bf16_t;                                  // the storage bits
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float bf16_widen(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
-// two floats to two bfloat16, round to nearest even, NaN stays NaN: one v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned bf16_pack_rne(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ bf16_t bf16_rne(float v) { return (bf16_t)(bf16_pack_rne(v, 0.0f) & 0xffffu); }
+// What a forward kernel stores for a mean v, and where image b of the output begins.  CorrBf16Plain: bf16_rne(v), dense images.
+// CorrBf16Lrelu: the bits of torch's bfloat16 leaky_relu on the STORED cost volume -- the mean is rounded to bfloat16 first; a
+// value that is not positive is then multiplied by the slope in float32 and rounded again (NaN stays NaN, -0 becomes
+// -0 * slope) -- into an output whose images lie `stride` elements apart, the 81 planes of an image contiguous.
+struct CorrBf16Plain {
+    __device__ __forceinline__ unsigned pack(float lo, float hi) const { return bf16_pack_rne(lo, hi); }
+    __device__ __forceinline__ int64_t image(int b, int64_t dense) const { return (int64_t)b * dense; }
+};
+struct CorrBf16Lrelu {
+    int64_t stride;
+    float slope;
+    __device__ __forceinline__ unsigned pack(float lo, float hi) const {
+        const unsigned m = bf16_pack_rne(lo, hi);
+        const float a = __uint_as_float(m << 16), b = __uint_as_float(m & 0xffff0000u);
+        return bf16_pack_rne(a > 0.0f ? a : a * slope, b > 0.0f ? b : b * slope);     // (a positive value: its own bits again)
+    }
+    __device__ __forceinline__ int64_t image(int b, int64_t) const { return (int64_t)b * stride; }
+};
+
+// What a backward kernel does with a gradOutput value g whose output position holds the saved ACTIVATED output yv, and where
+// the images of gradOutput and y begin.  CorrBf16Grad: nothing, dense.  CorrBf16GradLrelu: g' = yv > 0 ? g :
+// bf16_rne(float(g) * slope) -- torch's bfloat16 leaky_relu backward, a materialised bfloat16 g' -- with images gstride /
+// ystride elements apart (gradOutput: the narrow() view torch.cat's backward hands down).
+struct CorrBf16Grad {
+    static constexpr bool MASK = false;
+    __device__ __forceinline__ const bf16_t* y_image(int) const { return nullptr; }
+    __device__ __forceinline__ int64_t g_image(int n, int64_t dense) const { return (int64_t)n * dense; }
+    __device__ __forceinline__ float operator()(bf16_t g, bf16_t) const { return bf16_widen(g); }
+};
+struct CorrBf16GradLrelu {
+    static constexpr bool MASK = true;
+    const bf16_t* y;
+    int64_t ystride, gstride;
+    float slope;
+    __device__ __forceinline__ const bf16_t* y_image(int n) const { return y + (int64_t)n * ystride; }
+    __device__ __forceinline__ int64_t g_image(int n, int64_t) const { return (int64_t)n * gstride; }
+    __device__ __forceinline__ float operator()(bf16_t g, bf16_t yv) const {
+        const float gf = bf16_widen(g);
+        return bf16_widen(yv) > 0.0f ? gf : bf16_widen(bf16_rne(gf * slope));
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- forward, MFMA
 //
@@ -66,10 +104,10 @@ struct CorrMfmaTile {
     static __device__ __forceinline__ int unit(int p, int g) { return p * KG + (g ^ ((p >> 2) & (KG - 1))); }
 };
 
-template <class T>
+template <class T, class Epi>
 __device__ __forceinline__ void corr_mfma_bf16_body(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
-    int channel, int h, int w, int oh, int ow, int org, u32x4* lds) {
+    int channel, int h, int w, int oh, int ow, int org, u32x4* lds, const Epi& epi) {
     constexpr int D = T::D, TW = T::TW, TH = T::TH, MT = T::MT, NB = T::NB, BW = T::BW, LH = T::LH, KG = T::KG, NT = T::NT;
     constexpr unsigned OUTSIDE = 0x80000000u;
     const int lane = threadIdx.x, tj = __builtin_amdgcn_readfirstlane(threadIdx.y);
@@ -185,8 +223,9 @@ __device__ __forceinline__ void corr_mfma_bf16_body(
         const int oy = oy0 + r;
         if (oy >= oh || ox >= ow) continue;
         const f32x2 s = *reinterpret_cast<const f32x2*>(&t[u * T::TP + px]);
-        const unsigned two = bf16_pack_rne(s.x / nelems, s.y / nelems);
-        bf16_t* op = out + (((int64_t)b * (D * D) + tj * D + ti) * oh + oy) * ow + ox;
+        const unsigned two = epi.pack(s.x / nelems, s.y / nelems);
+        // (the alignment is tested per store: an image stride that is odd moves every other image onto a 2-byte boundary)
+        bf16_t* op = out + epi.image(b, (int64_t)(D * D) * oh * ow) + ((int64_t)(tj * D + ti) * oh + oy) * ow + ox;
         if (pair && (reinterpret_cast<uintptr_t>(op) & 3) == 0) {
             *reinterpret_cast<unsigned*>(op) = two;
         } else {
@@ -197,12 +236,12 @@ __device__ __forceinline__ void corr_mfma_bf16_body(
 }
 
 // (the body is a device function: the matrix-core builtin must not be instantiated by the host pass)
-template <class T>
+template <class T, class Epi>
 __global__ __launch_bounds__(T::NT) void corr_forward_k1_mfma_bf16(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
-    int channel, int h, int w, int oh, int ow, int org) {
+    int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     __shared__ __attribute__((aligned(16))) u32x4 lds[T::LDS_BYTES / 16];
-    corr_mfma_bf16_body<T>(in1, in2, out, channel, h, w, oh, ow, org, lds);
+    corr_mfma_bf16_body<T>(in1, in2, out, channel, h, w, oh, ow, org, lds, epi);
 }
 typedef CorrMfmaTile<4, 2> CorrMfma;
 
@@ -215,9 +254,10 @@ typedef CorrMfmaTile<4, 2> CorrMfma;
 // is skipped.  With one tap inside, the lane runs the same loop: its outside tap is read at the inside tap's pixel (a valid
 // address) and cleared by `keep`; eight channels of loads in flight (corr_forward_k1_flat's way, which this kernel stands
 // in for at the small PWC-Net levels).
+template <class Epi>
 __global__ __launch_bounds__(256) void corr_forward_generic_bf16(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
-    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1, int s2, int dr) {
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1, int s2, int dr, Epi epi) {
     const int64_t total = (int64_t)batch * oc * oh * ow;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
@@ -253,7 +293,8 @@ __global__ __launch_bounds__(256) void corr_forward_generic_bf16(
             for (; c < channel; ++c) acc = fmaf(bf16_widen(pa[(int64_t)c * plane]), bf16_widen(pb[(int64_t)c * plane] & keep), acc);
         }
     const int k = 2 * kr + 1;
-    out[gid] = bf16_rne(acc / (float)(k * k * channel));
+    const int64_t image = (int64_t)oc * oh * ow;
+    out[epi.image(b, image) + (gid - (int64_t)b * image)] = (bf16_t)(epi.pack(acc / (float)(k * k * channel), 0.0f) & 0xffffu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward
@@ -261,10 +302,10 @@ __global__ __launch_bounds__(256) void corr_forward_generic_bf16(
 // corr_backward (correlation.hip) on bfloat16 storage: one thread per gradient element, float32 terms s = fmaf(g, v, s) in 32
 // partials over tc = l, l + 32, ..., the partials added in sequence, r / (float)(k*k*C), rounded to bfloat16 once.  A term
 // whose other-map tap lies in the zero padding is not skipped (g * 0: NaN for an infinite g).
-template <bool SECOND>
+template <bool SECOND, class Act>
 __global__ __launch_bounds__(256) void corr_backward_bf16(
     const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
-    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr) {
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr, Act act) {
     const int64_t total = (int64_t)batch * channel * h * w;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
@@ -275,7 +316,8 @@ __global__ __launch_bounds__(256) void corr_backward_bf16(
     const int dsz = 2 * dr + 1;
     const int y = by + pad, x = bx + pad;                   // padded coordinates
     const bf16_t* of = other + ((int64_t)n * channel + c) * h * w;
-    const bf16_t* go = gout + (int64_t)n * oc * oh * ow;
+    const bf16_t* go = gout + act.g_image(n, (int64_t)oc * oh * ow);
+    const bf16_t* yo = act.y_image(n);
     const float nelems = (float)((2 * kr + 1) * (2 * kr + 1) * channel);
     bool any = SECOND;
     if constexpr (!SECOND) {
@@ -306,7 +348,11 @@ __global__ __launch_bounds__(256) void corr_backward_bf16(
             ymin = max(0, ymin); ymax = min(oh - 1, ymax);
             const bf16_t* g = go + (int64_t)tc * oh * ow;
             for (int j = ymin; j <= ymax; ++j)
-                for (int i = xmin; i <= xmax; ++i) s = fmaf(bf16_widen(g[(int64_t)j * ow + i]), val, s);
+                for (int i = xmin; i <= xmax; ++i) {
+                    const int64_t at = (int64_t)j * ow + i;
+                    const bf16_t yv = Act::MASK ? yo[(int64_t)tc * oh * ow + at] : (bf16_t)0;
+                    s = fmaf(act(g[at], yv), val, s);
+                }
         }
         r += s;
     }
@@ -318,10 +364,10 @@ __global__ __launch_bounds__(256) void corr_backward_bf16(
 // the workgroup stages the other map's 12x72 window, widened, in LDS (double-buffered, zero padded).  The same float32
 // terms in the same order as corr_backward_bf16, so the same bits.  (A term the reference skips -- gradInput2, displaced
 // position outside the frame -- has g = 0 and meets the window's zero padding: fma(0, 0, s) = s.)
-template <bool SECOND>
+template <bool SECOND, class Act>
 __global__ __launch_bounds__(256) void corr_backward_k1_bf16(
     const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
-    int channel, int h, int w, int groups, int ch_per_group) {
+    int channel, int h, int w, int groups, int ch_per_group, Act act) {
     typedef CorrBwdTile T;
     constexpr int MD = T::MD, D = T::D, OC = T::OC;
     __shared__ float win[2][T::LH][T::LW];
@@ -331,13 +377,24 @@ __global__ __launch_bounds__(256) void corr_backward_k1_bf16(
     const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
     const bool in = bx < w && by < h;
     const int64_t plane = (int64_t)h * w;
-    const bf16_t* go = gout + (int64_t)n * OC * plane;
+    const bf16_t* go = gout + act.g_image(n, OC * plane);
+    const bf16_t* yo = act.y_image(n);
 
     float g[OC];
 #pragma unroll
     for (int tc = 0; tc < OC; ++tc) {
         const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
-        g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? bf16_widen(go[(int64_t)tc * plane + (int64_t)gy * w + gx]) : 0.0f;
+        if constexpr (Act::MASK) {
+            // (a skipped term loads element 0 of its image -- a valid address -- and drops it, so that the loads of a
+            //  displacement row of gradOutput and y go out together: corr_backward_k1_body, correlation.hip)
+            const bool ok = in && gy >= 0 && gy < h && gx >= 0 && gx < w;
+            const int64_t at = ok ? (int64_t)tc * plane + (int64_t)gy * w + gx : 0;
+            const bf16_t gv = go[at], yv = yo[at];
+            g[tc] = ok ? act(gv, yv) : 0.0f;
+            if (tc % D == D - 1) __builtin_amdgcn_sched_barrier(0);
+        } else {
+            g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? bf16_widen(go[(int64_t)tc * plane + (int64_t)gy * w + gx]) : 0.0f;
+        }
     }
 
     auto stage = [&](int c, int buf) {
@@ -393,42 +450,67 @@ static bool corr_bf16_mfma_fits(int batch, int h, int w, int oh) {
     return (int64_t)h * w * 2 * CorrMfma::KC < INT_MAX && batch <= 65535 && (oh + CorrMfma::TH - 1) / CorrMfma::TH <= 65535;
 }
 
-template <class T>
+template <class T, class Epi = CorrBf16Plain>
 static int corr_bf16_launch_mfma(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oh,
-                                 int ow, int org, hipStream_t st) {
+                                 int ow, int org, hipStream_t st, const Epi& epi = Epi{}) {
     const dim3 grid((ow + T::TW - 1) / T::TW, (oh + T::TH - 1) / T::TH, batch);
-    hipLaunchKernelGGL(corr_forward_k1_mfma_bf16<T>, grid, dim3(64, T::D, 1), 0, st, (const bf16_t*)input1, (const bf16_t*)input2,
-                       (bf16_t*)output, channel, h, w, oh, ow, org);
+    hipLaunchKernelGGL((corr_forward_k1_mfma_bf16<T, Epi>), grid, dim3(64, T::D, 1), 0, st, (const bf16_t*)input1, (const bf16_t*)input2,
+                       (bf16_t*)output, channel, h, w, oh, ow, org, epi);
     return launch_status();
 }
 
+template <class Epi = CorrBf16Plain>
 static int corr_bf16_launch_generic(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oc,
                                     int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
-                                    hipStream_t st) {
+                                    hipStream_t st, const Epi& epi = Epi{}) {
     const int64_t total = (int64_t)batch * oc * oh * ow;
     if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipLaunchKernelGGL(corr_forward_generic_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)input1,
+    hipLaunchKernelGGL(corr_forward_generic_bf16<Epi>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)input1,
                        (const bf16_t*)input2, (bf16_t*)output, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2,
-                       max_displacement, stride1, stride2, max_displacement / stride2);
+                       max_displacement, stride1, stride2, max_displacement / stride2, epi);
     return launch_status();
+}
+
+// the forward of both entries: the checks, the kernel choice, one launch
+template <class Epi>
+static int corr_bf16_forward(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int pad_size,
+                             int kernel_size, int max_displacement, int stride1, int stride2, vfi_stream_t stream, const Epi& epi,
+                             int64_t image_stride) {
+    int oc, oh, ow;
+    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
+                   &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (image_stride < (int64_t)oc * oh * ow) return VFI_ERR_SHAPE;     // (the plain entry passes its dense stride)
+    if (corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) && corr_bf16_mfma_fits(batch, h, w, oh)) {
+        const int64_t mfma_tiles = (int64_t)((ow + CorrMfma::TW - 1) / CorrMfma::TW) * ((oh + CorrMfma::TH - 1) / CorrMfma::TH) * batch;
+        if (mfma_tiles >= corr_bf16_mfma_threshold) {
+            return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size,
+                                                   (hipStream_t)stream, epi);
+        }
+    }
+    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
+                                    stride1, stride2, (hipStream_t)stream, epi);
 }
 
 extern "C" int vfi_correlation_forward_bf16(const void* input1, const void* input2, void* output, int batch, int channel,
                                              int h, int w, int pad_size, int kernel_size, int max_displacement,
                                              int stride1, int stride2, vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
-                   &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) && corr_bf16_mfma_fits(batch, h, w, oh)) {
-        const int64_t mfma_tiles = (int64_t)((ow + CorrMfma::TW - 1) / CorrMfma::TW) * ((oh + CorrMfma::TH - 1) / CorrMfma::TH) * batch;
-        if (mfma_tiles >= corr_bf16_mfma_threshold) {
-            return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size,
-                                         (hipStream_t)stream);
-        }
-    }
-    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
-                                    stride1, stride2, (hipStream_t)stream);
+    return corr_bf16_forward(input1, input2, output, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
+                             stream, CorrBf16Plain{}, INT64_MAX);
+}
+
+// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
+static bool corr_bf16_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
+
+// vfi_correlation_forward_bf16 with PWC-Net's LeakyReLU applied to every stored value, into an output whose images lie
+// output_batch_stride elements apart: the same kernels and the same choice, with the epilogue compiled in.
+extern "C" int vfi_correlation_lrelu_forward_bf16(const void* input1, const void* input2, void* output, int64_t output_batch_stride,
+                                                   int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                                                   int max_displacement, int stride1, int stride2, float negative_slope,
+                                                   vfi_stream_t stream) {
+    if (!corr_bf16_slope_ok(negative_slope)) return VFI_ERR_SHAPE;
+    return corr_bf16_forward(input1, input2, output, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
+                             stream, CorrBf16Lrelu{output_batch_stride, negative_slope}, output_batch_stride);
 }
 
 // One kernel of vfi_correlation_forward_bf16 whatever the tile count (internal: the tests and tools/bench_corr_bf16.py run
@@ -450,38 +532,62 @@ extern "C" int vfi_correlation_forward_bf16_kernel(int which, const void* input1
 }
 
 // one gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1
+template <class Act>
 static int corr_bf16_backward_one(bool second, const bf16_t* other, const bf16_t* gout, bf16_t* gin, int batch, int channel, int h, int w,
-                                  int oc, int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st) {
+                                  int oc, int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st,
+                                  const Act& act) {
     if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
         int ch_per_group;
         const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
         if (groups) {
             const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            hipLaunchKernelGGL(second ? corr_backward_k1_bf16<true> : corr_backward_k1_bf16<false>, grid, dim3(256), 0, st, other, gout,
-                               gin, channel, h, w, groups, ch_per_group);
+            hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, Act> : corr_backward_k1_bf16<false, Act>), grid, dim3(256), 0, st, other,
+                               gout, gin, channel, h, w, groups, ch_per_group, act);
             return launch_status();
         }
     }
     const int64_t total = (int64_t)batch * channel * h * w;
     if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipLaunchKernelGGL(second ? corr_backward_bf16<true> : corr_backward_bf16<false>, dim3((unsigned)((total + 255) / 256)), dim3(256),
-                       0, st, other, gout, gin, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2, max_displacement,
-                       stride2, max_displacement / stride2);
+    hipLaunchKernelGGL((second ? corr_backward_bf16<true, Act> : corr_backward_bf16<false, Act>), dim3((unsigned)((total + 255) / 256)),
+                       dim3(256), 0, st, other, gout, gin, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2,
+                       max_displacement, stride2, max_displacement / stride2, act);
     return launch_status();
+}
+
+// both gradients of both entries: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
+template <class Act>
+static int corr_bf16_backward(const void* input1, const void* input2, const void* gradoutput, void* gradinput1, void* gradinput2,
+                              int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
+                              int stride2, vfi_stream_t stream, const Act& act, int64_t ystride, int64_t gstride) {
+    int oc, oh, ow;
+    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
+                   stride1, stride2, true, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (ystride < (int64_t)oc * oh * ow || gstride < (int64_t)oc * oh * ow) return VFI_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int err = corr_bf16_backward_one(false, (const bf16_t*)input2, (const bf16_t*)gradoutput, (bf16_t*)gradinput1, batch, channel, h, w,
+                                           oc, oh, ow, pad_size, kernel_size, max_displacement, stride2, st, act);
+    if (err != VFI_OK) return err;
+    return corr_bf16_backward_one(true, (const bf16_t*)input1, (const bf16_t*)gradoutput, (bf16_t*)gradinput2, batch, channel, h, w, oc,
+                                  oh, ow, pad_size, kernel_size, max_displacement, stride2, st, act);
 }
 
 extern "C" int vfi_correlation_backward_bf16(const void* input1, const void* input2, const void* gradoutput,
                                               void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
                                               int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                               vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                   stride1, stride2, true, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int err = corr_bf16_backward_one(false, (const bf16_t*)input2, (const bf16_t*)gradoutput, (bf16_t*)gradinput1, batch, channel, h, w,
-                                           oc, oh, ow, pad_size, kernel_size, max_displacement, stride2, st);
-    if (err != VFI_OK) return err;
-    return corr_bf16_backward_one(true, (const bf16_t*)input1, (const bf16_t*)gradoutput, (bf16_t*)gradinput2, batch, channel, h, w, oc,
-                                  oh, ow, pad_size, kernel_size, max_displacement, stride2, st);
+    return corr_bf16_backward(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                              max_displacement, stride1, stride2, stream, CorrBf16Grad{}, INT64_MAX, INT64_MAX);
+}
+
+// vfi_correlation_backward_bf16 of gradOutput masked by LeakyReLU's derivative: the same two launches of the masked kernels.
+extern "C" int vfi_correlation_lrelu_backward_bf16(const void* input1, const void* input2, const void* y, int64_t y_batch_stride,
+                                                    const void* gradoutput, int64_t gradoutput_batch_stride, void* gradinput1,
+                                                    void* gradinput2, int batch, int channel, int h, int w, int pad_size,
+                                                    int kernel_size, int max_displacement, int stride1, int stride2,
+                                                    float negative_slope, vfi_stream_t stream) {
+    if (!y || !corr_bf16_slope_ok(negative_slope)) return VFI_ERR_SHAPE;
+    const CorrBf16GradLrelu act = {(const bf16_t*)y, y_batch_stride, gradoutput_batch_stride, negative_slope};
+    return corr_bf16_backward(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                              max_displacement, stride1, stride2, stream, act, y_batch_stride, gradoutput_batch_stride);
 }

@@ -1,5 +1,6 @@
 // gradacc.h -- the deterministic fixed-point accumulator every image gradient of the library goes through (gradacc.hip).
 #pragma once
+#include "bf16.h"
 #include "vfi_common.h"
 
 namespace vfi {
@@ -90,6 +91,18 @@ struct GradPlain {
     __device__ __forceinline__ const float* row(int64_t o) const { return g + o; }
 };
 
+// a plain gradient in bfloat16 storage: its elements widened (exactly) as they are read, so the max-scan sees the values the
+// float32 entry sees for the widened tensor, and the scale is the same
+struct GradBf16 {
+    const bf16_t* __restrict__ g;
+    struct Row {
+        const bf16_t* g;
+        __device__ __forceinline__ float operator[](int64_t o) const { return bf16_widen(g[o]); }
+    };
+    __host__ __device__ bool any() const { return true; }
+    __device__ __forceinline__ Row row(int64_t o) const { return Row{g + o}; }
+};
+
 // The WS_GRADACC scratch of a call: [ndirs headers of 256 B][ndirs x cells 64-bit sums][nflags 32-bit words], ndirs 0, 1 or 2
 // (one header and one plane of sums per gradient the call accumulates; the flag words are the caller's kernels'): offsets
 // from gradacc_layout alone.
@@ -123,5 +136,16 @@ int gradacc_zero_fp32(hipStream_t st, const int* hdr, float* g1, int batch, int 
 // the sums to float, added into g1; overwrite: WRITTEN to every cell of g1 (0 where the sum is 0) instead
 int gradacc_finish(hipStream_t st, const GradAccDir& d, float* g1, int batch, int channel, int h, int w, vfi_strides s1,
                    bool overwrite = false);
+
+
+// bfloat16 gradients (vfi_pwc_warp_backward_bf16).  gradacc_begin_bf16: gradacc_begin for a bfloat16 gradoutput, no weights.
+// A call that gradacc_fp32 sends to fp32 atomics never adds into bfloat16 storage: its kernel adds FLOATS into the low
+// words of the zeroed 64-bit cells (gradacc_add with the scratch plane as the float plane, float index 2 x cell index).
+// gradacc_finish_bf16 WRITES every cell of the bfloat16 gradient g1 -- bf16_rne of the float the float32 finish would leave
+// in a zero-filled gradient (the converted integer sum, +0 where it is 0), or of the cell's float on the fp32 path: one
+// rounding either way.
+int gradacc_begin_bf16(hipStream_t st, const bf16_t* gout, int batch, int channel, int h, int w, vfi_strides sg, int taps,
+                       GradAccScratch* s);
+int gradacc_finish_bf16(hipStream_t st, const GradAccDir& d, bf16_t* g1, int batch, int channel, int h, int w, vfi_strides s1);
 
 }  // namespace vfi

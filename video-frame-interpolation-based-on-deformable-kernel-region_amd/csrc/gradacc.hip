@@ -62,6 +62,31 @@ __global__ __launch_bounds__(256) void gradacc_convert(const unsigned long long*
     }
 }
 
+// The sums of a bfloat16 gradient (gradacc.h): every cell of g1 written; a lane owns two adjacent cells (one 16-byte load of
+// the sums, one 4-byte store where the pair is 4-byte aligned and inside the row).
+__global__ __launch_bounds__(256) void gradacc_convert_bf16(const unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
+                                                            bf16_t* __restrict__ g1, int channel, int h, int w, vfi_strides s1, int64_t n) {
+    const bool fp32 = gradacc_fp32(hdr);
+    const int k = gradacc_exponent(hdr);
+    const int rows = (int)(n / w);
+    auto value = [&](unsigned long long cell) {
+        if (fp32) return __uint_as_float((unsigned)cell);                   // (the float the atomics left in the low word)
+        const long long sum = (long long)cell;
+        return sum != 0 ? (float)ldexp((double)sum, -k) : 0.0f;
+    };
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int y = row % h, bc = row / h;
+        const int c = bc % channel, b = bc / channel;
+        const unsigned long long* a = acc + (int64_t)row * w;
+        bf16_t* cells = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c + (int64_t)y * s1.h;
+        for (int x = 2 * threadIdx.x; x < w; x += 512) {
+            const bool pair = x + 1 < w;
+            const float lo = value(a[x]), hi = pair ? value(a[x + 1]) : 0.0f;
+            bf16_store_pair(cells + x, bf16_pack_rne(lo, hi), pair);
+        }
+    }
+}
+
 // before an fp32 scatter into a gradient the caller has not zeroed: zero it (nothing to do on the integer path)
 __global__ __launch_bounds__(256) void gradacc_zero_fp32_k(const int* __restrict__ hdr, float* __restrict__ g1, int channel, int h,
                                                            int w, vfi_strides s1, int64_t n) {
@@ -110,6 +135,7 @@ int gradacc_scan(hipStream_t st, G g, int batch, int channel, int h, int w, vfi_
     return launch_status();
 }
 template int gradacc_scan<GradPlain>(hipStream_t, GradPlain, int, int, int, int, vfi_strides, const float*, int, vfi_strides, int*);
+template int gradacc_scan<GradBf16>(hipStream_t, GradBf16, int, int, int, int, vfi_strides, const float*, int, vfi_strides, int*);
 template int gradacc_scan<GradTerms>(hipStream_t, GradTerms, int, int, int, int, vfi_strides, const float*, int, vfi_strides, int*);
 
 int gradacc_begin(hipStream_t st, const float* gout, int batch, int channel, int h, int w, vfi_strides sg,
@@ -117,6 +143,19 @@ int gradacc_begin(hipStream_t st, const float* gout, int batch, int channel, int
     const int err = gradacc_reserve(st, 1, (int64_t)batch * channel * h * w, nflags, s);
     if (err != VFI_OK) return err;
     return gradacc_scan(st, GradPlain{gout}, batch, channel, h, w, sg, weights, wchannel, sw, s->dir[0].hdr);
+}
+
+int gradacc_begin_bf16(hipStream_t st, const bf16_t* gout, int batch, int channel, int h, int w, vfi_strides sg, int taps,
+                       GradAccScratch* s) {
+    const int err = gradacc_reserve(st, 1, (int64_t)batch * channel * h * w, 0, s);
+    if (err != VFI_OK) return err;
+    return gradacc_scan(st, GradBf16{gout}, batch, channel, h, w, sg, nullptr, taps, sg, s->dir[0].hdr);
+}
+
+int gradacc_finish_bf16(hipStream_t st, const GradAccDir& d, bf16_t* g1, int batch, int channel, int h, int w, vfi_strides s1) {
+    const int64_t n = (int64_t)batch * channel * h * w;
+    hipLaunchKernelGGL(gradacc_convert_bf16, row_blocks(n / w, 8192), dim3(256), 0, st, d.acc, d.hdr, g1, channel, h, w, s1, n);
+    return launch_status();
 }
 
 int gradacc_zero_fp32(hipStream_t st, const int* hdr, float* g1, int batch, int channel, int h, int w, vfi_strides s1) {

@@ -550,7 +550,8 @@ def rectify_inputs(ref0, ref2, offsets, filter, filter_size2, time_offsets, ctx0
 
 
 class _Warp(torch.autograd.Function):
-    """`PWCDCNet.warp` with the gradients torch autograd gives for the reference's formula (vfi_pwc_warp_backward)."""
+    """`PWCDCNet.warp` with the gradients torch autograd gives for the reference's formula (vfi_pwc_warp_backward; for a
+    bfloat16 x vfi_pwc_warp_backward_bf16, whose grad_x is bfloat16 and whose grad_flow has the flow's dtype)."""
 
     @staticmethod
     def forward(ctx, x, flo, align_corners):
@@ -566,7 +567,10 @@ class _Warp(torch.autograd.Function):
         x, flo = ctx.saved_tensors
         if grad_out.stride(3) != 1:                         # (e.g. the expanded gradient of a sum())
             grad_out = grad_out.contiguous()
-        gx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None          # (added into)
+        if not ctx.needs_input_grad[0]:
+            gx = None
+        else:                                               # (float32: added into; bfloat16: written in full)
+            gx = torch.empty_like(x) if x.dtype == torch.bfloat16 else torch.zeros_like(x)
         gf = torch.empty_like(flo) if ctx.needs_input_grad[1] else None        # (written)
         if gx is not None or gf is not None:
             _check(cabi.pwc_warp_backward(x, flo, grad_out, gx, gf, ctx.align_corners), "pwc_warp_backward")
@@ -594,15 +598,31 @@ def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
-def warp(x, flo, align_corners=True):
-    """`PWCDCNet.warp`.  Differentiable when grad mode is on and x or flo requires grad; otherwise the plain forward
-    launch (no grad_fn).  float32 only (anything else raises): torch's own grid_sample runs in float32 under autocast too,
-    so in a bfloat16 network cast the result back for the correlation, `warp(c2.float(), flo).to(c1.dtype)`."""
+def _float32_only(what, hint, *tensors):
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: tensors must be float32 (%s)" % (what, hint))
+
+
+def _warp(x, flo, align_corners):
+    """`warp` for the dtypes the library warps: float32, or a bfloat16 x -- the dtype of a network under
+    torch.autocast(dtype=torch.bfloat16) -- with a float32 or a bfloat16 flow.  On bfloat16 the result is bit for bit
+    `warp(x.float(), flo.float()).to(x.dtype)` from one launch and without a cast; the gradients are that composition's too,
+    each rounded once (grad_x bfloat16, grad_flow in the flow's dtype).  float16 raises."""
     if _wants_grad(x, flo):
         return _Warp.apply(x, flo, bool(align_corners))
     out = torch.empty_like(x)
     _check(cabi.pwc_warp_forward(x, flo, out, align_corners), "pwc_warp_forward")
     return out
+
+
+def warp(x, flo, align_corners=True):
+    """`PWCDCNet.warp`.  Differentiable when grad mode is on and x or flo requires grad; otherwise the plain forward
+    launch (no grad_fn).  float32 only (anything else raises), as it has always been: a bfloat16 network warps inside
+    `warp_corr` / `warp_corr_lrelu`, which take bfloat16 features and run the warp on bfloat16 storage without a cast; the
+    warp alone on bfloat16 is `_Warp.apply(x, flo, align_corners)` (trainable) or `cabi.pwc_warp_forward`."""
+    _float32_only("warp", "warp_corr, warp_corr_lrelu and _Warp.apply take bfloat16", x, flo)
+    return _warp(x, flo, align_corners)
 
 
 def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
@@ -612,13 +632,14 @@ def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
     MI355X at PWC-Net's sizes (0.33 vs 0.15 ms for the five levels of a 1080p pair): every tile re-forms the bilinear
     samples of its 4-pixel halo (3.75 x the taps), which costs more than the 2 x 18 MB round trip it saves.
     Differentiable when grad mode is on and an input requires grad: then the two-launch path (one_launch is ignored;
-    same bits), whose warped tensor the correlation backward needs.  float32 only, because `warp` is; the correlation half
-    alone takes bfloat16 and float16 (`_Corr.apply(c1, warp(c2.float(), flo).to(c1.dtype))`)."""
+    same bits), whose warped tensor the correlation backward needs.  float32, or bfloat16 features (with a float32 or a
+    bfloat16 flow): two launches on bfloat16 storage, no cast; one_launch is ignored there too (the one-launch kernel is
+    float32 only).  float16 raises."""
     if _wants_grad(c1, c2, flo):
-        return _Corr.apply(c1, warp(c2, flo, align_corners))
-    if one_launch:
+        return _Corr.apply(c1, _warp(c2, flo, align_corners))
+    if one_launch and c1.dtype != torch.bfloat16:
         return cabi.pwc_warp_correlation_forward(c1, c2, flo, align_corners)
-    return cabi.correlation_forward(c1, warp(c2, flo, align_corners), 4, 1, 4, 1, 1)
+    return cabi.correlation_forward(c1, _warp(c2, flo, align_corners), 4, 1, 4, 1, 1)
 
 
 class _CorrPair(torch.autograd.Function):
@@ -652,7 +673,8 @@ def corr_pair(c1_a, c2_a, c1_b, c2_b):
 
 
 class _CorrLrelu(torch.autograd.Function):
-    """`_Corr` with PWC-Net's LeakyReLU in the correlation's own launch.  The saved tensor is the activated output y; the
+    """`_Corr` with PWC-Net's LeakyReLU in the correlation's own launch (float32 or bfloat16: `cabi.correlation_lrelu_forward` /
+    `_backward` dispatch on the dtype).  The saved tensor is the activated output y; the
     backward is one vfi_correlation_lrelu_backward call that masks the gradient as it loads it and reads a strided
     gradient (the narrow() view of torch.cat's backward) where it lies."""
 
@@ -702,8 +724,11 @@ def corr_lrelu(c1, c2, negative_slope=0.1, out=None):
     the bits of F.leaky_relu on the correlation's output.  Differentiable when grad mode is on and an input requires grad
     (one backward call, which masks the gradient as it loads it and takes torch.cat's strided gradient without a copy).
     Otherwise the plain launch, and out= may name where to write: buf[:, k:k + 81] of the contiguous NCHW buffer the
-    reference would get from `torch.cat((corr, ...), 1)`.  float32 only, as `warp_corr_lrelu` and `corr_pair_lrelu` are:
-    bfloat16 and float16 tensors raise (use `_Corr` / `Correlation` and torch's leaky_relu)."""
+    reference would get from `torch.cat((corr, ...), 1)`.  float32 only, as `corr_pair_lrelu` is: bfloat16 and float16 tensors
+    raise, as they always have.  On bfloat16 use `warp_corr_lrelu` (the warped levels), and for a level without a warp
+    `_CorrLrelu.apply(c1, c2, slope)` (trainable) or `cabi.correlation_lrelu_forward(..., out=)`: the bits of F.leaky_relu on
+    the bfloat16 cost volume -- the mean rounded first, the activation rounded again."""
+    _float32_only("corr_lrelu", "warp_corr_lrelu and _CorrLrelu.apply take bfloat16", c1, c2)
     if _wants_grad(c1, c2):
         _no_out_in_grad_mode(out, "corr_lrelu")
         return _CorrLrelu.apply(c1, c2, float(negative_slope))
@@ -711,12 +736,16 @@ def corr_lrelu(c1, c2, negative_slope=0.1, out=None):
 
 
 def warp_corr_lrelu(c1, c2, flo, align_corners=True, negative_slope=0.1, out=None):
-    """`self.leakyRELU(self.corr(c1, self.warp(c2, flo)))` (PWCNet/PWCNet.py:244-248 ...): `warp`, then `corr_lrelu`.
-    Differentiable as `warp_corr` is; in inference out= as `corr_lrelu`'s."""
+    """`self.leakyRELU(self.corr(c1, self.warp(c2, flo)))` (PWCNet/PWCNet.py:244-248 ...): the warp, then the correlation
+    with the LeakyReLU in its launch.  Differentiable as `warp_corr` is; in inference out= as `corr_lrelu`'s.  float32, or
+    bfloat16 features (out= included) with a float32 or a bfloat16 flow: a PWC-Net level under
+    torch.autocast(dtype=torch.bfloat16) is these two launches, with no cast and, with out=, no copy into the
+    concatenation; the bits are those of F.leaky_relu on the bfloat16 cost volume, and the backward's those of autograd
+    through it.  float16 raises."""
     if _wants_grad(c1, c2, flo):
         _no_out_in_grad_mode(out, "warp_corr_lrelu")
-        return _CorrLrelu.apply(c1, warp(c2, flo, align_corners), float(negative_slope))
-    return cabi.correlation_lrelu_forward(c1, warp(c2, flo, align_corners), 4, 1, 4, 1, 1, negative_slope, out=out)
+        return _CorrLrelu.apply(c1, _warp(c2, flo, align_corners), float(negative_slope))
+    return cabi.correlation_lrelu_forward(c1, _warp(c2, flo, align_corners), 4, 1, 4, 1, 1, negative_slope, out=out)
 
 
 def corr_pair_lrelu(c1_a, c2_a, c1_b, c2_b, negative_slope=0.1, out=None):
