@@ -122,6 +122,35 @@ int vfi_filterinterp_forward_ori_f16(const void* input1_half, const float* input
                                      vfi_strides s1, vfi_strides s2, vfi_strides s3,
                                      vfi_stream_t stream);
 
+/* bfloat16 STORAGE of the image and the outputs, float32 arithmetic: vfi_filterinterp_forward_ori_multi_to for a network
+ * that runs under bfloat16 autocast (the context warp, C = 196).  input1 and outputs[t] are bfloat16 tensors (strides in
+ * bfloat16 elements), flows and filter stay float32 (2 and 16 channels against 196).  The 16-bit patterns are widened
+ * exactly, the arithmetic is the float32 kernels' -- four quadrant chains and the blend, clamped taps read as replicated
+ * values; nothing is folded as in the fp16 entry above -- and each result is rounded once, to nearest even: every output
+ * element is, bit for bit, bf16_rne of what vfi_filterinterp_forward_ori writes for the widened image.  NaN stays NaN at the
+ * same positions; an invalid pixel copies the input's bits through.
+ * Contract of s_out as above: w stride 1, s_out.h == s1.h (else VFI_ERR_SHAPE), s_out.b and s_out.c free; every store is
+ * one 2-byte element, so outputs[t] needs 2-byte alignment only.  filter_channels == 16 with even s1.h, s1.c, s1.b and a
+ * 4-byte aligned input1 takes the LDS-staged kernel; everything else (any filter size, any strides, 2-byte alignment) the
+ * one-thread-per-pixel kernel, with the same bits.  One launch per flow (no shared-window kernel).  batch <= 65535. */
+int vfi_filterinterp_forward_ori_multi_to_bf16(const void* input1_bf16, const float* const* flows, const float* input3,
+                                               void* const* outputs_bf16, int nflows,
+                                               int batch, int channel, int h, int w, int filter_channels,
+                                               vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides s_out,
+                                               vfi_stream_t stream);
+
+/* vfi_filterinterp_backward_ori_image_multi on bfloat16 gradients: gradoutputs[t] (strides sg) and gradinput1 (strides s1)
+ * are bfloat16 tensors, flows and filter float32.  gradinput1 is, bit for bit, bf16_rne of what the float32 entry writes
+ * for the widened gradients: the same kernels on widened gradient rows, one fixed-point accumulation over all flows at the
+ * float32 call's scale, every element WRITTEN, reproducible bit for bit.  A call with a non-finite gradient or filter, or
+ * magnitudes whose product can overflow, scatters FLOATS with fp32 atomics into the zeroed scratch cells and rounds each
+ * once at the end: no atomic touches bfloat16 storage.  Scratch: 8 bytes per element of gradinput1. */
+int vfi_filterinterp_backward_ori_image_multi_bf16(const float* const* flows, const float* input3,
+                                                   const void* const* gradoutputs_bf16, void* gradinput1_bf16, int nflows,
+                                                   int batch, int channel, int h, int w, int filter_channels,
+                                                   vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
+                                                   vfi_stream_t stream);
+
 /* deformable-kernel variants (filterinterpolation_cuda.cc:11-92, 191-272, 374-447).
  * variant: 0 = FilterInterpolationLayer_gpu_forward (4 inputs, fs in {4,6}),
  *          1 = ..._forward_deforconv, 2 = ..._forward_nofilterwithdeforconv

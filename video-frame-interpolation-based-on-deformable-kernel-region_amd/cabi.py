@@ -34,6 +34,9 @@ SIGNATURES = {
     "vfi_filterinterp_forward_ori_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_multi_to": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_backward_ori_image_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_forward_ori_multi_to_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_backward_ori_image_multi_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides,
+                                                       _p],
     "vfi_filterinterp_forward_defor": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                        Strides, _p],
     "vfi_filterinterp_backward_defor": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides,
@@ -104,6 +107,8 @@ SIGNATURES = {
 INTERNAL_SIGNATURES = {
     "vfi_filterinterp_forward_ori_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_f16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_forward_ori_multi_to_bf16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides,
+                                                          _p],
     "vfi_filterinterp_forward_defor_general": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                                Strides, _p],
     # (which kernel: 0 the MFMA kernel, 1 the generic kernel)
@@ -187,8 +192,20 @@ def filterinterp_forward_ori(input1, input2, input3, output, direct=False):
                           _st(input1), _st(input2), _st(input3), _stream(input1)))
 
 
+def _fi_image_dtype(images, floats):
+    """_bf16_or_f32 over the image-side tensors of a FilterInterpolation call (the image and the outputs, or the gradients):
+    all bfloat16 -- the `_bf16` entries -- or all float32; the flows and the filter (`floats`) are float32 either way.
+    float16 and every mix raise here, before any library call."""
+    dtype, suffix = _bf16_or_f32(*images)
+    for t in floats:
+        _dev(t)
+    return dtype, suffix
+
+
 def filterinterp_forward_ori_multi(input1, flows, input3, outputs):
-    """outputs[t] = FilterInterpolation(input1, flows[t], input3): the time offsets of a slow-motion step in one launch."""
+    """outputs[t] = FilterInterpolation(input1, flows[t], input3): the time offsets of a slow-motion step in one launch.
+    input1 and the outputs float32, or all bfloat16 (vfi_filterinterp_forward_ori_multi_to_bf16 with the outputs laid out as
+    input1: bf16_rne of the float32 call on the widened image, bit for bit); flows and filter float32 always."""
     n = len(flows)
     if n == 0 or len(outputs) != n:
         return 1
@@ -196,20 +213,27 @@ def filterinterp_forward_ori_multi(input1, flows, input3, outputs):
         # (layouts compared as _same_strides does: the stride of a size-1 dimension is arbitrary, e.g. after slicing)
         if _fi_checks(input1, fl, input3, out) is None or not _same_strides(fl, flows[0]) or not _same_strides(out, input1):
             return 1
-        _dev(fl), _dev(out)
+    dtype, suffix = _fi_image_dtype((input1, *outputs), (input3, *flows))
     b, c, h, w = input1.shape
     fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
     op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outputs])
+    if suffix:
+        with torch.cuda.device(input1.device):
+            return _finish(lib().vfi_filterinterp_forward_ori_multi_to_bf16(
+                _ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1), _st(input1), _st(flows[0]), _st(input3),
+                _st(input1), _stream(input1, dtype)))
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_filterinterp_forward_ori_multi(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1),
                                                                 _st(input1), _st(flows[0]), _st(input3), _stream(input1)))
 
 
-def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs):
+def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs, direct=False):
     """filterinterp_forward_ori_multi into destinations with a layout of their own: outputs[t] (input1's shape; typically
     buf_t[:, k:k + C] of a wider contiguous buffer) receives the same bits.  The destinations share one layout with w
     stride 1 and input1's row stride -- anything else is refused here, before the call; batch and channel strides are
-    free.  They must not overlap input1 or each other (not checked)."""
+    free.  They must not overlap input1 or each other (not checked).  float32, or input1 and every output bfloat16 (a
+    bfloat16 destination slice needs 2-byte alignment only); direct=True (bfloat16 only): the one-thread-per-pixel kernel,
+    an internal entry point the tests compare the staged kernel with."""
     n = len(flows)
     if n == 0 or len(outputs) != n:
         return 1
@@ -221,13 +245,19 @@ def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs):
         # (the row stride of a one-row tensor addresses nothing)
         if input1.size(2) != 1 and out.stride(2) != input1.stride(2):
             return 1
-    for t in (input3, *flows, *outputs):
-        _dev(t)
+    dtype, suffix = _fi_image_dtype((input1, *outputs), (input3, *flows))
+    if direct and not suffix:
+        raise RuntimeError("filterinterp_forward_ori_multi_to: direct=True is the bfloat16 kernels' switch")
     b, c, h, w = input1.shape
     so = _st(outputs[0])
     so.h = input1.stride(2)
     fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
     op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outputs])
+    if suffix:
+        with torch.cuda.device(input1.device):
+            fn = lib().vfi_filterinterp_forward_ori_multi_to_bf16_direct if direct else lib().vfi_filterinterp_forward_ori_multi_to_bf16
+            return _finish(fn(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1), _st(input1), _st(flows[0]),
+                              _st(input3), so, _stream(input1, dtype)))
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_filterinterp_forward_ori_multi_to(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1),
                                                                    _st(input1), _st(flows[0]), _st(input3), so, _stream(input1)))
@@ -263,7 +293,9 @@ def filterinterp_backward_ori(input1, input2, input3, gradoutput, gradinput1, gr
 
 def filterinterp_backward_ori_image_multi(flows, input3, gradoutputs, gradinput1):
     """gradinput1 = the sum over t of the image gradient of FilterInterpolation(., flows[t], input3) for gradoutputs[t]: the
-    backward of filterinterp_forward_ori_multi towards the image alone.  gradinput1 is written in full (no zero fill needed)."""
+    backward of filterinterp_forward_ori_multi towards the image alone.  gradinput1 is written in full (no zero fill needed).
+    The gradients and gradinput1 float32, or all bfloat16 (vfi_filterinterp_backward_ori_image_multi_bf16: bf16_rne of the
+    float32 call on the widened gradients, bit for bit); flows and filter float32 always."""
     n = len(flows)
     if n == 0 or len(gradoutputs) != n:
         return 1
@@ -272,17 +304,16 @@ def filterinterp_backward_ori_image_multi(flows, input3, gradoutputs, gradinput1
         if _fi_checks(gradinput1, fl, input3, None) is None or not _same_strides(fl, flows[0]) or \
                 g.dim() != 4 or g.shape != gradinput1.shape or g.stride(3) != 1 or not _same_strides(g, gradoutputs[0]):
             return 1
-        _dev(fl), _dev(g)
     if not _fi_filter_ok(gradinput1, input3):
         return 1
-    _dev(input3)
+    dtype, suffix = _fi_image_dtype((gradinput1, *gradoutputs), (input3, *flows))
     b, c, h, w = gradinput1.shape
     fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
     gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in gradoutputs])
-    with torch.cuda.device(_dev(gradinput1)):
-        return _finish(lib().vfi_filterinterp_backward_ori_image_multi(
-            fp, _ptr(input3), gp, _ptr(gradinput1), n, b, c, h, w, input3.size(1), _st(gradinput1), _st(flows[0]), _st(input3),
-            _st(gradoutputs[0]), _stream(gradinput1)))
+    with torch.cuda.device(gradinput1.device):
+        fn = getattr(lib(), "vfi_filterinterp_backward_ori_image_multi" + suffix)
+        return _finish(fn(fp, _ptr(input3), gp, _ptr(gradinput1), n, b, c, h, w, input3.size(1), _st(gradinput1), _st(flows[0]),
+                          _st(input3), _st(gradoutputs[0]), _stream(gradinput1, dtype)))
 
 
 def filterinterp_forward_defor(variant, input1, input2, input3, input4, output, general=False):

@@ -7,6 +7,8 @@
 // every flow's addends land in the same cells, so ONE accumulator plane, one header and one conversion serve the whole call
 // (gradacc.h: every addend rounded to an integer at one scale per call, the sums order-free).  Each addend is formed as
 // fi_backward_ori4_tile (filterinterp.hip) forms it, so for one flow the result is that kernel's gradinput1 bit for bit.
+// The kernels and the launcher are templates on the gradients' storage E: float here; filterinterp_bf16.hip includes this
+// file and instantiates them for bfloat16 bits (vfi_filterinterp_backward_ori_image_multi_bf16).
 #include "filterinterp_dev.h"
 #include "gradacc.h"
 
@@ -26,11 +28,16 @@ static_assert(CB_THREADS <= 1024 && CB_THREADS % 64 == 0, "workgroup size");
 static_assert(((CB_WAVES * 256) / CB_THREADS) * (2 + CB_CELLS) * 8 <= 160 * 1024, "workgroups per CU x LDS per workgroup exceed the CU's LDS");
 static_assert(CB_CELLS < (1 << 15), "fi_row_of takes cell indices below 2^15");
 
-// the flows of one launch and their incoming gradients (t < nt)
+// the flows of one launch and their incoming gradients (t < nt); E: the gradients' storage, float or bfloat16 bits
+template <typename E>
 struct CbPtrs {
     const float* flow[CB_NT];
-    const float* gout[CB_NT];
+    const E* gout[CB_NT];
 };
+// an incoming gradient element as the arithmetic sees it: bfloat16 storage widened exactly (the addends, and so the integer
+// sums, are those of the float32 call on the widened gradients)
+__device__ __forceinline__ float cb_grad(const float* p, int64_t o) { return p[o]; }
+__device__ __forceinline__ float cb_grad(const bf16_t* p, int64_t o) { return bf16_widen(p[o]); }
 
 // one pixel under one flow: valid, the blend fractions, and its window's clamped rows and columns
 struct CbPixel {
@@ -59,8 +66,9 @@ __device__ __forceinline__ CbPixel cb_pixel(const float* __restrict__ flow, cons
 // flow, the blend fractions and the window's cell offsets stay in registers across the channel loop.  A tile whose window
 // does not fit one channel, and every tile of a call that scatters in fp32 or needs the second scale factor, is flagged
 // for fi_ctx_backward_px, launched after this kernel with the same flows.
+template <typename E>
 __global__ __launch_bounds__(CB_THREADS, CB_WAVES) void fi_ctx_backward4_lds(
-    CbPtrs ptr, int nt, const float* __restrict__ in3, unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
+    CbPtrs<E> ptr, int nt, const float* __restrict__ in3, unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
     int* __restrict__ tileflag, int channel, int h, int w, vfi_strides s2, vfi_strides s3, vfi_strides sg, int groups,
     int ch_per_group) {
     __shared__ __attribute__((aligned(16))) unsigned long long lds64[2 + CB_CELLS];      // header (bounding box), cells
@@ -116,12 +124,12 @@ __global__ __launch_bounds__(CB_THREADS, CB_WAVES) void fi_ctx_backward4_lds(
         __syncthreads();
         static_for<0, CB_NT>([&](auto t) {
             if (px[t].valid) {
-                const float* gp = ptr.gout[t] + gpx + (int64_t)c0 * sg.c;
+                const E* gp = ptr.gout[t] + gpx + (int64_t)c0 * sg.c;
                 const float alpha = px[t].alpha, beta = px[t].beta;
-                float g = gp[0];
+                float g = cb_grad(gp, 0);
 #pragma unroll 1
                 for (int cc = 0; cc < cn; ++cc) {
-                    const float gnext = cc + 1 < cn ? gp[(int64_t)(cc + 1) * sg.c] : 0.0f;
+                    const float gnext = cc + 1 < cn ? cb_grad(gp, (int64_t)(cc + 1) * sg.c) : 0.0f;
                     unsigned long long* plane = cells + cc * n;
                     const float qg[4] = { g * (1.0f - alpha) * (1.0f - beta), g * alpha * (1.0f - beta),
                                           g * (1.0f - alpha) * beta,          g * alpha * beta };
@@ -152,9 +160,11 @@ __global__ __launch_bounds__(CB_THREADS, CB_WAVES) void fi_ctx_backward4_lds(
 
 // one thread per pixel, any filter size: every flow of the launch, every channel, each addend through gradacc_add (the
 // integer sums, or the reference's fp32 atomics for a call with non-finite inputs).  After fi_ctx_backward4_lds: only the
-// tiles that kernel flagged (VFI_TX x VFI_TY blocks nest in them).
+// tiles that kernel flagged (VFI_TX x VFI_TY blocks nest in them).  A bfloat16 call that scatters in fp32 adds its floats
+// into the low words of the zeroed 64-bit cells (gradacc.h), never into bfloat16 storage: g1 is not looked at.
+template <typename E>
 __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_ctx_backward_px(
-    CbPtrs ptr, int nt, const float* __restrict__ in3, unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
+    CbPtrs<E> ptr, int nt, const float* __restrict__ in3, unsigned long long* __restrict__ acc, const int* __restrict__ hdr,
     const int* __restrict__ tileflag, float* g1, int channel, int h, int w, int fs, vfi_strides s1, vfi_strides s2,
     vfi_strides s3, vfi_strides sg) {
     const int x = blockIdx.x * VFI_TX + threadIdx.x;
@@ -172,11 +182,12 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_ctx_backward_px(
         const int ix = g.ix, iy = g.iy;
         const int L = ix + 1 - fs / 2, T = iy + 1 - fs / 2;
         const float alpha = g.alpha, beta = g.beta;
-        const float* gpx = ptr.gout[t] + (int64_t)b * sg.b + (int64_t)y * sg.h + x;
+        const E* gpx = ptr.gout[t] + (int64_t)b * sg.b + (int64_t)y * sg.h + x;
         for (int c = 0; c < channel; ++c) {
             unsigned long long* gp = gimg + (int64_t)c * h * w;
-            float* gfp = g1 + (int64_t)b * s1.b + (int64_t)c * s1.c;    // (the fp32 scatter of a call with non-finite inputs)
-            const float gr = gpx[(int64_t)c * sg.c];
+            // (the fp32 scatter of a call with non-finite inputs)
+            float* gfp = std::is_same<E, float>::value ? g1 + (int64_t)b * s1.b + (int64_t)c * s1.c : reinterpret_cast<float*>(gp);
+            const float gr = cb_grad(gpx, (int64_t)c * sg.c);
             const float qg[4] = { gr * (1.0f - alpha) * (1.0f - beta), gr * alpha * (1.0f - beta),
                                   gr * (1.0f - alpha) * beta,          gr * alpha * beta };
             for (int j = 0; j < fs; ++j) {
@@ -185,7 +196,10 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_ctx_backward_px(
                     const int cx = clampi(L + i, 0, w - 1);
                     const int quad = (T + j > iy ? 2 : 0) + (L + i > ix ? 1 : 0);
                     const float fv = fpx[(int64_t)(j * fs + i) * s3.c];
-                    gradacc_add(gp, gfp, (int64_t)cy * w + cx, (int64_t)cy * s1.h + cx, qg[quad] * fv, gctx);
+                    if constexpr (std::is_same<E, float>::value)
+                        gradacc_add(gp, gfp, (int64_t)cy * w + cx, (int64_t)cy * s1.h + cx, qg[quad] * fv, gctx);
+                    else                                    // (float index 2 x cell index: the cell's low word)
+                        gradacc_add(gp, gfp, (int64_t)cy * w + cx, 2 * ((int64_t)cy * w + cx), qg[quad] * fv, gctx);
                 }
             }
         }
@@ -193,17 +207,17 @@ __global__ __launch_bounds__(VFI_TX * VFI_TY) void fi_ctx_backward_px(
 }
 
 // hdr[3] of the call: gradacc_scan writes the value for one flow's taps; the call's cells receive every flow's
+// (a template like the two above: each translation unit that instantiates the call carries its own copy)
+template <typename E>
 __global__ void fi_ctx_set_cells_log2(int* __restrict__ hdr, int cells_log2) { hdr[3] = cells_log2; }
 
-}  // namespace vfi
-
-using namespace vfi;
-
-extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flows, const float* input3,
-                                                          const float* const* gradoutputs, float* gradinput1, int nflows,
-                                                          int batch, int channel, int h, int w, int filter_channels,
-                                                          vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
-                                                          vfi_stream_t stream) {
+// the call for gradients stored as E (float, or bfloat16 bits): gradoutputs[t] and gradinput1 are E tensors
+template <typename E>
+static int backward_image_multi(const float* const* flows, const float* input3, const E* const* gradoutputs, E* gradinput1,
+                                int nflows, int batch, int channel, int h, int w, int filter_channels, vfi_strides s1,
+                                vfi_strides s2, vfi_strides s3, vfi_strides sg, vfi_stream_t stream) {
+    constexpr bool F32 = std::is_same<E, float>::value;
+    using Scan = typename std::conditional<F32, GradPlain, GradBf16>::type;
     if (nflows <= 0 || !flows || !gradoutputs || batch <= 0 || channel <= 0 || h <= 0 || w <= 0 || filter_channels <= 0)
         return VFI_ERR_SHAPE;
     if (!input3 || !gradinput1) return VFI_ERR_SHAPE;
@@ -223,7 +237,7 @@ extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flo
     if (err != VFI_OK) return err;
     // the maxima over every gradient and the filter (the scans raise them with atomicMax into the one header)
     for (int t = 0; t < nflows; ++t) {
-        err = gradacc_scan(st, GradPlain{gradoutputs[t]}, batch, channel, h, w, sg, t == 0 ? input3 : nullptr, filter_channels, s3,
+        err = gradacc_scan(st, Scan{gradoutputs[t]}, batch, channel, h, w, sg, t == 0 ? input3 : nullptr, filter_channels, s3,
                            sc.dir[0].hdr);
         if (err != VFI_OK) return err;
     }
@@ -231,10 +245,12 @@ extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flo
     const int64_t taps = (int64_t)(filter_channels > 4 ? filter_channels : 4) * nflows;
     int cells_log2 = 0;
     while (cells_log2 < 62 && ((int64_t)1 << cells_log2) < (int64_t)h * w * taps) ++cells_log2;
-    hipLaunchKernelGGL(fi_ctx_set_cells_log2, dim3(1), dim3(1), 0, st, sc.dir[0].hdr, cells_log2);
+    hipLaunchKernelGGL(fi_ctx_set_cells_log2<E>, dim3(1), dim3(1), 0, st, sc.dir[0].hdr, cells_log2);
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    err = gradacc_zero_fp32(st, sc.dir[0].hdr, gradinput1, batch, channel, h, w, s1);
-    if (err != VFI_OK) return err;
+    if constexpr (F32) {                                    // (a bfloat16 call's fp32 scatter goes into the zeroed scratch)
+        err = gradacc_zero_fp32(st, sc.dir[0].hdr, gradinput1, batch, channel, h, w, s1);
+        if (err != VFI_OK) return err;
+    }
     static_assert(VFI_TX == CB_TW && CB_TH % VFI_TY == 0, "fi_ctx_backward_px's blocks nest in the staged kernel's tiles");
     // channel groups: a workgroup repeats the tile's prologue (flows, filter, bounding box) per group
     int groups = 1, ch_per_group = channel;
@@ -248,7 +264,7 @@ extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flo
         groups = (channel + ch_per_group - 1) / ch_per_group;
     }
     for (int l = 0; l < launches; ++l) {
-        CbPtrs ptr;
+        CbPtrs<E> ptr;
         const int nt = nflows - l * CB_NT < CB_NT ? nflows - l * CB_NT : CB_NT;
         for (int t = 0; t < CB_NT; ++t) {
             ptr.flow[t] = flows[l * CB_NT + (t < nt ? t : 0)];
@@ -256,11 +272,30 @@ extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flo
         }
         int* flags = staged ? sc.flags + (int64_t)l * ntiles : nullptr;
         if (staged)
-            hipLaunchKernelGGL(fi_ctx_backward4_lds, dim3(tiles_x, tiles_y, batch * groups), dim3(CB_THREADS), 0, st, ptr, nt,
+            hipLaunchKernelGGL(fi_ctx_backward4_lds<E>, dim3(tiles_x, tiles_y, batch * groups), dim3(CB_THREADS), 0, st, ptr, nt,
                                input3, sc.dir[0].acc, sc.dir[0].hdr, flags, channel, h, w, s2, s3, sg, groups, ch_per_group);
-        hipLaunchKernelGGL(fi_ctx_backward_px, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, st, ptr, nt, input3,
-                           sc.dir[0].acc, sc.dir[0].hdr, flags, gradinput1, channel, h, w, fs, s1, s2, s3, sg);
+        hipLaunchKernelGGL(fi_ctx_backward_px<E>, pixel_grid(w, h, batch), dim3(VFI_TX, VFI_TY, 1), 0, st, ptr, nt, input3,
+                           sc.dir[0].acc, sc.dir[0].hdr, flags, F32 ? reinterpret_cast<float*>(gradinput1) : nullptr, channel, h, w,
+                           fs, s1, s2, s3, sg);
     }
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
-    return gradacc_finish(st, sc.dir[0], gradinput1, batch, channel, h, w, s1, true);
+    if constexpr (F32) return gradacc_finish(st, sc.dir[0], gradinput1, batch, channel, h, w, s1, true);
+    else return gradacc_finish_bf16(st, sc.dir[0], gradinput1, batch, channel, h, w, s1);
 }
+
+}  // namespace vfi
+
+// filterinterp_bf16.hip includes this file for the templates above (its bfloat16 instances live in that unit's object and
+// assembly); the float32 entry point is this unit's alone
+#ifndef FI_CTX_BWD_TEMPLATES_ONLY
+using namespace vfi;
+
+extern "C" int vfi_filterinterp_backward_ori_image_multi(const float* const* flows, const float* input3,
+                                                          const float* const* gradoutputs, float* gradinput1, int nflows,
+                                                          int batch, int channel, int h, int w, int filter_channels,
+                                                          vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
+                                                          vfi_stream_t stream) {
+    return backward_image_multi<float>(flows, input3, gradoutputs, gradinput1, nflows, batch, channel, h, w, filter_channels, s1,
+                                       s2, s3, sg, stream);
+}
+#endif

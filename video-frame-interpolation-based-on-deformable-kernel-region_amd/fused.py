@@ -349,13 +349,14 @@ class _FilterInterpolateCtx(torch.autograd.Function):
     """One direction of `FilterInterpolate_ctx` for a list of time offsets: the forward is the one multi-flow launch, the
     backward ONE vfi_filterinterp_backward_ori_image_multi call over the outputs that received a gradient.  The context
     tensor's gradient does not depend on its values, so only the flows and the filter are saved.  Flows and filter get no
-    gradient (the reference detaches them)."""
+    gradient (the reference detaches them).  A bfloat16 image takes the bfloat16 entries: its outputs and its gradient are
+    bfloat16, flows and filter arrive here as float32 (`_ctx_warp` widens them) and are saved as such."""
 
     @staticmethod
     def forward(ctx, image, filt, *offsets):
         outs = _ctx_warp_launch(image, offsets, filt)
         ctx.save_for_backward(filt, *offsets)
-        ctx.image_layout = (image.shape, image.stride())
+        ctx.image_layout = (image.shape, image.stride(), image.dtype)
         ctx.set_materialize_grads(False)                   # (an unused time offset is an absent flow, not a tensor of zeros)
         return tuple(outs)
 
@@ -368,15 +369,23 @@ class _FilterInterpolateCtx(torch.autograd.Function):
         if not live or not ctx.needs_input_grad[0]:
             return none
         gs = _grad_layout([grads[i] for i in live])
-        shape, stride = ctx.image_layout
-        gimg = torch.empty_strided(shape, stride, dtype=torch.float32, device=gs[0].device)      # (written in full)
+        shape, stride, dtype = ctx.image_layout
+        gimg = torch.empty_strided(shape, stride, dtype=dtype, device=gs[0].device)      # (written in full)
         _check(cabi.filterinterp_backward_ori_image_multi([offsets[i] for i in live], filt, gs, gimg),
                "filterinterp_backward_ori_image_multi")
         return (gimg,) + none[1:]
 
 
+def _f32_once(t):
+    """a bfloat16 flow or filter widened to float32 (exact); a float32 tensor as it is"""
+    return t.float() if t.dtype == torch.bfloat16 else t
+
+
 def _ctx_warp(image, offsets, filt):
-    """one direction: the Function when the context tensor can train, today's plain launch otherwise"""
+    """one direction: the Function when the context tensor can train, today's plain launch otherwise.  With a bfloat16
+    context tensor a bfloat16 flow or filter is widened here, once per direction; float32 calls pass through untouched."""
+    if image.dtype == torch.bfloat16:
+        offsets, filt = [_f32_once(o) for o in offsets], _f32_once(filt)
     if _wants_grad(image):
         return list(_FilterInterpolateCtx.apply(image, filt, *offsets))
     return _ctx_warp_launch(image, offsets, filt)
@@ -391,7 +400,12 @@ def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
     tensor gets the sum over the time offsets of FilterInterpolationModule's image gradient, from ONE call of the library
     over the outputs the loss used (reproducible bit for bit).  Offsets and filter get NO gradient, whether or not they
     require grad: the reference passes `offset[d].detach()` and `filter[d].detach()` on this path.  Otherwise (inference,
-    or no context tensor requiring grad) the plain forward launches, with no grad_fn."""
+    or no context tensor requiring grad) the plain forward launches, with no grad_fn.
+    bfloat16 context tensors (a context network under `torch.autocast(dtype=torch.bfloat16)`) are warped as they are: the
+    outputs are bfloat16 -- bit for bit `.float()`, the float32 call, `.bfloat16()` -- and so is the context gradient,
+    bf16_rne of the float32 backward on the widened incoming gradients.  Flow and filter stay float32 in the kernels: a
+    bfloat16 flow or filter is widened once per direction with `.float()`, which is exact.  A float32 context tensor takes
+    the launches it always took."""
     out0 = _ctx_warp(ctx0, list(offsets[0]), filter[0])
     out2 = _ctx_warp(ctx2, list(offsets[1]), filter[1])
     return list(zip(out0, out2))
