@@ -52,6 +52,7 @@ BLOCK_CAP, NMAX, INV_BITS = _c("PROJ_BLOCK_CAP"), _c("PROJ_NMAX"), _c("PROJ_INV_
 GH, GW = TH + 1, TW + 1                                     # K1's grid: one row above, one column left of the tile
 MAX_CLS = 4                                                 # min(4, ...) in both K1 variants
 K_CLAMP = 100                                               # max(-100, min(100, ...)) of the scales
+W_LO_BITS, W_HI_BITS = _c("PROJ_W_LO_BITS"), _c("PROJ_W_HI_BITS")   # a block's largest |weight| outside: fallback
 
 K1_VARIANTS = ("lean", "pull_vec", "pull_scalar")
 BASE_LABELS = ("empty", "plain", "retry_1", "retry_2", "retry_3+", "wide_cell", "edge_x", "edge_y", "lopsided")
@@ -95,6 +96,13 @@ def _bits(a):
     return np.abs(a.astype(f32)).view(np.int32).astype(np.int64)
 
 
+def weight_unfit(cbits):
+    """proj_weight_unfit: the bits of a block's largest |weight| over its valid sources that the fixed-point path cannot
+    hold -- NaN, infinite, 2^64 and more, or non-zero below 2^-56.  Such a block sends the call to the fallback."""
+    cbits = int(cbits)
+    return cbits != 0 and not W_LO_BITS <= cbits < W_HI_BITS
+
+
 def targets(fx, fy, h, w):
     """The reference's top-left target: x2 = x + fx in fp32, valid when 0 <= x2 <= w - 1 (NaN fails), L = trunc(x2)."""
     ys, xs = np.meshgrid(np.arange(h, dtype=f32), np.arange(w, dtype=f32), indexing="ij")
@@ -136,7 +144,7 @@ def _image_records(fx, fy, d, h, w):
             Y0, Y1 = max(y0 + dtmin, 0), min(by1 + dtmax, h - 1)
             a0, a1 = X0 // TW, min(X1 + 1, w - 1) // TW
             c0, c1 = Y0 // TH, min(Y1 + 1, h - 1) // TH
-            if (a1 - a0 + 1) * (c1 - c0 + 1) > BLOCK_CAP:
+            if (a1 - a0 + 1) * (c1 - c0 + 1) > BLOCK_CAP or weight_unfit(f5):
                 wild = True
                 continue
             for ty in range(c0, c1 + 1):

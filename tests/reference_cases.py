@@ -213,6 +213,18 @@ def cases(extra=False):
         c["x_corr_planted"] = Case("corr_planted", dict(f1=f1, f2=f2), cfg=pwc)
         # pad 8: the output origin lies outside the frame, so the FIRST map's tap meets the padding too (0 * inf)
         c["x_corr_planted_pad8"] = Case("corr_planted", dict(f1=f1, f2=f2), cfg=(8, 1, 4, 1, 1))
+        # the forward warps and projections on planted inputs (tests/forward_edges.py): forward only, NaN and infinity are
+        # results.  Every planted flow fails the reference's validity test or gives an exactly representable position
+        # inside the frame, so no case depends on the conversion of an out-of-range float to int
+        from tests import forward_edges as fe
+        rng = np.random.default_rng(20261020)
+        flow, depth = fe.small_proj_inputs(rng)
+        c["x_flowproj_planted"] = Case("planted", dict(flow=flow), what="flowproj")
+        c["x_depthproj_planted"] = Case("planted", dict(flow=flow, depth=depth), what="depthproj")
+        img, flow, filt = fe.small_fi_inputs(rng)
+        c["x_fi_ori_planted"] = Case("planted", dict(img=img, flow=flow, filt=filt), what="fi_ori")
+        img, flow = fe.small_interp_inputs(rng)
+        c["x_interp_planted"] = Case("planted", dict(img=img, flow=flow), what="interp")
     return c
 
 
@@ -313,6 +325,16 @@ def run_ref(R, case, given=None):
             o["g1"], o["g2"], (o["mask1"], o["mask2"]) = R.correlation_bwd(i["f1"], i["f2"], i["gout"], *cfg, canvas=True)
     elif op == "corr_planted":
         o["out"] = R.correlation_fwd(i["f1"], i["f2"], *p["cfg"])      # (NaN is a result here: no canvas mask)
+    elif op == "planted":                                              # (likewise)
+        what = p["what"]
+        if what == "flowproj":
+            (o["out0"], o["count"]), (o["out1"], _) = R.flowproj_fwd(i["flow"], 0), R.flowproj_fwd(i["flow"], 1)
+        elif what == "depthproj":
+            (o["out0"], o["count"]), (o["out1"], _) = (R.depthflowproj_fwd(i["flow"], i["depth"], fh) for fh in (0, 1))
+        elif what == "fi_ori":
+            o["out"] = R.filterinterp_ori_fwd(i["img"], i["flow"], i["filt"])
+        else:
+            o["out"] = R.interp_fwd(i["img"], i["flow"])
     else:
         raise KeyError(op)
     return o
@@ -365,6 +387,16 @@ def run_oracle(O, case, ref):
             o["g1"], o["g2"] = O.correlation_bwd(i["f1"], i["f2"], i["gout"], *cfg, fmad=0)
     elif op == "corr_planted":
         o["out"] = O.correlation_fwd(i["f1"], i["f2"], *p["cfg"], order=0, fmad=0)
+    elif op == "planted":
+        what = p["what"]
+        if what == "flowproj":
+            (o["out0"], o["count"]), (o["out1"], _) = O.flowproj_fwd(i["flow"], 0), O.flowproj_fwd(i["flow"], 1)
+        elif what == "depthproj":
+            (o["out0"], o["count"]), (o["out1"], _) = (O.depthflowproj_fwd(i["flow"], i["depth"], fh) for fh in (0, 1))
+        elif what == "fi_ori":
+            o["out"] = O.filterinterp_ori_fwd(i["img"], i["flow"], i["filt"], fmad=0)
+        else:
+            o["out"] = O.interp_fwd(i["img"], i["flow"], fmad=0)
     else:
         raise KeyError(op)
     return o
@@ -460,6 +492,29 @@ def check(name, case, ref_raster, got, ref_blocks=None):
             assert corr_edges.same_bits_nan_aware(ref_blocks["out"], want), (name, "the executor's two orders differ")
         assert corr_edges.same_bits_nan_aware(got["out"], want), (name, "oracle != reference",
                                                                   corr_edges.describe_difference(got["out"], want))
+        return
+    if case.op == "planted":
+        # as above: NaN masks equal and everything else bit for bit, in both thread orders (the planted values sit apart and
+        # the rest is dyadic, so the projections' sums do not depend on the order); and the plants did reach the outputs
+        from tests import corr_edges
+        what = case.params["what"]
+        for key, want in ref_raster.items():
+            if ref_blocks is not None:
+                assert corr_edges.same_bits_nan_aware(ref_blocks[key], want), (name, key, "the executor's two orders differ")
+            assert corr_edges.same_bits_nan_aware(got[key], want), (name, key, "oracle != reference",
+                                                                    corr_edges.describe_difference(got[key], want))
+            assert np.isfinite(want).mean() >= 0.5, (name, key)
+        if what == "flowproj":
+            assert all(np.isfinite(v).all() for v in ref_raster.values()), (name, "no planted flow is a valid source")
+        elif what == "depthproj":
+            cnt = ref_raster["count"]
+            assert np.isnan(cnt).any() and (cnt == np.inf).any() and (cnt == -np.inf).any(), name
+            assert ((cnt > 0) & (cnt < 2.0 ** -140)).any(), (name, "subnormal counts")
+            hole = cnt <= 0
+            assert (hole & np.isfinite(ref_raster["out0"][:, :1]) & np.isnan(ref_raster["out1"][:, :1])).any(), (
+                name, "a hole filled with NaN from a poisoned neighbour")
+        else:
+            assert np.isnan(ref_raster["out"]).any() and np.isinf(ref_raster["out"]).any(), name
         return
     scatter = SCATTER.get(case.op, {})
     check_masks(case, ref_raster)

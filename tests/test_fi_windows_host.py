@@ -164,3 +164,27 @@ def test_random_boxes_never_reach_an_uncompiled_instance():
     for aligned in (True, False):
         names, _ = fw.decide("lds", x0, y0, x0 + bw - 1, y0 + bh - 1, np.ones(n, bool), 1080, 1920, aligned)
         assert not any("UNCOMPILED" in s for s in set(names))
+
+
+def test_non_finite_flows_are_invalid_pixels_that_add_nothing_to_the_box():
+    """A NaN, infinite or huge flow fails fi_valid (every comparison with NaN is false, |inf| < w/2 is false): the pixel is
+    copied through and its tile's box is that of the other pixels -- the mirror's, as the kernels' (tests/forward_edges.py
+    plants such flows)."""
+    h, w = 16, 64
+    flow = np.full((1, 2, h, w), 0.5, np.float32)
+    base = fw.tile_boxes("lds", flow, h, w)
+    f2 = flow.copy()
+    for k, v in enumerate((np.nan, -np.nan, np.inf, -np.inf, 3e38, -3e38)):
+        f2[0, k % 2, 3, 5 + 4 * k] = v
+    valid0 = fw.samples(flow, h, w)[0]
+    valid, ix, iy, _, _ = fw.samples(f2, h, w)
+    assert (valid0 & ~valid).sum() == 6 and not (valid & ~valid0).any()
+    assert (ix[~valid] == 0).all() and (iy[~valid] == 0).all()
+    for a, b in zip(base, fw.tile_boxes("lds", f2, h, w)):
+        assert np.array_equal(a, b)
+    assert np.array_equal(fw.classes("lds", flow, h, w), fw.classes("lds", f2, h, w))
+    # -0.0 stays valid everywhere; the largest negative subnormal only leaves the frame from column 0
+    f3 = flow.copy()
+    f3[0, 0, 2, 0], f3[0, 0, 2, 7], f3[0, 0, 4, 0] = -2.0 ** -149, -2.0 ** -149, -0.0
+    v3 = fw.samples(f3, h, w)[0]
+    assert not v3[0, 2, 0] and v3[0, 2, 7] and v3[0, 4, 0]

@@ -82,6 +82,56 @@ def test_hand_worked_records():
     assert not pt.records(flow, None, 16 * 13, 64 * 5)[1]
 
 
+def test_weight_predicate_matches_the_source_and_spares_ordinary_calls():
+    """The second fallback reason: a block whose largest |weight| the fixed-point sums cannot hold (proj_weight_unfit)."""
+    text = " ".join(source(pt.SOURCE).split())
+    assert ("return cbits != 0 && (unsigned)(cbits - PROJ_W_LO_BITS) >= (unsigned)(PROJ_W_HI_BITS - PROJ_W_LO_BITS);") in text
+    # both K0 kernels test it beside the PROJ_BLOCK_CAP reason, on the block's largest weight over its valid sources
+    assert "> PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));" in text
+    assert "const bool wild = any && (nx * ny > PROJ_BLOCK_CAP || proj_weight_unfit(e[5]));" in text
+    assert text.count("proj_weight_unfit(") == 3
+    bits = lambda v: int(np.abs(f32(v)).view(np.int32))     # noqa: E731
+    assert pt.W_LO_BITS == bits(2.0 ** -56) and pt.W_HI_BITS == bits(2.0 ** 64)
+    for v, unfit in ((0.0, False), (-0.0, False), (2.0 ** -40, False), (2.0 ** 40, False), (-2.0 ** 40, False), (2.0 ** -56, False),
+                     (np.nextafter(f32(2.0 ** 64), f32(0)), False), (2.0 ** 64, True), (2.0 ** 100, True), (3.4e38, True),
+                     (np.inf, True), (-np.inf, True), (np.nan, True), (np.nextafter(f32(2.0 ** -56), f32(0)), True),
+                     (2.0 ** -80, True), (2.0 ** -149, True)):
+        assert pt.weight_unfit(bits(v)) == unfit, v
+    # inside the range no scale clamp bites on account of the weight: a valid |flow| is below 2^15 (frames are at most 32767
+    # wide), the last class adds (MAX_CLS - 1) * CLS_BITS
+    for ec in (-55, 64):                                     # frexp exponents of 2^-56 and of the float below 2^64
+        for efx in (0, 15):
+            for cls in range(pt.MAX_CLS):
+                assert abs(pt.ADD_BITS - (ec - pt.CLS_BITS * cls)) <= pt.K_CLAMP
+                assert abs(pt.ADD_BITS - (efx + ec - pt.CLS_BITS * cls)) <= pt.K_CLAMP
+    # the largest product weight x flow stays finite in fp32
+    assert np.isfinite(np.nextafter(f32(2.0 ** 64), f32(0)) * f32(32767))
+    # weights in [2^-40, 2^40] with flows below 2^12 keep their path; one weight outside the range sends the call away --
+    # but only at a VALID source
+    rng = np.random.default_rng(8)
+    h, w = 48, 160
+    flow = np.round(rng.uniform(-3, 3, (1, 2, h, w)) * 8).astype(f32) / 8
+    depth = np.exp2(rng.integers(-40, 41, (1, 1, h, w))).astype(f32)
+    assert not pt.records(flow, depth, h, w)[1]
+    assert not pt.records(flow, np.zeros_like(depth), h, w)[1]
+    for v in (np.inf, -np.inf, np.nan, 2.0 ** 100, -2.0 ** 64):
+        d2 = depth.copy()
+        d2[0, 0, 20, 70] = v
+        fl = flow.copy()
+        fl[0, :, 20, 70] = 0
+        assert pt.records(fl, d2, h, w)[1], v
+        fl[0, 0, 20, 70] = 4000.0                            # the source leaves the frame: its weight is never read
+        assert not pt.records(fl, d2, h, w)[1], v
+    # a whole block of tiny weights (its largest is tiny): fallback; one tiny weight beside ordinary ones: not
+    d2 = depth.copy()
+    d2[0, 0, 16:32, 32:48] = 2.0 ** -90
+    assert pt.records(flow, d2, h, w)[1]
+    d2 = depth.copy()
+    d2[0, 0, 20, 70] = 2.0 ** -149
+    d2[0, 0, 20, 71] = 1.0
+    assert not pt.records(flow, d2, h, w)[1]
+
+
 def test_hand_worked_regimes():
     h, w = 32, 128
     flow = np.full((1, 2, h, w), 0.5, f32)

@@ -30,7 +30,8 @@
 // no kernel argument changes from call to call: a captured graph is replayable.
 //
 // Fallback: a block whose pixels scatter over more than PROJ_BLOCK_CAP output tiles (random flow of
-// +-W/2) raises a flag in K0; K1 then splats its own tile with global atomics exactly like the
+// +-W/2), or whose weights the fixed-point sums cannot hold (proj_weight_unfit: non-finite, huge or
+// tiny), raises a flag in K0; K1 then splats its own tile with global atomics exactly like the
 // reference -- into three scratch planes of the workspace that are zero between calls -- and K2
 // normalises them into count / output and fills holes from them.  (The scratch planes are cleaned by
 // the next call's K0, whose workgroups see a "dirty" word.)
@@ -83,6 +84,18 @@ namespace vfi {
 #define PROJ_WS_DIRTY 2
 #define PROJ_TILE_WORDS 8
 #define PROJ_INV_BITS 0x7f7fffff       // a weight's bits are stored as this minus them where the SMALLEST is wanted
+
+// What the fixed-point path can hold (DepthFlowProjection).  A block whose largest |weight| over its valid sources is NaN,
+// infinite, at least 2^64 or -- unless it is zero -- below 2^-56 raises the fallback flag in K0 like a block that scatters too
+// widely: the call then runs the reference's own fp32 atomic scheme, in which a non-finite weight poisons exactly the cells it
+// poisons there.  Inside [2^-56, 2^64) the weights make none of K1's scale clamps max(-100, min(100, .)) bite (a valid |flow| is
+// below 2^15 and the last weight class adds 18: 25 + 55 + 18 <= 100, 25 - 64 - 15 >= -100; only flows that are tiny as well
+// reach the upper clamp, which then costs precision below 2^-101, never range) and no product weight x flow leaves fp32.
+#define PROJ_W_LO_BITS 0x23800000      // bits of 2^-56
+#define PROJ_W_HI_BITS 0x5f800000      // bits of 2^64; infinities and NaNs (|weight|'s bits as an integer) lie above
+__device__ __forceinline__ bool proj_weight_unfit(int cbits) {
+    return cbits != 0 && (unsigned)(cbits - PROJ_W_LO_BITS) >= (unsigned)(PROJ_W_HI_BITS - PROJ_W_LO_BITS);
+}
 
 // header words [2], [3]: how many floats of the fallback's scratch planes hold sums (64 bits; 0 = clean).  The count, not a
 // flag: the next call cleans what THIS call dirtied, whatever its own frame size is.
@@ -213,7 +226,7 @@ __device__ __forceinline__ void scan_scatter(const ProjGeom& g, int* __restrict_
         if (!__builtin_amdgcn_readlane((int)any, sl)) continue;
         const int a0 = __builtin_amdgcn_readlane(X0, sl) / PROJ_TW, a1 = min(__builtin_amdgcn_readlane(X1, sl) + 1, g.w - 1) / PROJ_TW;
         const int c0 = __builtin_amdgcn_readlane(Y0, sl) / PROJ_TH, c1 = min(__builtin_amdgcn_readlane(Y1, sl) + 1, g.h - 1) / PROJ_TH;
-        wild = wild || (a1 - a0 + 1) * (c1 - c0 + 1) > PROJ_BLOCK_CAP;
+        wild = wild || (a1 - a0 + 1) * (c1 - c0 + 1) > PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));
         ta = min(ta, a0); tb = max(tb, a1); tc = min(tc, c0); td = max(td, c1);
     }
     if (wild) { if (lane == 0) ws[PROJ_WS_FLAG] = 1; return; }
@@ -398,7 +411,7 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
         const int Y0 = max(y0 + dtmin_, 0), Y1 = min(by1 + dtmax_, g.h - 1);
         const int a0 = X0 / PROJ_TW, a1 = min(X1 + 1, g.w - 1) / PROJ_TW, c0 = Y0 / PROJ_TH, c1 = min(Y1 + 1, g.h - 1) / PROJ_TH;
         const int nx = a1 - a0 + 1, ny = c1 - c0 + 1;
-        const bool wild = any && nx * ny > PROJ_BLOCK_CAP;
+        const bool wild = any && (nx * ny > PROJ_BLOCK_CAP || proj_weight_unfit(e[5]));
         if (wild && j == 0) ws[PROJ_WS_FLAG] = 1;               // the call takes the fallback; records no longer matter
         const bool wide = any && !wild && (nx > 2 || ny > 8);   // more tiles than slots: thread j == 0 walks them all
         const int torg_x = gxi * 4 - PROJ_STAB_X0, torg_y = tyi - PROJ_STAB_Y0;
@@ -1320,21 +1333,24 @@ __global__ __launch_bounds__(PROJ_FIN_THREADS) void proj_finish(
                 o1[row + x] = p1[me] / c;
                 continue;
             }
-            float v0 = 0.0f, v1 = 0.0f;
-            if (fillhole) {
+            // not positive: the sums stay as they are (:129-134) -- zero in a cell nothing reached, the weighted sums where the
+            // weights cancel or are negative, NaN where the count is NaN -- and a NaN count is no hole (:186: count <= 0)
+            float v0 = p0[me], v1 = p1[me];
+            if (fillhole && c <= 0.0f) {
                 const ProjScan l = proj_walk_plain(pc, (int64_t)y * g.w, 1, x, g.w, -1), rr = proj_walk_plain(pc, (int64_t)y * g.w, 1, x, g.w, +1);
                 const ProjScan u = proj_walk_plain(pc, x, g.w, y, g.h, -1), d = proj_walk_plain(pc, x, g.w, y, g.h, +1);
-                if (l.cnt + rr.cnt + u.cnt + d.cnt > 0.0f) {
+                if (!(l.cnt + rr.cnt + u.cnt + d.cnt <= 0.0f)) {            // (a NaN count among them goes on, as in the reference)
                     const float lt = (l.cnt > 0.0f) ? 1.0f : 0.0f, rt = (rr.cnt > 0.0f) ? 1.0f : 0.0f;
                     const float ut = (u.cnt > 0.0f) ? 1.0f : 0.0f, dt = (d.cnt > 0.0f) ? 1.0f : 0.0f;
                     const float den = lt + rt + ut + dt;
                     const int64_t il = (int64_t)y * g.w + l.pos, ir = (int64_t)y * g.w + rr.pos;
                     const int64_t iu = (int64_t)u.pos * g.w + x, id = (int64_t)d.pos * g.w + x;
-                    // a neighbour found by a walk has count > 0; the others carry weight 0 (their cell is a hole: value 0)
-                    const float a0 = l.cnt > 0.0f ? p0[il] / l.cnt : 0.0f, b0 = rr.cnt > 0.0f ? p0[ir] / rr.cnt : 0.0f;
-                    const float c0 = u.cnt > 0.0f ? p0[iu] / u.cnt : 0.0f, d0 = d.cnt > 0.0f ? p0[id] / d.cnt : 0.0f;
-                    const float a1 = l.cnt > 0.0f ? p1[il] / l.cnt : 0.0f, b1 = rr.cnt > 0.0f ? p1[ir] / rr.cnt : 0.0f;
-                    const float c1 = u.cnt > 0.0f ? p1[iu] / u.cnt : 0.0f, d1 = d.cnt > 0.0f ? p1[id] / d.cnt : 0.0f;
+                    // The reference MULTIPLIES the cell a walk stopped at by its 0 / 1 weight: a cell of weight 0 -- a negative or
+                    // NaN count, or the frame's border when the walk found nothing -- still gives 0 * its value, NaN when that is
+                    // not finite.  Its value: normalised where its count is positive, else its sums.
+                    auto val = [](const float* p, int64_t i, float cnt) { const float s = p[i]; return cnt > 0.0f ? s / cnt : s; };
+                    const float a0 = val(p0, il, l.cnt), b0 = val(p0, ir, rr.cnt), c0 = val(p0, iu, u.cnt), d0 = val(p0, id, d.cnt);
+                    const float a1 = val(p1, il, l.cnt), b1 = val(p1, ir, rr.cnt), c1 = val(p1, iu, u.cnt), d1 = val(p1, id, d.cnt);
                     v0 = (lt * a0 + rt * b0 + ut * c0 + dt * d0) / den;
                     v1 = (lt * a1 + rt * b1 + ut * c1 + dt * d1) / den;
                 }
