@@ -1,4 +1,4 @@
-"""Host mirror, exact restatement and field builder for vfi_filterinterp_backward_ori_image_multi (filterinterp_ctx_bwd.hip):
+"""Host mirror, exact restatement and field builder for vfi_filterinterp_backward_ori_image_multi (filterinterp_ctx_bwd.h; the float32 unit filterinterp_ctx_bwd.hip):
 the image gradient of FilterInterpolation `_ori` summed over several flows, the backward of the context warp.
 
   channels(n) / channel_groups(...)   the staged kernel's per-tile decision and the launcher's channel groups, as written in the source
@@ -21,8 +21,9 @@ from oracle.np_oracle import _fi_geometry
 from tests import bwd_tiles as bt
 
 f32 = np.float32
-SRC = "filterinterp_ctx_bwd.hip"
-CB_TW, CB_TH, CB_THREADS, CB_CH, CB_CELLS, CB_NT = (bt.constants(SRC)[n] for n in
+SRC = "filterinterp_ctx_bwd.h"              # the kernels and the launcher, templates on the gradients' storage
+UNIT = "filterinterp_ctx_bwd.hip"           # their float32 instances; restates the tile constants (read here, as ever)
+CB_TW, CB_TH, CB_THREADS, CB_CH, CB_CELLS, CB_NT = (bt.constants(UNIT)[n] for n in
                                                      ("CB_TW", "CB_TH", "CB_THREADS", "CB_CH", "CB_CELLS", "CB_NT"))
 FLOW_LABELS = ("union_sides", "one_flow")
 

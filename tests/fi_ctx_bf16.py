@@ -1,7 +1,8 @@
 """Helpers of the bfloat16 context-warp tests (vfi_filterinterp_forward_ori_multi_to_bf16 and
 vfi_filterinterp_backward_ori_image_multi_bf16, csrc/filterinterp_bf16.hip).  No test functions, nothing of the product imported.
 
-  constants() / RUNGS                 the staged kernel's #defines (read from the source) and the mirror's own rung ladder
+  constants() / RUNGS                 the staged kernel's #defines (read from the source: the unit and filterinterp_16.h) and
+                                      the mirror's own rung ladder
   takes_staged(...)                   the launcher's choice between the staged and the direct kernel, by layout
   decide(x0, y0, x1, y1, any)         the per-tile decision from the box of the moved windows: dwords per row, pitch, staged
                                       dwords, ring class ("K=2" .. "K=8", "gather", "none")
@@ -16,7 +17,7 @@ vfi_filterinterp_backward_ori_image_multi_bf16, csrc/filterinterp_bf16.hip).  No
   pipeline_spills(path)               tests/test_abi_and_host's criterion -- no scratch operation in an LDS-DMA pipeline -- applied
                                       to one assembly file
 
-The tile geometry is the fp16 kernel's (asserted by tests/test_fi_ctx_bf16_host.py), so fi_windows.build_field("f16", ...) builds
+The tile geometry is the fp16 kernel's (one set of constants and one prologue, filterinterp_16.h), so fi_windows.build_field("f16", ...) builds
 the all-class fields: its windows are moved inside the image exactly as this kernel's are.
 """
 import re
@@ -40,14 +41,14 @@ INT_MAX = 2 ** 31 - 1
 
 def constants():
     d = fw.defines(SRC)
-    return {k: d[k] for k in ("BF_TW", "BF_TH", "BF_PX", "BF_THREADS", "BF_PASS_ROWS", "BF_HDR", "BF_RING_DWORDS", "BF_RMAX",
-                              "BF_KTOP", "FI_PITCH_SKEW")}
+    return {k: d[k] for k in ("FI16_TW", "FI16_TH", "FI16_PX", "FI16_THREADS", "FI16_PASS_ROWS", "FI16_HDR", "FI16_RING_DWORDS",
+                              "FI16_RMAX", "FI16_KTOP", "FI_PITCH_SKEW")}
 
 
 def ring_geometry(K):
-    """(slots R, windows in flight D) of the instance for K dwords per thread, as bf16_run_channels computes them"""
+    """(slots R, windows in flight D) of the instance for K dwords per thread, as fi16_run_channels (filterinterp_16.h) computes them"""
     c = constants()
-    R = min(c["BF_RING_DWORDS"] // (K * c["BF_THREADS"]), c["BF_RMAX"])
+    R = min(c["FI16_RING_DWORDS"] // (K * c["FI16_THREADS"]), c["FI16_RMAX"])
     return R, R - 1
 
 
@@ -69,16 +70,16 @@ def decide(x0, y0, x1, y1, anyv):
     bh = np.where(anyv, y1 - y0 + 1, 0)
     pitch = fw.pitch_for(bw, c["FI_PITCH_SKEW"])
     n = pitch * bh
-    kmax = -(-n // c["BF_THREADS"])
+    kmax = -(-n // c["FI16_THREADS"])
     K = fw._pick(RUNGS, kmax)
-    label = np.where(~anyv, "none", np.where(kmax > c["BF_KTOP"], "gather", fw._lut("K=%d")[K])).astype(object)
+    label = np.where(~anyv, "none", np.where(kmax > c["FI16_KTOP"], "gather", fw._lut("K=%d")[K])).astype(object)
     return {"bx0": bx0, "bw": bw, "bh": bh, "pitch": pitch, "n": n, "kmax": kmax, "label": label}
 
 
 def tiles(flow, h, w):
     """per (b, tile row, tile column): 'label' and the moves of the valid pixels' windows, 'left', 'right1', 'right2' (bool arrays)"""
     c = constants()
-    th, tw = c["BF_TH"], c["BF_TW"]
+    th, tw = c["FI16_TH"], c["FI16_TW"]
     valid, ix, iy, _, _ = fw.samples(flow, h, w)
     L, T = ix - 1, iy - 1
     Lc = np.clip(L, 0, w - 4)
@@ -101,7 +102,7 @@ def features(flow, h, w):
             got.add(name)
     if (staged & ~t["edge"]).any():
         got.add("interior")
-    if w % constants()["BF_TW"] and staged[:, :, -1].any():
+    if w % constants()["FI16_TW"] and staged[:, :, -1].any():
         got.add("ragged last column")
     return got
 
@@ -111,7 +112,7 @@ def pixel_labels(flow, h, w):
     t = tiles(flow, h, w)
     c = constants()
     lab = np.where(t["edge"] & (t["label"] != "gather") & (t["label"] != "none"), t["label"] + " edge", t["label"]).astype(object)
-    return np.repeat(np.repeat(lab, c["BF_TH"], axis=1), c["BF_TW"], axis=2)[:, :h, :w]
+    return np.repeat(np.repeat(lab, c["FI16_TH"], axis=1), c["FI16_TW"], axis=2)[:, :h, :w]
 
 
 # ------------------------------------------------------------------ references

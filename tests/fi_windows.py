@@ -11,11 +11,11 @@ the GPU tests compare per class, and the classes come from this module:
                                        in which every class of all_classes(...) owns at least one tile
 
 kernels: "lds" (filterinterp_lds.hip, lean loop, fs 4), "blend" (the same kernel with the blend epilogue), "n"
-(filterinterp_lds_n.hip, fs 2 / 5 / 6), "f16" (filterinterp_f16.hip), "multi" (filterinterp_multi.hip, two flows),
-"defor" (filterinterp_defor_lds.hip, fs 4 / 6).
+(filterinterp_lds_n.hip, fs 2 / 5 / 6), "f16" (filterinterp_f16.hip; its tile, ring and ladder are filterinterp_16.h's, which
+filterinterp_bf16.hip shares), "multi" (filterinterp_multi.hip, two flows), "defor" (filterinterp_defor_lds.hip, fs 4 / 6).
 
 Every constant (tile size, threads, ring and ladder limits, thresholds, pitch skew) is read from the #defines of the
-kernel's translation unit, so an edited constant moves the mirror with it.  The rung ladders below are the mirror's own
+kernel's translation unit and of the headers it includes, so an edited constant moves the mirror with it.  The rung ladders below are the mirror's own
 statement of each dispatch chain; tests/test_fi_windows_host.py compares them with the chains in the sources.
 """
 import functools
@@ -29,6 +29,9 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 SOURCES = {"lds": "filterinterp_lds.hip", "blend": "filterinterp_lds.hip", "n": "filterinterp_lds_n.hip",
            "f16": "filterinterp_f16.hip", "multi": "filterinterp_multi.hip", "defor": "filterinterp_defor_lds.hip"}
+
+# the header of the 16-bit staged kernels: constants, tile prologue, channel loop, ladder, launch plan
+FAMILY16 = "filterinterp_16.h"
 
 f32 = np.float32
 
@@ -53,22 +56,38 @@ def _eval(expr, env):
     return int(eval(expr.replace("/", "//"), {"__builtins__": {}}, dict(env)))
 
 
+_DEFINE = r"^\s*#define\s+(\w+)[ \t]+([^\n]+)$"
+
+
+def includes(name):
+    """the project headers a file includes itself (`#include "..."`), in source order"""
+    return re.findall(r'^\s*#include\s+"([^"]+)"', source(name), flags=re.M)
+
+
 @functools.lru_cache(maxsize=None)
 def defines(name):
     """The object-like integer #defines of a translation unit: filterinterp_dev.h's (its FI_PITCH_SKEW only where the
-    unit does not define one first), then the unit's own, each evaluated in terms of the ones before it."""
+    unit, or a header the unit includes, does not define one first), then those of the unit's own headers (one level of
+    #include "..."), then the unit's own, each evaluated in terms of the ones before it."""
     env = {}
-    own = re.findall(r"^\s*#define\s+(\w+)[ \t]+([^\n]+)$", source(name), flags=re.M)
-    own_names = {k for k, _ in own}
-    for fname in ("filterinterp_dev.h", name):
-        for k, v in re.findall(r"^\s*#define\s+(\w+)[ \t]+([^\n]+)$", source(fname), flags=re.M):
-            if fname != name and k in own_names:
+    files = [h for h in includes(name) if h != "filterinterp_dev.h" and os.path.exists(os.path.join(CSRC, h))] + [name]
+    own_names = {k for f in files for k, _ in re.findall(_DEFINE, source(f), flags=re.M)}
+    for fname in ["filterinterp_dev.h"] + files:
+        for k, v in re.findall(_DEFINE, source(fname), flags=re.M):
+            if fname == "filterinterp_dev.h" and k in own_names:
                 continue
             try:
                 env[k] = _eval(v, env)
             except (ValueError, SyntaxError, NameError, TypeError):
                 pass
     return env
+
+
+def macro_body(name, macro):
+    """(parameter, body) of the one-parameter function-like macro `macro` of a file, continuation lines joined; None
+    where the file defines no such macro"""
+    m = re.search(r"^\s*#define\s+" + macro + r"\((\w+)\)((?:[^\n]*\\\n)*[^\n]*)$", source(name), flags=re.M)
+    return (m.group(1), m.group(2).replace("\\\n", "\n")) if m else None
 
 
 def _dispatch_text(name):
@@ -84,11 +103,17 @@ def _dispatch_text(name):
 
 def source_chain(name, macro):
     """The uses of `macro` in source order as (variable, op, bound, args): `if (kmax <= 2 * FI_KS) FI_RUN(2 * FI_KS)`
-    -> ("kmax", "<=", 2, (2,)); an `else` without a condition -> (None, None, None, args).  Values evaluated."""
+    -> ("kmax", "<=", 2, (2,)); an `else` without a condition -> (None, None, None, args).  Values evaluated.  Where the
+    file defines `macro` itself as a ladder over its parameter (`#define FI16_LADDER(RUN) if (kmax <= 2) RUN(2); ...`),
+    the chain is that definition's."""
     env = defines(name)
+    text = _dispatch_text(name)
+    ladder = macro_body(name, macro)
+    if ladder and re.search(r"\bif\s*\(", ladder[1]) and re.search(r"\b%s\(" % ladder[0], ladder[1]):
+        macro, text = ladder
     pat = r"(?:if\s*\(\s*(\w+)\s*(<=|==)\s*([^()]*?)\s*\)\s*)?\b" + macro + r"\(([^()]*)\)"
     out = []
-    for var, op, bound, args in re.findall(pat, _dispatch_text(name)):
+    for var, op, bound, args in re.findall(pat, text):
         vals = tuple(_eval(a, env) for a in args.split(","))
         out.append((var or None, op or None, _eval(bound, env) if bound else None, vals))
     return out
@@ -173,7 +198,7 @@ def geometry(kernel, fs=4):
     if kernel == "n":
         return d["FN_TH"], d["FN_TW"], d["FN_THREADS"], 1 - fs // 2, fs
     if kernel == "f16":
-        return d["F16_TH"], d["F16_TW"], d["F16_THREADS"], -1, 4
+        return d["FI16_TH"], d["FI16_TW"], d["FI16_THREADS"], -1, 4
     if kernel == "multi":
         return d["FM_TH"], d["FM_TW"], d["FM_THREADS"], -1, 4
     if kernel == "defor":
@@ -264,7 +289,7 @@ def decide(kernel, x0, y0, x1, y1, anyv, h, w, aligned=True, detail=None):
         bw = np.where(anyv, (x1 - bx0 + 2) >> 1, 0)
         pitch = pitch_for(bw, d["FI_PITCH_SKEW"])
         n = pitch * bh
-        kmax, ktop = _ceil(n, d["F16_THREADS"]), d["F16_KTOP"]
+        kmax, ktop = _ceil(n, d["FI16_THREADS"]), d["FI16_KTOP"]
     elif kernel == "n":
         bw = np.where(anyv, x1 - x0 + 1, 0)
         n = ((bw + 31) & ~31) * bh

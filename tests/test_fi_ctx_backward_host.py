@@ -68,6 +68,10 @@ def test_argument_errors_return_1_without_a_gpu(built):
 def test_decision_expressions_and_constants_match_the_source():
     src = " ".join(source(fc.SRC).split())
     assert (fc.CB_TW, fc.CB_TH, fc.CB_THREADS, fc.CB_CH, fc.CB_CELLS, fc.CB_NT) == (64, 8, 512, 6, 6144, 3)
+    # the unit restates the header's tile, and a differing restatement is a compile error
+    names = ("CB_TW", "CB_TH", "CB_THREADS", "CB_CH", "CB_CELLS", "CB_NT")
+    assert [bt.constants(fc.SRC)[n] for n in names] == [bt.constants(fc.UNIT)[n] for n in names]
+    assert '#pragma clang diagnostic error "-Wmacro-redefined"' in source(fc.UNIT)
     assert "const int pc = min(CB_CH, CB_CELLS / n);" in src
     assert "if (!gradacc_staged_ok(gctx) || pc == 0) {" in src
     assert "if (!fi_box_fold(box, tid, lo_x, lo_y, hi_x, hi_y)) return;" in src
@@ -128,7 +132,7 @@ def test_kernels_hold_no_scratch(built, tmp_path):
     flags = re.search(r"^HIPFLAGS\s*\?=\s*(.*)$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M).group(1)
     flags = flags.replace("$(ARCH)", "gfx950").split()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, fc.SRC), "-o", asm], check=True)
+    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, fc.UNIT), "-o", asm], check=True)
     text = open(asm).read()
     names = re.findall(r"^(_Z\S*fi_ctx_\S*):", text, flags=re.M)
     assert len(names) == 3, names

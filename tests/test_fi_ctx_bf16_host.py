@@ -1,7 +1,8 @@
 """CPU tests (`-m "not gpu"`) of the bfloat16 context warp (csrc/filterinterp_bf16.hip, tests/fi_ctx_bf16.py):
 
-  * the mirror's ladder and constants equal the dispatch chain and the expressions in the source, and the tile geometry is the
-    fp16 kernel's (so its field builder builds this kernel's fields);
+  * the mirror's ladder and constants equal the dispatch chain and the expressions in the source -- the unit and the header it
+    shares with the fp16 kernel, each shared expression in the header alone -- and the tile geometry is the fp16 kernel's (so
+    its field builder builds this kernel's fields);
   * the new symbols are declared, exported and in the ctypes table; argument errors return before any launch;
   * the counted-vmcnt pipelines of the new unit hold no scratch operation (the existing spill test's criterion);
   * with the library stubbed, cabi dispatches on the image / gradient dtype and refuses mixes, float16, a bfloat16 flow and a
@@ -35,37 +36,50 @@ f32 = np.float32
 # ------------------------------------------------------------------ 1. the mirror and the source
 
 def test_ladder_and_constants_match_the_source():
-    chain = fw.source_chain(fb.SRC, "BF_RUN")
+    # one ladder for both 16-bit kernels, in the family header; each unit runs it once
+    chain = fw.source_chain(fw.FAMILY16, "FI16_LADDER")
     assert chain == [("kmax" if op else None, op, b, (k,)) for op, b, k in fb.RUNGS]
+    units = {name: " ".join(fw.source(name).split()) for name in (fb.SRC, fw.SOURCES["f16"])}
+    assert all(u.count("FI16_LADDER(") == 1 for u in units.values())
     c = fb.constants()
-    assert c == {"BF_TW": 64, "BF_TH": 16, "BF_PX": 2, "BF_THREADS": 512, "BF_PASS_ROWS": 8, "BF_HDR": 16, "BF_RING_DWORDS": 15984,
-                 "BF_RMAX": 5, "BF_KTOP": 8, "FI_PITCH_SKEW": 16}
-    # the fp16 kernel's tile geometry, ring and ladder: fi_windows.build_field("f16", ...) serves both
-    d16 = fw.defines("filterinterp_f16.hip")
-    assert all(c["BF_" + k] == d16["F16_" + k] for k in ("TW", "TH", "PX", "THREADS", "PASS_ROWS", "HDR", "RING_DWORDS", "RMAX", "KTOP"))
-    assert c["FI_PITCH_SKEW"] == d16["FI_PITCH_SKEW"] and fb.RUNGS == fw.rungs("f16")
+    assert c == {"FI16_TW": 64, "FI16_TH": 16, "FI16_PX": 2, "FI16_THREADS": 512, "FI16_PASS_ROWS": 8, "FI16_HDR": 16,
+                 "FI16_RING_DWORDS": 15984, "FI16_RMAX": 5, "FI16_KTOP": 8, "FI_PITCH_SKEW": 16}
+    # the fp16 kernel's tile geometry, ring and ladder: one set of constants, so fi_windows.build_field("f16", ...) serves both
+    d16 = fw.defines(fw.SOURCES["f16"])
+    assert all(c[k] == d16[k] for k in c)
+    assert not [k for name in units for k in re.findall(r"#define\s+((?:F16|BF|FI16)_\w+)[ \t]+\d", fw.source(name))]
+    assert fb.RUNGS == fw.rungs("f16")
     assert [fb.ring_geometry(k) for _, _, k in fb.RUNGS] == [(5, 4), (5, 4), (5, 4), (5, 4), (3, 2)]
-    assert all(r * k * c["BF_THREADS"] <= c["BF_RING_DWORDS"] and (r - 2) * k <= 63 for k in (2, 3, 4, 6, 8) for r in [fb.ring_geometry(k)[0]])
-    src = " ".join(fw.source(fb.SRC).split())
-    for expr in ("Lc[p] = clampi(L[p], 0, w - 4);",
-                 "const int shift = L[p] - Lc[p];",
-                 "fi_box_add4(g.valid, Lc[p], T[p], bx_lo, by_lo, bx_hi, by_hi);",
+    assert all(r * k * c["FI16_THREADS"] <= c["FI16_RING_DWORDS"] and (r - 2) * k <= 63 for k in (2, 3, 4, 6, 8) for r in [fb.ring_geometry(k)[0]])
+    src = units[fb.SRC]
+    family = " ".join(fw.source(fw.FAMILY16).split())
+    # what both kernels share stands in the family header exactly once, and in neither unit
+    for expr in ("t.Lc = clampi(t.L, 0, w - 4);",
+                 "fi_box_add4(g.valid, t.Lc, t.T, box.bx_lo, box.by_lo, box.bx_hi, box.by_hi);",
                  "const int bx0 = any_valid ? box[0] & ~1 : 0, by0 = box[1];",
                  "const int bw = any_valid ? (box[2] - bx0 + 2) >> 1 : 0;",
                  "const int bh = any_valid ? box[3] - by0 + 1 : 0;",
                  "const int pitch = fi_pitch_for(bw);",
-                 "const int kmax = (n + BF_THREADS - 1) / BF_THREADS;",
-                 "if (kmax > BF_KTOP) {",
-                 "moved = moved || (g.valid && shift != 0);",
                  "const bool staged = filter_channels == 16 && w >= 4 && ((s1.h | s1.c | s1.b) & 1) == 0 && "
                  "(reinterpret_cast<uintptr_t>(input1) & 3) == 0 && (int64_t)h * s1.h * 2 < INT_MAX;",
-                 "const FiSplit split = fi_channel_split(ntiles, channel, 4.3);",
+                 "const FiSplit split = fi_channel_split(ntiles, channel, 4.3);"):
+        assert family.count(expr) == 1 and not any(expr in u for u in units.values()), expr
+    # what changes a kernel's code when a helper forms it stays written out, the same in both units
+    for expr in ("const int n = win.pitch * win.bh;",
+                 "const int kmax = (n + FI16_THREADS - 1) / FI16_THREADS;",
+                 "if (kmax > FI16_KTOP) {"):
+        assert all(u.count(expr) == 1 for u in units.values()) and expr not in family, expr
+    # this kernel's own
+    for expr in ("const int shift = L[p] - Lc[p];",
+                 "moved = moved || (g.valid && shift != 0);",
                  "if (so.h != s1.h || batch > 65535) return VFI_ERR_SHAPE;"):
         assert expr in src, expr
-    # the arithmetic is the float32 kernels': fi4_pixel on widened taps, no folded weights
+    # the arithmetic is the float32 kernels': fi4_pixel on widened taps, no folded weights; the family header knows no format
     assert src.count("fi4_pixel(v, px[p].f, px[p].alpha, px[p].beta)") == 2 and "v_fma_mix" not in src and "__half" not in src
+    assert not [t for t in ("__half", "v_fma_mix", "bf16_", "fi4_pixel") if t in family]
     # the backward instantiates the float32 call's templates
-    assert "backward_image_multi<bf16_t>(" in src and '#include "filterinterp_ctx_bwd.hip"' in fw.source(fb.SRC)
+    assert "backward_image_multi<bf16_t>(" in src and '#include "filterinterp_ctx_bwd.h"' in fw.source(fb.SRC)
+    assert "backward_image_multi<float>(" in fw.source("filterinterp_ctx_bwd.hip") and "FI_CTX_BWD" not in fw.source("filterinterp_ctx_bwd.h")
 
 
 def test_hand_worked_tiles():

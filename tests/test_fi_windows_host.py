@@ -6,13 +6,15 @@ import pytest
 
 from tests import fi_windows as fw
 
-CHAINS = [("lds", "FI_RUN"), ("n", "FN_RUN"), ("f16", "F16_RUN"), ("multi", "FM_RUN_PLAIN"), ("defor", "DF_RUN")]
+CHAINS = [("lds", "FI_RUN"), ("n", "FN_RUN"), ("f16", "FI16_LADDER"), ("multi", "FM_RUN_PLAIN"), ("defor", "DF_RUN")]
+# where a kernel's ladder and launch plan live, when not in its own unit
+SHARED = {"f16": fw.FAMILY16}
 
 
 @pytest.mark.parametrize("kernel,macro", CHAINS)
 def test_rung_lists_match_the_sources(kernel, macro):
     """Adding, removing or moving a rung in a kernel fails here until the mirror follows."""
-    got = fw.source_chain(fw.SOURCES[kernel], macro)
+    got = fw.source_chain(SHARED.get(kernel, fw.SOURCES[kernel]), macro)
     assert all(var in (None, "kmax") for var, _, _, _ in got), got
     assert [(op, b, args[0]) for _, op, b, args in got] == fw.rungs(kernel)
     assert got[-1][1] is None and all(op is not None for _, op, _, _ in got[:-1])
@@ -51,7 +53,7 @@ def test_shared_window_classes_match_the_source():
 
 def test_channel_split_arguments_match_the_sources():
     for kernel, expr in fw.SPLIT_PROLOGUE.items():
-        assert fw.source_expr(fw.SOURCES[kernel], r"fi_channel_split\(ntiles, channel, (.*?)\);") == expr, kernel
+        assert fw.source_expr(SHARED.get(kernel, fw.SOURCES[kernel]), r"fi_channel_split\(ntiles, channel, (.*?)\);") == expr, kernel
     # the blend epilogue keeps the channels in one workgroup
     assert "blend.out ? FiSplit{channel, 1}" in fw.source(fw.SOURCES["blend"])
     # a frame of the GPU file's channel-split case: more than one group, and a short last one
@@ -60,7 +62,8 @@ def test_channel_split_arguments_match_the_sources():
 
 
 def test_constants_come_from_each_translation_unit():
-    assert fw.defines(fw.SOURCES["f16"])["FI_PITCH_SKEW"] == 16
+    assert fw.defines(fw.SOURCES["f16"])["FI_PITCH_SKEW"] == 16 and fw.defines("filterinterp_bf16.hip")["FI_PITCH_SKEW"] == 16
+    assert fw.FAMILY16 in fw.includes(fw.SOURCES["f16"]) and fw.FAMILY16 in fw.includes("filterinterp_bf16.hip")
     assert fw.defines(fw.SOURCES["lds"])["FI_PITCH_SKEW"] == 0
     d = fw.defines(fw.SOURCES["lds"])
     assert d["FI_THREADS"] == d["FI_TW"] * d["FI_TH"] // d["FI_PX"] and d["FI_KTOP"] == 15 * d["FI_KS"]

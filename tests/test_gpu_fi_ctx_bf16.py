@@ -118,7 +118,7 @@ def test_long_channel_loop(torch_mod, cabi, oracle):
     torch = torch_mod
     B, C, h, w = 1, 196, 24, 72
     cu = torch.cuda.get_device_properties(0).multi_processor_count
-    ntiles = -(-w // fb.constants()["BF_TW"]) * -(-h // fb.constants()["BF_TH"]) * B
+    ntiles = -(-w // fb.constants()["FI16_TW"]) * -(-h // fb.constants()["FI16_TH"]) * B
     assert fw.fi_channel_split(ntiles, C, 4.3, cu)[1] > 1
     rng = np.random.default_rng(196)
     flow = (np.round(rng.uniform(-2.5, 2.5, (B, 2, h, w)) * 16) / 16).astype(f32)

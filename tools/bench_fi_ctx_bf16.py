@@ -15,7 +15,7 @@ bytes of the bfloat16 forward (the context read once per offset and each output 
 4) over the median time.  Prints one block per shape, then a JSON line; `bf16_faster` says whether the bfloat16 path beat the
 composition at that shape.
 
-    python tools/bench_fi_ctx_bf16.py [--reps 7] [--iters 5] [--warmup 2]
+    python tools/bench_fi_ctx_bf16.py [--reps 7] [--iters 5] [--warmup 2] [--lib <pkg>/lib_vX/libvfi_hip.so]
 """
 import argparse
 import json
@@ -28,6 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import vfidkr_amd  # noqa: E402,F401
+if "--lib" in sys.argv:         # a variant build of the library (tools/mkvariant.sh)
+    vfidkr_amd.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 from vfidkr_amd import cabi, fused  # noqa: E402
 
 C = 196
@@ -93,6 +95,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--lib", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fi_ctx_bf16.py needs a GPU")
