@@ -602,6 +602,35 @@ int vfi_filterinterp_blend_backward(const float* ref0, const float* ref2,
                                     vfi_strides s_ref, vfi_strides s_flow, vfi_strides s_filt, vfi_strides s_grad,
                                     vfi_stream_t stream);
 
+/* The "head" of rectifyNet's input on bfloat16 storage, for a network under bfloat16 autocast: one launch writes the
+ * 3 * channel + 4 + 2 * filter_channels consecutive channels blend, out0, out2, flow0, flow2, filt0, filt2 (the order of the
+ * reference's torch.cat, networks/DAIN_slowmotion.py:177-181; 45 channels at channel = 3, filter_channels = 16) of head_bf16,
+ * a bfloat16 tensor with strides s_head in bfloat16 elements -- typically the first channels of the network's wider input,
+ * whose context channels vfi_filterinterp_forward_ori_multi_to_bf16 fills -- and, where blend_f32 is not NULL, the blend as
+ * float32 with strides s_blend.  All inputs are float32, with the meaning and the pairwise shared strides of
+ * vfi_filterinterp_blend_forward.
+ * Bits: with blend, out0, out2 the float32 values vfi_filterinterp_blend_forward writes for the same inputs, blend_f32 is
+ * that blend, and the head holds bf16_rne (round to nearest even, once) of blend, out0, out2 and of every flow and filter
+ * value.  The blend is formed from the UNROUNDED out0 and out2, its two products rounded separately and not contracted:
+ * both sides' values of a pixel are in registers when it is formed, nothing is read back.  So the head equals, bit for bit,
+ * torch.cat((blend, out0, out2, flow0, flow2, filt0, filt2), 1).to(torch.bfloat16); NaN stays NaN at the same positions
+ * (payloads are not specified); an invalid pixel copies the frame's value through, rounded.
+ * Layouts: w stride 1 everywhere; s_head.h == s_ref.h (else VFI_ERR_SHAPE: the rule of the entry that fills the rest of the
+ * buffer), s_head.b and s_head.c free; head_bf16 needs 2-byte alignment only.  A lane owns two horizontally adjacent pixels:
+ * where every row of the flows, the filters and blend_f32 starts 8-byte aligned and every row of the head 4-byte aligned
+ * (even strides, aligned bases) they are read and written as pairs, otherwise element by element, with the same bits.
+ * Any filter_channels vfi_filterinterp_blend_forward accepts, any channel >= 1, batch <= 65535.  The destinations must not
+ * overlap the inputs or each other (not checked).  Every argument is checked before the launch. */
+int vfi_rectify_head_forward_bf16(const float* ref0, const float* ref2,
+                                  const float* flow0, const float* flow2,
+                                  const float* filt0, const float* filt2,
+                                  void* head_bf16, float* blend_f32,
+                                  int batch, int channel, int h, int w, int filter_channels,
+                                  float w0, float w2,
+                                  vfi_strides s_ref, vfi_strides s_flow, vfi_strides s_filt, vfi_strides s_head,
+                                  vfi_strides s_blend,
+                                  vfi_stream_t stream);
+
 /* PWCDCNet.warp (PWCNet/PWCNet.py:159-199): output = grid_sample(x, grid(flow)) * mask, mask = 1
  * where grid_sample(ones, grid) >= 0.9999 else 0; bilinear, zeros padding.  align_corners: 1 = the
  * grid_sample of torch <= 1.2 the reference was written for, 0 = the default of torch >= 1.3. */

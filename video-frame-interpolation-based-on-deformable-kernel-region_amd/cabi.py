@@ -88,6 +88,8 @@ SIGNATURES = {
                                        Strides, Strides, _p],
     "vfi_filterinterp_blend_backward": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
                                         _f, _f, Strides, Strides, Strides, Strides, _p],
+    "vfi_rectify_head_forward_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, Strides, Strides, Strides,
+                                      Strides, Strides, _p],
     "vfi_pwc_warp_forward": [_p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_backward": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, Strides, _p],
     "vfi_pwc_warp_forward_bf16": [_p, _p, _i, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
@@ -997,6 +999,33 @@ def filterinterp_blend_forward(ref0, ref2, flow0, flow2, filt0, filt2, blend, ou
             _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), _ptr(blend),
             _ptr(out0) if out0 is not None else null, _ptr(out2) if out2 is not None else null, b, c, h, w,
             filt0.size(1), w0, w2, _st(ref0), _st(flow0), _st(filt0), _st(blend), _stream(ref0)))
+
+
+def rectify_head_forward_bf16(ref0, ref2, flow0, flow2, filt0, filt2, head, blend, w0, w2):
+    """The first 3 C + 4 + 2 filter channels of a bfloat16 rectify buffer in one launch (vfi_rectify_head_forward_bf16): head
+    (bfloat16, [B, 3 C + 4 + 2 filter channels, H, W], typically buf[:, :45]) receives bf16_rne of blend, out0, out2 of
+    filterinterp_blend_forward and of the flows and filters; blend (float32, [B, C, H, W], or None) the unrounded blend.
+    The inputs are float32.  The head has w stride 1 and the frames' row stride -- anything else is refused here (1), before the
+    call; its batch and channel strides are free, and it needs 2-byte alignment only."""
+    dims = _fi_checks(ref0, flow0, filt0, None)
+    if dims is None or not (_same_strides(ref0, ref2) and _same_strides(flow0, flow2) and _same_strides(filt0, filt2)):
+        return 1
+    b, c, h, w = dims
+    if not _fi_filter_ok(ref0, filt0) or head.dim() != 4 or tuple(head.shape) != (b, 3 * c + 4 + 2 * filt0.size(1), h, w) or \
+            head.stride(3) != 1 or (h != 1 and head.stride(2) != ref0.stride(2)):      # (a one-row tensor's row stride addresses nothing)
+        return 1
+    if blend is not None and (blend.shape != ref0.shape or blend.stride(3) != 1):
+        return 1
+    for t in (ref0, ref2, flow0, flow2, filt0, filt2) + (() if blend is None else (blend,)):
+        _dev(t)
+    _dev(head, torch.bfloat16)
+    sh = _st(head)
+    sh.h = ref0.stride(2)
+    with torch.cuda.device(ref0.device):
+        return _finish(lib().vfi_rectify_head_forward_bf16(
+            _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), _ptr(head),
+            _ptr(blend) if blend is not None else ctypes.c_void_p(0), b, c, h, w, filt0.size(1), w0, w2, _st(ref0), _st(flow0),
+            _st(filt0), sh, _st(blend if blend is not None else ref0), _stream(ref0)))
 
 
 def filterinterp_blend_backward(ref0, ref2, flow0, flow2, filt0, filt2, grad_blend, grad_out0, grad_out2, w0, w2,

@@ -287,4 +287,27 @@ __device__ __forceinline__ void quadrants_generic(const float* __restrict__ plan
     q[0] = TL; q[1] = TR; q[2] = BL; q[3] = BR;
 }
 
+// ---- the fused FilterInterpolate of both frames (glue.hip, rectify_head_bf16.hip)
+
+// one side's pixel geometry (fi_geom) and window corner, from the pixel's flow in registers or from memory
+struct FiSide {
+    bool valid;
+    int L, T, ix, iy;
+    float alpha, beta;
+};
+__device__ __forceinline__ FiSide fi_side(float fx, float fy, int x, int y, int w, int h, int fs, bool inimg = true) {
+    const FiGeom g = fi_geom(fx, fy, x, y, w, h, inimg);
+    return FiSide{g.valid, g.ix + 1 - fs / 2, g.iy + 1 - fs / 2, g.ix, g.iy, g.alpha, g.beta};
+}
+__device__ __forceinline__ FiSide fi_side(const float* __restrict__ flow, int64_t cstride, int x, int y, int w, int h, int fs) {
+    return fi_side(flow[0], flow[cstride], x, y, w, h, fs);
+}
+__device__ __forceinline__ float fi_side_value(const FiSide& s, const float* __restrict__ plane, const float* __restrict__ fpx,
+                                               int64_t fcs, int hs, int h, int w, int fs, int x, int y) {
+    if (!s.valid) return plane[(int64_t)y * hs + x];       // copy-through (:2814-2818)
+    float q[4];
+    quadrants_generic(plane, fpx, fcs, hs, h, w, fs, s.L, s.T, s.ix, s.iy, q);
+    return blend4(s.alpha, s.beta, q[0], q[1], q[2], q[3]);
+}
+
 }  // namespace vfi

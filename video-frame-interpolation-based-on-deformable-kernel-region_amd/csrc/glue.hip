@@ -16,23 +16,7 @@ namespace vfi {
 
 // ------------------------------------------------------------------ FilterInterpolate x2 + blend
 
-// one side's pixel geometry (fi_geom) and window corner
-struct FiSide {
-    bool valid;
-    int L, T, ix, iy;
-    float alpha, beta;
-};
-__device__ __forceinline__ FiSide fi_side(const float* __restrict__ flow, int64_t cstride, int x, int y, int w, int h, int fs) {
-    const FiGeom g = fi_geom(flow[0], flow[cstride], x, y, w, h);
-    return FiSide{g.valid, g.ix + 1 - fs / 2, g.iy + 1 - fs / 2, g.ix, g.iy, g.alpha, g.beta};
-}
-__device__ __forceinline__ float fi_side_value(const FiSide& s, const float* __restrict__ plane, const float* __restrict__ fpx,
-                                               int64_t fcs, int hs, int h, int w, int fs, int x, int y) {
-    if (!s.valid) return plane[(int64_t)y * hs + x];       // copy-through (:2814-2818)
-    float q[4];
-    quadrants_generic(plane, fpx, fcs, hs, h, w, fs, s.L, s.T, s.ix, s.iy, q);
-    return blend4(s.alpha, s.beta, q[0], q[1], q[2], q[3]);
-}
+// (one side's pixel geometry and value, FiSide / fi_side / fi_side_value: filterinterp_dev.h, shared with rectify_head_bf16.hip)
 
 // out0 = FI(ref0, flow0, filt0), out2 = FI(ref2, flow2, filt2), blend = out0 * w0 + out2 * w2 with the
 // two products rounded separately (torch evaluates a*(1-t) + b*t as three elementwise ops)

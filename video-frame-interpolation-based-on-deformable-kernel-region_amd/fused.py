@@ -17,6 +17,8 @@ the library for all time offsets (vfi_flow_upsample4_backward, vfi_[depth]flowpr
 `rectify_inputs` is the end of the synthesis stage in one call: `FilterInterpolate`, `FilterInterpolate_ctx_all` and the `torch.cat`
 that builds rectifyNet's input, with the warps written straight into that input (vfi_filterinterp_forward_ori_multi_to) and one
 autograd Function over all time offsets.
+With dtype=torch.bfloat16 that input is a bfloat16 tensor for a network under bfloat16 autocast: one vfi_rectify_head_forward_bf16
+launch per time offset writes its first 45 channels and the float32 `cur_output`, the bfloat16 context warp the rest.
 `FilterInterpolate_ctx_all` and `FilterInterpolate_ctx` train the context network: the context tensors get the image
 gradient of every time offset from one call per direction (vfi_filterinterp_backward_ori_image_multi), and flows and
 filter get none, because the reference detaches them on this path.  The rest (the frame glue) is inference only."""
@@ -438,26 +440,119 @@ def _ch(t, rng):
     return t[:, rng[0]:rng[1]]
 
 
-def _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2):
-    """the T buffers, every channel written: the frames' kernel into 0-8, one multi-flow call per direction into the context
-    slices of all T buffers, copy_ for the flows and filters"""
+def _rectify_buffers(ref0, filt0, ctx0, ctx2, time_offsets, off0, off2, dtype):
+    """the argument checks of both launches, then the T buffers (uninitialised) and the channel map"""
     if (ctx0 is None) != (ctx2 is None):
         raise RuntimeError("rectify_inputs: ctx0 and ctx2 are given together or not at all")
     b, c, h, w = ref0.shape
     if c != 3 or len(off0) != len(time_offsets) or len(off2) != len(time_offsets):
         raise RuntimeError("rectify_inputs: 3-channel frames and one flow per direction and time offset")
     m = rectify_channels(filt0.size(1), None if ctx0 is None else ctx0.size(1))
-    bufs = [torch.empty((b, m["total"], h, w), device=ref0.device, dtype=torch.float32) for _ in time_offsets]
+    return [torch.empty((b, m["total"], h, w), device=ref0.device, dtype=dtype) for _ in time_offsets], m
+
+
+def _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2):
+    """the T buffers, every channel written: the frames' kernel into 0-8, one multi-flow call per direction into the context
+    slices of all T buffers, copy_ for the flows and filters"""
+    bufs, m = _rectify_buffers(ref0, filt0, ctx0, ctx2, time_offsets, off0, off2, torch.float32)
     for buf, t, f0, f2 in zip(bufs, time_offsets, off0, off2):
         _check(cabi.filterinterp_blend_forward(ref0, ref2, f0, f2, filt0, filt2, _ch(buf, m["cur_output"]), _ch(buf, m["ref0"]),
                                                _ch(buf, m["ref2"]), float(1.0 - t), float(t)), "filterinterp_blend_forward")
         for name, src in (("offset0", f0), ("offset1", f2), ("filter0", filt0), ("filter1", filt2)):
             _ch(buf, m[name]).copy_(src)
+    _rectify_ctx_launch(bufs, m, filt0, filt2, ctx0, ctx2, off0, off2)
+    return bufs, m
+
+
+def _rectify_ctx_launch(bufs, m, filt0, filt2, ctx0, ctx2, off0, off2):
+    """one multi-flow call per direction into the context slices of all T buffers, in the buffers' dtype"""
     for name, image, flows, filt in (("ctx0", ctx0, off0, filt0), ("ctx2", ctx2, off2, filt2)):
         if image is not None:
             _check(cabi.filterinterp_forward_ori_multi_to(image, list(flows), filt, [_ch(buf, m[name]) for buf in bufs]),
                    "filterinterp_forward_ori_multi_to")
-    return bufs, m
+
+
+def _rectify_launch_bf16(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2):
+    """the T bfloat16 buffers and the T dense float32 blends, every element written by a kernel: ONE head launch per time
+    offset (vfi_rectify_head_forward_bf16: channels 0-44 and the float32 blend), one multi-flow call per direction into the
+    context slices of all T buffers.  No copy_, no cast."""
+    bufs, m = _rectify_buffers(ref0, filt0, ctx0, ctx2, time_offsets, off0, off2, torch.bfloat16)
+    curs = [torch.empty(ref0.shape, device=ref0.device, dtype=torch.float32) for _ in time_offsets]
+    head = (0, m["filter1"][1])
+    for buf, cur, t, f0, f2 in zip(bufs, curs, time_offsets, off0, off2):
+        _check(cabi.rectify_head_forward_bf16(ref0, ref2, f0, f2, filt0, filt2, _ch(buf, head), cur, float(1.0 - t), float(t)),
+               "rectify_head_forward_bf16")
+    _rectify_ctx_launch(bufs, m, filt0, filt2, ctx0, ctx2, off0, off2)
+    return bufs, curs, m
+
+
+def _rectify_forward(ctx, bf16, ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, *offsets):
+    n = len(time_offsets)
+    off0, off2 = offsets[:n], offsets[n:]
+    if bf16:
+        bufs, curs, m = _rectify_launch_bf16(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2)
+    else:
+        bufs, m = _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2)
+        curs = [_ch(buf, m["cur_output"]).clone() for buf in bufs]
+    ctx.save_for_backward(ref0, ref2, filt0, filt2, *offsets)
+    ctx.time_offsets, ctx.map = tuple(time_offsets), m
+    ctx.ctx_layouts = [None if t is None else (t.shape, t.stride(), t.dtype) for t in (ctx0, ctx2)]
+    ctx.set_materialize_grads(False)                   # (an unused output is an absent term, not a tensor of zeros)
+    return (*bufs, *curs)
+
+
+def _rectify_backward(ctx, bf16, *grads):
+    """bf16: the buffers' gradients are bfloat16 (the cur_output gradients float32).  The nine frame channels and the slices
+    that passed through are widened (exactly) where they are used; the context channels are read in place, as bfloat16."""
+    ref0, ref2, filt0, filt2 = ctx.saved_tensors[:4]
+    offsets = ctx.saved_tensors[4:]
+    n, m = len(ctx.time_offsets), ctx.map
+    off = (offsets[:n], offsets[n:])
+    g_buf, g_cur = grads[:n], grads[n:]
+    need = ctx.needs_input_grad
+    like = lambda t: torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)      # noqa: E731
+    f32 = (lambda g, name: _ch(g, m[name]).float()) if bf16 else (lambda g, name: _ch(g, m[name]))
+    # ---- frames, flows, filters: one blend backward per time offset that received a gradient; its flow and filter terms,
+    # then the slice of the buffer's gradient that passed through.  Sums run over t ascending, the kernel's term first.
+    terms = {"ref0": [], "ref2": [], "filt0": [], "filt2": []}
+    g_off = [[None] * n, [None] * n]
+    for t in range(n):
+        gb, gc = g_buf[t], g_cur[t]
+        if gb is None and gc is None:
+            continue
+        g_blend = gc if gb is None else (f32(gb, "cur_output") if gc is None else f32(gb, "cur_output") + gc)
+        g_blend, g_out0, g_out2 = _grad_layout([g_blend, None if gb is None else f32(gb, "ref0"),
+                                                None if gb is None else f32(gb, "ref2")])
+        outs = [like(x) if nd else None for x, nd in
+                ((ref0, need[0]), (ref2, need[1]), (off[0][t], need[7 + t]), (off[1][t], need[7 + n + t]), (filt0, need[2]),
+                 (filt2, need[3]))]
+        if any(o is not None for o in outs):
+            w0, w2 = float(1.0 - ctx.time_offsets[t]), float(ctx.time_offsets[t])
+            _check(cabi.filterinterp_blend_backward(ref0, ref2, off[0][t], off[1][t], filt0, filt2, g_blend, g_out0, g_out2,
+                                                    w0, w2, *outs), "filterinterp_blend_backward")
+        gr0, gr2, gf0, gf2, gk0, gk2 = outs
+        for d, gf in ((0, gf0), (1, gf2)):
+            if gf is not None:
+                g_off[d][t] = gf if gb is None else gf + f32(gb, "offset%d" % d)
+        for key, kernel, through in (("ref0", gr0, None), ("ref2", gr2, None), ("filt0", gk0, "filter0"), ("filt2", gk2, "filter1")):
+            if kernel is not None:
+                terms[key].append(kernel)
+                if through is not None and gb is not None:
+                    terms[key].append(f32(gb, through))
+    total = {k: (_add_in_order(v) if v else None) for k, v in terms.items()}
+    # ---- context tensors: one image-only call per direction over the buffers that received a gradient, which reads the
+    # context channels of those gradients where they lie
+    g_ctx = [None, None]
+    live = [t for t in range(n) if g_buf[t] is not None]
+    for d, name in ((0, "ctx0"), (1, "ctx2")):
+        if ctx.ctx_layouts[d] is None or not need[4 + d] or not live:
+            continue
+        gs = _grad_layout([_ch(g_buf[t], m[name]) for t in live])
+        shape, stride, dtype = ctx.ctx_layouts[d]
+        g_ctx[d] = torch.empty_strided(shape, stride, dtype=dtype, device=gs[0].device)      # (written in full)
+        _check(cabi.filterinterp_backward_ori_image_multi([off[d][t] for t in live], (filt0, filt2)[d], gs, g_ctx[d]),
+               "filterinterp_backward_ori_image_multi")
+    return (total["ref0"], total["ref2"], total["filt0"], total["filt2"], g_ctx[0], g_ctx[1], None, *g_off[0], *g_off[1])
 
 
 class _RectifyInputs(torch.autograd.Function):
@@ -467,70 +562,45 @@ class _RectifyInputs(torch.autograd.Function):
     their values)."""
 
     @staticmethod
-    def forward(ctx, ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, *offsets):
-        n = len(time_offsets)
-        off0, off2 = offsets[:n], offsets[n:]
-        bufs, m = _rectify_launch(ref0, ref2, filt0, filt2, ctx0, ctx2, time_offsets, off0, off2)
-        ctx.save_for_backward(ref0, ref2, filt0, filt2, *offsets)
-        ctx.time_offsets, ctx.map = tuple(time_offsets), m
-        ctx.ctx_layouts = [None if t is None else (t.shape, t.stride()) for t in (ctx0, ctx2)]
-        ctx.set_materialize_grads(False)                   # (an unused output is an absent term, not a tensor of zeros)
-        return (*bufs, *[_ch(buf, m["cur_output"]).clone() for buf in bufs])
+    def forward(ctx, *args):
+        return _rectify_forward(ctx, False, *args)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        ref0, ref2, filt0, filt2 = ctx.saved_tensors[:4]
-        offsets = ctx.saved_tensors[4:]
-        n, m = len(ctx.time_offsets), ctx.map
-        off = (offsets[:n], offsets[n:])
-        g_buf, g_cur = grads[:n], grads[n:]
-        need = ctx.needs_input_grad
-        like = lambda t: torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)      # noqa: E731
-        # ---- frames, flows, filters: one blend backward per time offset that received a gradient; its flow and filter terms,
-        # then the slice of the buffer's gradient that passed through.  Sums run over t ascending, the kernel's term first.
-        terms = {"ref0": [], "ref2": [], "filt0": [], "filt2": []}
-        g_off = [[None] * n, [None] * n]
-        for t in range(n):
-            gb, gc = g_buf[t], g_cur[t]
-            if gb is None and gc is None:
-                continue
-            g_blend = gc if gb is None else (_ch(gb, m["cur_output"]) if gc is None else _ch(gb, m["cur_output"]) + gc)
-            g_blend, g_out0, g_out2 = _grad_layout([g_blend, None if gb is None else _ch(gb, m["ref0"]),
-                                                    None if gb is None else _ch(gb, m["ref2"])])
-            outs = [like(x) if nd else None for x, nd in
-                    ((ref0, need[0]), (ref2, need[1]), (off[0][t], need[7 + t]), (off[1][t], need[7 + n + t]), (filt0, need[2]),
-                     (filt2, need[3]))]
-            if any(o is not None for o in outs):
-                w0, w2 = float(1.0 - ctx.time_offsets[t]), float(ctx.time_offsets[t])
-                _check(cabi.filterinterp_blend_backward(ref0, ref2, off[0][t], off[1][t], filt0, filt2, g_blend, g_out0, g_out2,
-                                                        w0, w2, *outs), "filterinterp_blend_backward")
-            gr0, gr2, gf0, gf2, gk0, gk2 = outs
-            for d, gf in ((0, gf0), (1, gf2)):
-                if gf is not None:
-                    g_off[d][t] = gf if gb is None else gf + _ch(gb, m["offset%d" % d])
-            for key, kernel, through in (("ref0", gr0, None), ("ref2", gr2, None), ("filt0", gk0, "filter0"), ("filt2", gk2, "filter1")):
-                if kernel is not None:
-                    terms[key].append(kernel)
-                    if through is not None and gb is not None:
-                        terms[key].append(_ch(gb, m[through]))
-        total = {k: (_add_in_order(v) if v else None) for k, v in terms.items()}
-        # ---- context tensors: one image-only call per direction over the buffers that received a gradient, which reads the
-        # context channels of those gradients where they lie
-        g_ctx = [None, None]
-        live = [t for t in range(n) if g_buf[t] is not None]
-        for d, name in ((0, "ctx0"), (1, "ctx2")):
-            if ctx.ctx_layouts[d] is None or not need[4 + d] or not live:
-                continue
-            gs = _grad_layout([_ch(g_buf[t], m[name]) for t in live])
-            shape, stride = ctx.ctx_layouts[d]
-            g_ctx[d] = torch.empty_strided(shape, stride, dtype=torch.float32, device=gs[0].device)      # (written in full)
-            _check(cabi.filterinterp_backward_ori_image_multi([off[d][t] for t in live], (filt0, filt2)[d], gs, g_ctx[d]),
-                   "filterinterp_backward_ori_image_multi")
-        return (total["ref0"], total["ref2"], total["filt0"], total["filt2"], g_ctx[0], g_ctx[1], None, *g_off[0], *g_off[1])
+        return _rectify_backward(ctx, False, *grads)
 
 
-def rectify_inputs(ref0, ref2, offsets, filter, filter_size2, time_offsets, ctx0=None, ctx2=None):
+class _RectifyInputsBf16(torch.autograd.Function):
+    """`_RectifyInputs` with bfloat16 buffers (and bfloat16 context tensors): the same arguments, outputs, saved tensors and
+    gradient bookkeeping; the T `cur_output` tensors stay float32, written by the head kernel beside the rounded channels.
+    The buffers' gradients arrive as bfloat16, the context gradients leave as bfloat16, everything else is float32."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _rectify_forward(ctx, True, *args)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        return _rectify_backward(ctx, True, *grads)
+
+
+def _rectify_dtypes(bf16, frames, floats, contexts):
+    """the dtype rules of `rectify_inputs`, checked before any launch: float32 frames; float32 flows and filters, for a
+    bfloat16 buffer bfloat16 ones too; context tensors of the buffer's dtype"""
+    def must_be(t, *dtypes):
+        if t.dtype not in dtypes:
+            raise RuntimeError("rectify_inputs: tensors must be %s" % " or ".join(str(d).replace("torch.", "") for d in dtypes))
+    for t in frames:
+        must_be(t, torch.float32)
+    for t in floats:
+        must_be(t, *((torch.float32, torch.bfloat16) if bf16 else (torch.float32,)))
+    for t in contexts:
+        must_be(t, torch.bfloat16 if bf16 else torch.float32)
+
+
+def rectify_inputs(ref0, ref2, offsets, filter, filter_size2, time_offsets, ctx0=None, ctx2=None, dtype=None):
     """The end of the synthesis stage for every time offset of a step (networks/DAIN_slowmotion.py:167-182; without context
     tensors networks/DAIN.py:255-269): `FilterInterpolate`, `FilterInterpolate_ctx` and the `torch.cat` that builds
     rectifyNet's input, with the warps written straight into that input.  offsets[d][t] is the projected flow of direction
@@ -550,16 +620,38 @@ def rectify_inputs(ref0, ref2, offsets, filter, filter_size2, time_offsets, ctx0
     filters no gradient.  An output the loss did not use is an absent term.
     Bit-equal, backward: a flow's gradient is kernel term + passed-through slice; a filter's or frame's is the left-to-right
     sum over t ascending of (kernel term of t, passed-through slice of t).  For one time offset each sum has at most two
-    terms, so every gradient equals autograd's through `torch.cat` over the functions above, bit for bit."""
+    terms, so every gradient equals autograd's through `torch.cat` over the functions above, bit for bit.
+    dtype: None -- everything float32, as described above -- or torch.bfloat16, for a rectifyNet under
+    `torch.autocast(dtype=torch.bfloat16)`: rectify_input_t is then a BFLOAT16 tensor, written in place and once.  Frames
+    are float32; flows and filters float32 or bfloat16 (widened once, exactly, outside the autograd Function: autograd rounds
+    their gradient back); context tensors bfloat16, or absent.  Every other dtype is refused before any launch.  Per time
+    offset ONE vfi_rectify_head_forward_bf16 launch writes channels 0-44 and cur_output_t; one
+    vfi_filterinterp_forward_ori_multi_to_bf16 call per direction writes the context channels of all buffers; there is no
+    copy_, no cast and no torch.cat.  cur_output_t is float32 and a tensor of its own, in inference too: the reference adds
+    it to rectifyNet's output and puts it into the loss, where a view of the rounded channels would have lost 16 bits.
+    Bit-equal: rectify_input_t is the float32 call's (the contexts entering through `.float()`) `.to(torch.bfloat16)`,
+    cur_output_t the float32 call's; every gradient is what autograd gives through that graph -- float32 for frames, flows
+    and filters (the buffers' bfloat16 gradients widened where they are used), bfloat16 for the context tensors, from one
+    vfi_filterinterp_backward_ori_image_multi_bf16 call per direction that reads the gradients' context channels in place."""
     assert filter[0].size(1) == filter_size2
+    if dtype is not None and dtype != torch.bfloat16:
+        raise RuntimeError("rectify_inputs: dtype is None (float32) or torch.bfloat16")
+    bf16 = dtype is not None
     time_offsets = [float(t) for t in time_offsets]
-    off0, off2 = list(offsets[0]), list(offsets[1])
-    tensors = [ref0, ref2, filter[0], filter[1], *off0, *off2] + [t for t in (ctx0, ctx2) if t is not None]
+    off0, off2, filt = list(offsets[0]), list(offsets[1]), list(filter[:2])
+    _rectify_dtypes(bf16, (ref0, ref2), (*filt, *off0, *off2), [t for t in (ctx0, ctx2) if t is not None])
+    if bf16:
+        off0, off2, filt = [_f32_once(o) for o in off0], [_f32_once(o) for o in off2], [_f32_once(f) for f in filt]
+    n = len(time_offsets)
+    tensors = [ref0, ref2, *filt, *off0, *off2] + [t for t in (ctx0, ctx2) if t is not None]
     if _wants_grad(*tensors):
-        outs = _RectifyInputs.apply(ref0, ref2, filter[0], filter[1], ctx0, ctx2, tuple(time_offsets), *off0, *off2)
-        n = len(time_offsets)
+        fn = _RectifyInputsBf16 if bf16 else _RectifyInputs
+        outs = fn.apply(ref0, ref2, filt[0], filt[1], ctx0, ctx2, tuple(time_offsets), *off0, *off2)
         return list(zip(outs[:n], outs[n:]))
-    bufs, m = _rectify_launch(ref0, ref2, filter[0], filter[1], ctx0, ctx2, time_offsets, off0, off2)
+    if bf16:
+        bufs, curs, m = _rectify_launch_bf16(ref0, ref2, filt[0], filt[1], ctx0, ctx2, time_offsets, off0, off2)
+        return list(zip(bufs, curs))
+    bufs, m = _rectify_launch(ref0, ref2, filt[0], filt[1], ctx0, ctx2, time_offsets, off0, off2)
     return [(buf, _ch(buf, m["cur_output"])) for buf in bufs]
 
 
