@@ -46,6 +46,21 @@ def _c(name):
     return constants()[name]
 
 
+def function_body(name):
+    """The body of the function or kernel `name` of projection.hip, found by matching braces from the `{` that ends its
+    signature (comment-free text, whitespace collapsed).  `name` is followed by `(` at its definition: a call inside
+    another body ends in `;`, not in `{`, before the next `{`."""
+    text = source(SOURCE)
+    m = re.search(r"\b%s\s*\([^;{}]*\)\s*\{" % re.escape(name), text)
+    if not m:
+        raise AssertionError("no function %s" % name)
+    depth, i = 1, m.end()
+    while depth:
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        i += 1
+    return " ".join(text[m.end():i - 1].split())
+
+
 TW, TH, BLK = _c("PROJ_TW"), _c("PROJ_TH"), _c("PROJ_BLK")
 ADD_BITS, ADD_CELL, CLS_BITS = _c("PROJ_ADD_BITS"), _c("PROJ_ADD_CELL"), _c("PROJ_CLS_BITS")
 BLOCK_CAP, NMAX, INV_BITS = _c("PROJ_BLOCK_CAP"), _c("PROJ_NMAX"), _c("PROJ_INV_BITS")

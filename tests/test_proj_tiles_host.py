@@ -20,9 +20,20 @@ def test_constants_match_the_source():
                         ("PROJ_NMAX", pt.NMAX), ("PROJ_INV_BITS", pt.INV_BITS)):
         m = re.search(r"^\s*#define\s+%s\s+(\S+)" % name, text, flags=re.M)
         assert m and int(m.group(1), 0) == value, name
-    # the constants the mirror states itself
-    assert text.count("min(4, max(0, emax - emin) / PROJ_CLS_BITS + 1)") == 2
-    assert text.count("max(-100, min(100, PROJ_ADD_BITS - (") == 6
+    # the constants the mirror states itself: each defined once, in a helper both K1 families call
+    flat = " ".join(text.split())
+    pull, lean = pt.function_body("proj_pull"), pt.function_body("proj_pull_lean")
+    ncls = "min(4, max(0, p.emax - emin) / PROJ_CLS_BITS + 1)"
+    assert flat.count("max(0, p.emax - emin) / PROJ_CLS_BITS") == flat.count("/ PROJ_CLS_BITS") == 1
+    assert ncls in pt.function_body("proj_plan")
+    clamp = "max(-100, min(100, PROJ_ADD_BITS - ("
+    assert flat.count(clamp) == flat.count("max(-100,") == 3 and pt.function_body("proj_class_scales").count(clamp) == 3
+    for body in (pull, lean):
+        assert "proj_plan<DEPTH>(" in body and "proj_class_scales(plan, cls)" in body
+    # a source's weight class: once, both K1 families through it (proj_pull inside pull_add)
+    assert flat.count(">= 3 * PROJ_CLS_BITS") == 1 and ">= 3 * PROJ_CLS_BITS" in pt.function_body("proj_weight_class")
+    assert "proj_weight_class(d, emax, ncls)" in pt.function_body("pull_add") and "pull_add<DEPTH>(" in pull
+    assert "proj_weight_class(d, emax, ncls)" in lean
     assert text.count("(32 - __clz(nmax - 1)) - 5") == 1 and text.count("(32 - __clz(busiest - 1)) - 5") == 1
     assert 2 ** 5 == pt.ADD_CELL
 
@@ -53,11 +64,37 @@ def test_dispatch_chain_matches_project_forward_list():
 def test_k1_scale_and_retry_statements_match_the_sources():
     text = " ".join(source(pt.SOURCE).split())
     # proj_pull: per class, retried once; proj_pull_lean: one shift for all classes, bias scaled with it
-    assert "kvx -= shift; kvy -= shift; kc -= shift;" in text
-    assert "const int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls))) - shift;" in text
+    assert "kvx -= shift; kvy -= shift; kc -= shift;" in pt.function_body("proj_pull")
+    assert "const int kc = k0.kc - shift, kvx = k0.kvx - shift, kvy = k0.kvy - shift;" in pt.function_body("proj_pull_lean")
+    assert "max(-100, min(100, PROJ_ADD_BITS - (p.efx + p.ec - PROJ_CLS_BITS * cls)))," in pt.function_body("proj_class_scales")
     assert "const int bias_bits = max(PROJ_ADD_BITS - shift, 0);" in text
     assert "const int Y = (int)(vlo[j] - ((unsigned)n << bias_bits));" in text
     assert "PL_BIAS" not in text
+
+
+def test_shared_helpers_are_defined_once_and_called_from_every_kernel():
+    text = " ".join(source(pt.SOURCE).split())
+    bodies = {k: pt.function_body(k) for k in ("proj_scan", "proj_scan4", "proj_pull", "proj_pull_lean", "proj_finish")}
+    # workgroup -> tile: one chain of divisions
+    assert text.count("tile / per_img") == 1 and "const int b = tile / per_img;" in pt.function_body("proj_tile")
+    for k, body in bodies.items():
+        assert "proj_tile(" in body and "band_item(blockIdx.x, gridDim.x)" in body, k
+    assert "proj_tile(band_item(blockIdx.x, gridDim.x), groups_x, g.tiles_y)" in bodies["proj_scan4"]
+    # proj_finish leaves before the divisions where a tile has nothing to do
+    fin = bodies["proj_finish"]
+    assert fin.index("if (!fallback && (!fillhole || tflag == 0)) return;") < fin.index("proj_tile(tile, g.tiles_x, g.tiles_y)")
+    # the fallback's dirty planes: cleaned by K0, marked by K1
+    assert text.count("planes[i] = 0.0f;") == 1 and text.count("ws[PROJ_WS_DIRTY] =") == 1
+    assert "proj_clean_dirty<64>(ws, planes);" in bodies["proj_scan"] and "proj_clean_dirty<256>(ws, planes);" in bodies["proj_scan4"]
+    # K1: strip walk, quad loads, output buffers, stores and bookkeeping
+    for stmt, helper in (("(lr * src.fh + px) * 4", "proj_quad_strip"), ("buf_f32x4(pl.f1, s.vo, yu * src.fh * 4)", "proj_load_quad"),
+                         ("buffer_rsrc(out + oc,", "proj_out"), ("o.ro1, vo, so0, PROJ_ST_AUX);", "proj_store_quad"),
+                         ("o.rcn, voc, soc, 0);", "proj_store_cell"), ("ws[PROJ_WS_DIRTY + 1] =", "proj_mark_dirty")):
+        assert text.count(stmt) == 1 and stmt in pt.function_body(helper), helper
+        for k in ("proj_pull", "proj_pull_lean"):
+            assert re.search(r"\b%s(<[^>]*>)?\(" % helper, bodies[k]), (helper, k)
+    assert "PROJ_ST_AUX" not in bodies["proj_pull"] + bodies["proj_pull_lean"]
+    assert not re.search(r"#\s*ifndef\s+(PROJ_|PL_)", source(pt.SOURCE))
 
 
 def test_hand_worked_records():
@@ -86,10 +123,19 @@ def test_weight_predicate_matches_the_source_and_spares_ordinary_calls():
     """The second fallback reason: a block whose largest |weight| the fixed-point sums cannot hold (proj_weight_unfit)."""
     text = " ".join(source(pt.SOURCE).split())
     assert ("return cbits != 0 && (unsigned)(cbits - PROJ_W_LO_BITS) >= (unsigned)(PROJ_W_HI_BITS - PROJ_W_LO_BITS);") in text
-    # both K0 kernels test it beside the PROJ_BLOCK_CAP reason, on the block's largest weight over its valid sources
-    assert "> PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));" in text
-    assert "const bool wild = any && (nx * ny > PROJ_BLOCK_CAP || proj_weight_unfit(e[5]));" in text
-    assert text.count("proj_weight_unfit(") == 3
+    # both K0 kernels test it beside the PROJ_BLOCK_CAP reason, on the block's largest weight over its valid sources, and on
+    # the tiles proj_block_reach gives (the test itself is written out in each: as a function it changes proj_scan4's code)
+    scatter, scan4 = pt.function_body("scan_scatter"), pt.function_body("proj_scan4")
+    assert "> PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));" in scatter
+    assert "const bool wild = any && (nx * ny > PROJ_BLOCK_CAP || proj_weight_unfit(e[5]));" in scan4
+    assert text.count("proj_weight_unfit(") == 3 and text.count("> PROJ_BLOCK_CAP") == 2
+    # the span of a block's targets, the tiles it reaches and its part that reaches one tile: one definition each, both K0s
+    flat = " ".join(text.split())
+    for helper, stmt in (("proj_block_span", "max(bx0 + range.x0, 0)"), ("proj_block_reach", "min(span.x1 + 1, g.w - 1) / PROJ_TW"),
+                         ("proj_block_part", "max(bx0, ox0 - 1 - range.x1)")):
+        assert stmt in pt.function_body(helper) and flat.count(stmt) == 1, helper
+        assert helper + "(" in scatter and helper + "(" in scan4, helper
+    assert "scan_scatter(" in pt.function_body("proj_scan")
     bits = lambda v: int(np.abs(f32(v)).view(np.int32))     # noqa: E731
     assert pt.W_LO_BITS == bits(2.0 ** -56) and pt.W_HI_BITS == bits(2.0 ** 64)
     for v, unfit in ((0.0, False), (-0.0, False), (2.0 ** -40, False), (2.0 ** 40, False), (-2.0 ** 40, False), (2.0 ** -56, False),

@@ -193,6 +193,32 @@ __device__ __forceinline__ int band_item(int bid, int n) {
     const int x = bid & 7, k = bid >> 3, base = n >> 3, rem = n & 7;
     return x * base + min(x, rem) + k;
 }
+// item -> (image, tile row, tile column) of a raster of tiles_x x tiles_y per image (K0 with 16-byte lanes: groups of four tiles)
+struct ProjTile { int tile, b, tyi, txi; };
+__device__ __forceinline__ ProjTile proj_tile(int tile, int tiles_x, int tiles_y) {
+    const int per_img = tiles_x * tiles_y;
+    const int b = tile / per_img;
+    const int trem = tile - b * per_img;
+    const int tyi = trem / tiles_x;
+    return ProjTile{tile, b, tyi, trem - tyi * tiles_x};
+}
+
+// K0: the previous call on this workspace took the fallback: the floats IT dirtied (its frame may have been larger than
+// this one) are cleaned here, a slice per workgroup (this call's K1 rewrites the words)
+template <int THREADS>
+__device__ __forceinline__ void proj_clean_dirty(const int* ws, float* __restrict__ planes) {
+    const int64_t dirty = proj_dirty_floats(ws);
+    if (dirty != 0) {
+        const int64_t chunk = (dirty + gridDim.x - 1) / gridDim.x;
+        const int64_t lo = (int64_t)blockIdx.x * chunk, hi = min(dirty, lo + chunk);
+        for (int64_t i = lo + threadIdx.x; i < hi; i += THREADS) planes[i] = 0.0f;
+    }
+}
+// K1 (one thread of the call): what this call leaves in the scratch planes
+__device__ __forceinline__ void proj_mark_dirty(int* __restrict__ ws, bool fallback, int64_t plane_floats) {
+    ws[PROJ_WS_DIRTY] = fallback ? (int)(unsigned)(plane_floats & 0xffffffffll) : 0;
+    ws[PROJ_WS_DIRTY + 1] = fallback ? (int)(plane_floats >> 32) : 0;
+}
 
 // min / max over each row of 16 lanes (four DPP row_shr steps); the result is in lane 15 of the row
 #define PROJ_ROW_STEP(OP, CTRL) v = OP(v, __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false))
@@ -206,46 +232,60 @@ __device__ __forceinline__ int row16_max(int v) {
 }
 #undef PROJ_ROW_STEP
 
+// K0, per 16x16 block [bx0, bx1] x [y0, by1] of the source frame.  Four boxes [x0, x1] x [y0, y1]:
+//   range: the integer displacements (L - x, T - y) of the block's valid pixels (none: x0 == INT_MAX);
+//   span:  their top-left targets (a target (L, T) feeds columns L, L + 1 and rows T, T + 1);
+//   reach: the output tiles the block can reach;
+//   part:  the pixels of the block that can reach tile (tx, ty) (empty: x0 > x1 or y0 > y1) -- a pixel at x has L in
+//          [x + range.x0, x + range.x1], the tile takes L in [ox0 - 1, tx1].
+struct ProjBox { int x0, x1, y0, y1; };
+__device__ __forceinline__ ProjBox proj_block_span(const ProjBox range, int bx0, int bx1, int y0, int by1, const ProjGeom& g) {
+    return ProjBox{max(bx0 + range.x0, 0), min(bx1 + range.x1, g.w - 1), max(y0 + range.y0, 0), min(by1 + range.y1, g.h - 1)};
+}
+__device__ __forceinline__ ProjBox proj_block_reach(const ProjBox span, const ProjGeom& g) {
+    return ProjBox{span.x0 / PROJ_TW, min(span.x1 + 1, g.w - 1) / PROJ_TW, span.y0 / PROJ_TH, min(span.y1 + 1, g.h - 1) / PROJ_TH};
+}
+__device__ __forceinline__ ProjBox proj_block_part(const ProjBox range, int bx0, int bx1, int y0, int by1, int tx, int ty, const ProjGeom& g) {
+    const int ox0 = tx * PROJ_TW, oy0 = ty * PROJ_TH;
+    const int tx1 = min(ox0 + PROJ_TW - 1, g.w - 1), ty1 = min(oy0 + PROJ_TH - 1, g.h - 1);
+    return ProjBox{max(bx0, ox0 - 1 - range.x1), min(bx1, tx1 - range.x0), max(y0, oy0 - 1 - range.y1), min(by1, ty1 - range.y0)};
+}
+
 // The tail of K0.  Lanes 15, 31, 47, 63 of the wave speak for four 16x16 blocks that sit side by side (x = the
 // block's last column, y0 = its first row) and mostly feed the same two or three output tiles: per tile of the
 // union of their ranges the four parts are merged in registers and the record is updated by ONE atomic
 // instruction (lane k = field k) -- the atomics are the expensive part of this kernel (one wave instruction
 // per ~50 ns per CU at the memory side, whatever its lane count).
-__device__ __forceinline__ void scan_scatter(const ProjGeom& g, int* __restrict__ ws, int b, int lane, int x, int y0,
-                                             int dlmin, int dlmax, int dtmin, int dtmax, int vbits, int cbits, int mbits, int fbits) {
-    const bool any = dlmin != INT_MAX;
+__device__ __forceinline__ void scan_scatter(const ProjGeom& g, int* __restrict__ ws, int b, int lane, int x, int y0, const ProjBox range,
+                                             int vbits, int cbits, int mbits, int fbits) {
+    const bool any = range.x0 != INT_MAX;
     const int bx0 = x - 15, bx1 = min(x, g.w - 1), by1 = min(y0 + PROJ_BLK - 1, g.h - 1);
-    // top-left targets of the block lie in [X0, X1] x [Y0, Y1]; a target (L, T) feeds columns L, L + 1, rows T, T + 1
-    const int X0 = max(bx0 + dlmin, 0), X1 = min(bx1 + dlmax, g.w - 1);
-    const int Y0 = max(y0 + dtmin, 0), Y1 = min(by1 + dtmax, g.h - 1);
+    const ProjBox span = proj_block_span(range, bx0, bx1, y0, by1, g);
     int ta = INT_MAX, tb = INT_MIN, tc = INT_MAX, td = INT_MIN;
     bool wild = false;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int sl = 16 * q + 15;
         if (!__builtin_amdgcn_readlane((int)any, sl)) continue;
-        const int a0 = __builtin_amdgcn_readlane(X0, sl) / PROJ_TW, a1 = min(__builtin_amdgcn_readlane(X1, sl) + 1, g.w - 1) / PROJ_TW;
-        const int c0 = __builtin_amdgcn_readlane(Y0, sl) / PROJ_TH, c1 = min(__builtin_amdgcn_readlane(Y1, sl) + 1, g.h - 1) / PROJ_TH;
-        wild = wild || (a1 - a0 + 1) * (c1 - c0 + 1) > PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));
-        ta = min(ta, a0); tb = max(tb, a1); tc = min(tc, c0); td = max(td, c1);
+        const ProjBox reach = proj_block_reach(ProjBox{__builtin_amdgcn_readlane(span.x0, sl), __builtin_amdgcn_readlane(span.x1, sl),
+                                                       __builtin_amdgcn_readlane(span.y0, sl), __builtin_amdgcn_readlane(span.y1, sl)}, g);
+        // (the fallback test is written out in both K0s: as a function it changes the compare forms proj_scan4 compiles to)
+        wild = wild || (reach.x1 - reach.x0 + 1) * (reach.y1 - reach.y0 + 1) > PROJ_BLOCK_CAP || proj_weight_unfit(__builtin_amdgcn_readlane(cbits, sl));
+        ta = min(ta, reach.x0); tb = max(tb, reach.x1); tc = min(tc, reach.y0); td = max(td, reach.y1);
     }
     if (wild) { if (lane == 0) ws[PROJ_WS_FLAG] = 1; return; }
     for (int ty = tc; ty <= td; ++ty)
         for (int tx = ta; tx <= tb; ++tx) {
-            const int ox0 = tx * PROJ_TW, oy0 = ty * PROJ_TH;
-            const int tx1 = min(ox0 + PROJ_TW - 1, g.w - 1), ty1 = min(oy0 + PROJ_TH - 1, g.h - 1);
-            // a pixel at x has L in [x + dlmin, x + dlmax]; the tile takes L in [ox0 - 1, tx1]
-            const int sx0 = max(bx0, ox0 - 1 - dlmax), sx1 = min(bx1, tx1 - dlmin);
-            const int sy0 = max(y0, oy0 - 1 - dtmax), sy1 = min(by1, ty1 - dtmin);
-            const bool hit = any && sx0 <= sx1 && sy0 <= sy1;
+            const ProjBox part = proj_block_part(range, bx0, bx1, y0, by1, tx, ty, g);
+            const bool hit = any && part.x0 <= part.x1 && part.y0 <= part.y1;
             // fields as stored (0 = nothing), merged over the four blocks
             int f0m = 0, f1m = 0, f2m = 0, f3m = 0, f4m = 0, f5m = 0, f6m = 0, f7m = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int sl = 16 * q + 15;
                 if (!__builtin_amdgcn_readlane((int)hit, sl)) continue;
-                f0m = max(f0m, 32767 - __builtin_amdgcn_readlane(sx0, sl)); f1m = max(f1m, 32767 - __builtin_amdgcn_readlane(sy0, sl));
-                f2m = max(f2m, __builtin_amdgcn_readlane(sx1, sl) + 1); f3m = max(f3m, __builtin_amdgcn_readlane(sy1, sl) + 1);
+                f0m = max(f0m, 32767 - __builtin_amdgcn_readlane(part.x0, sl)); f1m = max(f1m, 32767 - __builtin_amdgcn_readlane(part.y0, sl));
+                f2m = max(f2m, __builtin_amdgcn_readlane(part.x1, sl) + 1); f3m = max(f3m, __builtin_amdgcn_readlane(part.y1, sl) + 1);
                 f4m = max(f4m, __builtin_amdgcn_readlane(vbits, sl)); f5m = max(f5m, __builtin_amdgcn_readlane(cbits, sl));
                 f6m = max(f6m, __builtin_amdgcn_readlane(mbits, sl));
                 f7m = max(f7m, __builtin_amdgcn_readlane(fbits, sl));
@@ -264,19 +304,9 @@ __device__ __forceinline__ void scan_scatter(const ProjGeom& g, int* __restrict_
 template <bool DEPTH>
 __global__ __launch_bounds__(64) void proj_scan(ProjSrc src, ProjGeom g, int* __restrict__ ws, float* __restrict__ planes,
                                                 int64_t plane_floats) {
-    const int64_t dirty = proj_dirty_floats(ws);
-    if (dirty != 0) {
-        // the previous call on this workspace took the fallback: the floats IT dirtied (its frame may have been larger
-        // than this one) are cleaned here, a slice per workgroup (this call's K1 rewrites the words)
-        const int64_t chunk = (dirty + gridDim.x - 1) / gridDim.x;
-        const int64_t lo = (int64_t)blockIdx.x * chunk, hi = min(dirty, lo + chunk);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += 64) planes[i] = 0.0f;
-    }
-    const int tile = band_item(blockIdx.x, gridDim.x), lane = threadIdx.x;
-    const int per_img = g.tiles_x * g.tiles_y;
-    const int b = tile / per_img;
-    const int trem = tile - b * per_img;
-    const int tyi = trem / g.tiles_x, txi = trem - tyi * g.tiles_x;
+    proj_clean_dirty<64>(ws, planes);
+    const ProjTile t = proj_tile(band_item(blockIdx.x, gridDim.x), g.tiles_x, g.tiles_y);
+    const int lane = threadIdx.x, b = t.b, tyi = t.tyi, txi = t.txi;
     const int x = txi * PROJ_TW + lane, y0 = tyi * PROJ_TH;
     const int xc = min(x, g.w - 1);
     const ProjPlanes pl = proj_planes<DEPTH>(src, b, g.h, g.w);
@@ -294,6 +324,8 @@ __global__ __launch_bounds__(64) void proj_scan(ProjSrc src, ProjGeom g, int* __
             const float fx = raw[k].fx, fy = raw[k].fy;
             int L, T;
             const bool valid = pix_target(fx, fy, x, y, wbits, hbits, L, T) && x < g.w && y < g.h;
+            // (the merge is written out in both K0s: with selects here, with a branch in proj_scan4 -- either form in the
+            //  other kernel compiles to other code)
             const int dl = L - x, dt = T - y;
             dlmin = min(dlmin, valid ? dl : INT_MAX); dlmax = max(dlmax, valid ? dl : INT_MIN);
             dtmin = min(dtmin, valid ? dt : INT_MAX); dtmax = max(dtmax, valid ? dt : INT_MIN);
@@ -312,7 +344,7 @@ __global__ __launch_bounds__(64) void proj_scan(ProjSrc src, ProjGeom g, int* __
     dlmin = row16_min(dlmin); dlmax = row16_max(dlmax);
     dtmin = row16_min(dtmin); dtmax = row16_max(dtmax);
     vbits = row16_max(vbits); cbits = row16_max(cbits); mbits = row16_max(mbits); fbits = row16_max(fbits);
-    scan_scatter(g, ws, b, lane, x, y0, dlmin, dlmax, dtmin, dtmax, vbits, cbits, mbits, fbits);
+    scan_scatter(g, ws, b, lane, x, y0, ProjBox{dlmin, dlmax, dtmin, dtmax}, vbits, cbits, mbits, fbits);
 }
 
 // K0 for a full-resolution flow: the same, with 16-byte lanes (a walk with 4-byte lanes reaches ~4 TB/s on this
@@ -338,11 +370,8 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
     if (tid < 128) sblk[tid >> 3][tid & 7] = ((tid & 7) == 0 || (tid & 7) == 2) ? INT_MAX : ((tid & 7) == 1 || (tid & 7) == 3) ? INT_MIN : 0;
     reinterpret_cast<uint4*>(&stab[tid][0])[0] = make_uint4(0u, 0u, 0u, 0u);
     reinterpret_cast<uint4*>(&stab[tid][0])[1] = make_uint4(0u, 0u, 0u, 0u);
-    const int per_img = groups_x * g.tiles_y;
-    const int item = band_item(blockIdx.x, gridDim.x);
-    const int b = item / per_img;
-    const int rem = item - b * per_img;
-    const int tyi = rem / groups_x, gxi = rem - tyi * groups_x;
+    const ProjTile t = proj_tile(band_item(blockIdx.x, gridDim.x), groups_x, g.tiles_y);      // (a "tile" here: a group of four)
+    const int b = t.b, tyi = t.tyi, gxi = t.txi;
     const int x0 = gxi * 4 * PROJ_TW + 4 * lane, y0 = tyi * PROJ_TH, yw = y0 + 4 * wave;
     const ProjPlanes pl = proj_planes<DEPTH>(src, b, g.h, g.w);
     const unsigned wbits = (unsigned)__float_as_int((float)(g.w - 1)), hbits = (unsigned)__float_as_int((float)(g.h - 1));
@@ -355,12 +384,7 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
         if constexpr (DEPTH) qd[r] = buf_f32x4(pl.d, x0 * 4, min(yw + r, g.h - 1) * src.dh * 4);
     }
     // (behind the flow loads, so that they are in flight while the header word arrives)
-    const int64_t dirty = proj_dirty_floats(ws);
-    if (dirty != 0) {                                       // (see proj_scan)
-        const int64_t chunk = (dirty + gridDim.x - 1) / gridDim.x;
-        const int64_t lo = (int64_t)blockIdx.x * chunk, hi = min(dirty, lo + chunk);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) planes[i] = 0.0f;
-    }
+    proj_clean_dirty<256>(ws, planes);
     __syncthreads();
     int dlmin = INT_MAX, dlmax = INT_MIN, dtmin = INT_MAX, dtmax = INT_MIN, vbits = 0, cbits = 0, mbits = 0, fbits = 0;
 #pragma unroll
@@ -404,25 +428,18 @@ __global__ __launch_bounds__(256) void proj_scan4(ProjSrc src, ProjGeom g, int g
         const int k = tid >> 4, j = tid & 15;
         const int* e = sblk[k];
         const int bx0 = gxi * 4 * PROJ_TW + k * PROJ_BLK, bx1 = min(bx0 + PROJ_BLK - 1, g.w - 1), by1 = min(y0 + PROJ_BLK - 1, g.h - 1);
-        const int dlmin_ = e[0], dlmax_ = e[1], dtmin_ = e[2], dtmax_ = e[3];
-        const bool any = dlmin_ != INT_MAX && bx0 < g.w;
-        // top-left targets of the block lie in [X0, X1] x [Y0, Y1]; a target (L, T) feeds columns L, L + 1, rows T, T + 1
-        const int X0 = max(bx0 + dlmin_, 0), X1 = min(bx1 + dlmax_, g.w - 1);
-        const int Y0 = max(y0 + dtmin_, 0), Y1 = min(by1 + dtmax_, g.h - 1);
-        const int a0 = X0 / PROJ_TW, a1 = min(X1 + 1, g.w - 1) / PROJ_TW, c0 = Y0 / PROJ_TH, c1 = min(Y1 + 1, g.h - 1) / PROJ_TH;
-        const int nx = a1 - a0 + 1, ny = c1 - c0 + 1;
+        const ProjBox range{e[0], e[1], e[2], e[3]};
+        const bool any = range.x0 != INT_MAX && bx0 < g.w;
+        const ProjBox reach = proj_block_reach(proj_block_span(range, bx0, bx1, y0, by1, g), g);
+        const int a0 = reach.x0, a1 = reach.x1, c0 = reach.y0, c1 = reach.y1, nx = a1 - a0 + 1, ny = c1 - c0 + 1;
         const bool wild = any && (nx * ny > PROJ_BLOCK_CAP || proj_weight_unfit(e[5]));
         if (wild && j == 0) ws[PROJ_WS_FLAG] = 1;               // the call takes the fallback; records no longer matter
         const bool wide = any && !wild && (nx > 2 || ny > 8);   // more tiles than slots: thread j == 0 walks them all
         const int torg_x = gxi * 4 - PROJ_STAB_X0, torg_y = tyi - PROJ_STAB_Y0;
         auto update = [&](int tx, int ty) {
-            const int ox0 = tx * PROJ_TW, oy0 = ty * PROJ_TH;
-            const int tx1 = min(ox0 + PROJ_TW - 1, g.w - 1), ty1 = min(oy0 + PROJ_TH - 1, g.h - 1);
-            // a pixel at x has L in [x + dlmin, x + dlmax]; the tile takes L in [ox0 - 1, tx1]
-            const int sx0 = max(bx0, ox0 - 1 - dlmax_), sx1 = min(bx1, tx1 - dlmin_);
-            const int sy0 = max(y0, oy0 - 1 - dtmax_), sy1 = min(by1, ty1 - dtmin_);
-            if (sx0 > sx1 || sy0 > sy1) return;
-            const int f[8] = {32767 - sx0, 32767 - sy0, sx1 + 1, sy1 + 1, e[4], e[5], e[6], e[7]};
+            const ProjBox part = proj_block_part(range, bx0, bx1, y0, by1, tx, ty, g);
+            if (part.x0 > part.x1 || part.y0 > part.y1) return;
+            const int f[8] = {32767 - part.x0, 32767 - part.y0, part.x1 + 1, part.y1 + 1, e[4], e[5], e[6], e[7]};
             const int rx = tx - torg_x, ry = ty - torg_y;
             if ((unsigned)rx < PROJ_STAB && (unsigned)ry < PROJ_STAB) {
 #pragma unroll
@@ -478,23 +495,15 @@ template <> struct ProjCountCell<true> { typedef unsigned long long type; };    
 // Memory: the kernel is bound by the memory system (in-kernel stamps: the later a
 // workgroup's requests are queued, the longer it lives), so the flow is read and count / output are written
 // with 16-byte lanes: a lane owns four consecutive pixels.
-#ifndef PROJ_PULL_THREADS
 #define PROJ_PULL_THREADS 128
-#endif
-#ifndef PROJ_PULL_WAVES
 #define PROJ_PULL_WAVES 5           // 9 workgroups x 2 waves per CU
-#endif
-#ifndef PROJ_PULL_CH
 #define PROJ_PULL_CH 2              // loads in flight per lane: CH x 4 pixels (CH x 1 through the scalar walk)
-#endif
 #define PROJ_AW (PROJ_TW + 1)
 #define PROJ_AH (PROJ_TH + 1)
 #define PROJ_VS 66                                  // grid row pitch of the 8-byte planes: rows start 16-byte aligned
 #define PROJ_CS4 68                                 // ... of the 4-byte count plane
 #define PROJ_NW (PROJ_PULL_THREADS / 64)            // waves per workgroup
-#ifndef PROJ_ST_AUX
 #define PROJ_ST_AUX 2                               // cache policy of K1's result stores: nt (0 = default, 16 = sc1: K1 1.4 us slower at 1080p)
-#endif
 #define PROJ_EPI_ITERS (PROJ_TH / (4 * PROJ_NW))    // a wave writes four rows per instruction (16 lanes x 16 bytes each)
 template <bool DEPTH> struct ProjLds {
     static constexpr int cs = DEPTH ? PROJ_VS : PROJ_CS4;                      // count plane pitch
@@ -559,6 +568,95 @@ __device__ __forceinline__ void pull_bitmaps(const ProjGeom& g, int* __restrict_
     if (tid == 0) ws[g.off_list + tile] = s_misc[1] ? (s_misc[2] ? 3 : 1) : 0;
 }
 
+// K1, record -> plan: the tile's source rectangle (uh == 0: nothing lands here) and what its fixed-point scales follow.
+// A value addend is below 2^(ef + ec) and a weight below 2^ec, with 2^efx / 2^efy / 2^ec above the largest |fx| / |fy| /
+// |weight| that can reach this tile (from K0; each flow component has a scale of its own: a component that is small all over
+// the tile's sources -- the zero crossings of a smooth field, a pan along one axis -- keeps its own precision beside a large
+// other component; one common scale left 1.6e-4 px on such cells under 256-pixel flows, SURVEY's tolerance is 1e-4), so
+// addend * 2^(25 - e) is below 2^25.
+// DepthFlowProjection: the weights (inverse depth, 1e-6 + exp(-d): DAIN_slowmotion.py:143) can span many orders of magnitude
+// inside one tile, e.g. at the edge of a near object in front of sky, and a cell that only far-away sources reach must still
+// get full relative precision (the reference's fp32 sums give it that).  So the sources are taken in up to four passes by
+// weight class -- class j: weights within 2^(-6 j) .. 2^(-6 j - 6) of the largest, the last class everything below -- each
+// pass with its own scale, exact integer sums, one rounding to float, and the classes' results are added.  Almost every
+// tile has one class.
+struct ProjPlan { int ux0, uy0, uw, uh, efx, efy, ec, emax, ncls; };
+template <bool DEPTH, typename REC>      // REC: int[8], or the lean kernel's eight-word vector
+__device__ __forceinline__ ProjPlan proj_plan(const REC& rec) {
+    ProjPlan p;
+    p.ux0 = 32767 - rec[0]; p.uy0 = 32767 - rec[1];
+    p.uw = rec[2] - p.ux0; p.uh = rec[2] > 0 ? rec[3] - p.uy0 : 0;
+    p.efx = p.efy = p.ec = 0;
+    (void)frexpf(__int_as_float(rec[4]), &p.efx);
+    (void)frexpf(__int_as_float(rec[7]), &p.efy);
+    if constexpr (DEPTH) (void)frexpf(__int_as_float(rec[5]), &p.ec);
+    p.emax = (rec[5] >> 23) & 0xff;
+    const int emin = rec[6] ? ((PROJ_INV_BITS - rec[6]) >> 23) & 0xff : p.emax;
+    p.ncls = DEPTH ? min(4, max(0, p.emax - emin) / PROJ_CLS_BITS + 1) : 1;
+    return p;
+}
+// the scales of weight class cls, before a retry's shift (clamped so that 2^k stays a normal float when every addend is tiny
+// or huge)
+struct ProjScales { int kc, kvx, kvy; };
+__device__ __forceinline__ ProjScales proj_class_scales(const ProjPlan p, const int cls) {
+    return ProjScales{max(-100, min(100, PROJ_ADD_BITS - (p.ec - PROJ_CLS_BITS * cls))),
+                      max(-100, min(100, PROJ_ADD_BITS - (p.efx + p.ec - PROJ_CLS_BITS * cls))),
+                      max(-100, min(100, PROJ_ADD_BITS - (p.efy + p.ec - PROJ_CLS_BITS * cls)))};
+}
+// the weight class of a source of weight d
+__device__ __forceinline__ int proj_weight_class(float d, int emax, int ncls) {
+    const int delta = emax - ((__float_as_int(d) >> 23) & 0xff);
+    return min((delta >= PROJ_CLS_BITS ? 1 : 0) + (delta >= 2 * PROJ_CLS_BITS ? 1 : 0) + (delta >= 3 * PROJ_CLS_BITS ? 1 : 0), ncls - 1);
+}
+
+// K1 with 16-byte lanes: a row of the rectangle is read in quads that start at multiples of four pixels, nq per row; the
+// rectangle is walked in strips of up to 64 quads, a narrower strip packs rpi = 64 / width rows into a wave instruction.  Lane
+// -> row lr of the instruction and first pixel px of its quad; the NW waves take the rows in turn (step); vo / vod: the
+// lane's byte offsets in the flow / depth planes (the row a wave works on is the wave-uniform part).
+struct ProjStrip { int rpi, lr, px, step, vo, vod; };
+__device__ __forceinline__ int proj_quad_count(const ProjPlan p) { return p.uh > 0 ? (p.ux0 + p.uw - 1 - (p.ux0 & ~3)) / 4 + 1 : 0; }
+template <int NW>
+__device__ __forceinline__ ProjStrip proj_quad_strip(int ux0, int nq, int cs, int lane, const ProjSrc& src) {
+    const int width = min(64, nq - cs), rpi = 64 / width, lr = lane / width, lc = lane - lr * width;
+    const int px = (ux0 & ~3) + 4 * (cs + lc);
+    return ProjStrip{rpi, lr, px, NW * rpi, (lr * src.fh + px) * 4, (lr * src.dh + px) * 4};
+}
+// the quad of a lane in row `row` of the rectangle (wave-uniform); rows past the rectangle are not loaded (zeros)
+template <bool DEPTH>
+__device__ __forceinline__ void proj_load_quad(const ProjSrc& src, const ProjPlanes& pl, const ProjStrip s, int uy0, int uh, int row,
+                                               proj_v4f& qx, proj_v4f& qy, proj_v4f& qd) {
+    qx = qy = qd = proj_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    if (row < uh) {
+        const int yu = uy0 + row;
+        qx = buf_f32x4(pl.f0, s.vo, yu * src.fh * 4);
+        qy = buf_f32x4(pl.f1, s.vo, yu * src.fh * 4);
+        if constexpr (DEPTH) qd = buf_f32x4(pl.d, s.vod, yu * src.dh * 4);
+    }
+}
+
+// K1, output: the two flow planes and the count plane of image b as buffers
+struct ProjOut { __amdgpu_buffer_rsrc_t ro0, ro1, rcn; };
+__device__ __forceinline__ ProjOut proj_out(const ProjDst& dst, int per, int b, const ProjGeom& g, int64_t ob, int64_t oc, int oh,
+                                            int64_t cb, int ch) {
+    const ProjImage im = proj_image(b, per);
+    float* const out = dst.out[im.item] + (int64_t)im.bi * ob;
+    float* const count = dst.count[im.item] + (int64_t)im.bi * cb;
+    return ProjOut{buffer_rsrc(out, ((g.h - 1) * oh + g.w) * 4), buffer_rsrc(out + oc, ((g.h - 1) * oh + g.w) * 4),
+                   buffer_rsrc(count, ((g.h - 1) * ch + g.w) * 4)};
+}
+// a lane's four consecutive cells of a row as three 16-byte stores (vo / voc: the lane's byte offsets in the flow / count planes,
+// so0 / soc: the wave's row), and one cell of them (the rows are not 16-byte aligned, or the quad reaches past the frame)
+__device__ __forceinline__ void proj_store_quad(const ProjOut o, int vo, int so0, int voc, int soc, proj_v4f vx, proj_v4f vy, proj_v4f c) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(proj_v4i, vx), o.ro0, vo, so0, PROJ_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(proj_v4i, vy), o.ro1, vo, so0, PROJ_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(proj_v4i, c), o.rcn, voc, soc, PROJ_ST_AUX);
+}
+__device__ __forceinline__ void proj_store_cell(const ProjOut o, int vo, int so0, int voc, int soc, float vx, float vy, float c) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vx), o.ro0, vo, so0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vy), o.ro1, vo, so0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(c), o.rcn, voc, soc, 0);
+}
+
 // one source pixel into the grid
 // cls / ncls / emax: with depth, only the sources of weight class cls are taken (see proj_pull)
 template <bool DEPTH>
@@ -568,8 +666,7 @@ __device__ __forceinline__ void pull_add(unsigned long long* accv, typename Proj
     int L, T;
     bool valid = pix_target(fx, fy, px, py, wbits, hbits, L, T);
     if constexpr (DEPTH) {
-        const int delta = emax - ((__float_as_int(d) >> 23) & 0xff);
-        const int mine = min((delta >= PROJ_CLS_BITS ? 1 : 0) + (delta >= 2 * PROJ_CLS_BITS ? 1 : 0) + (delta >= 3 * PROJ_CLS_BITS ? 1 : 0), ncls - 1);
+        const int mine = proj_weight_class(d, emax, ncls);
         valid = valid && mine == cls;
     }
     const unsigned c = (unsigned)(L - cx), r = (unsigned)(T - cy);
@@ -593,21 +690,15 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     ccell* accc = reinterpret_cast<ccell*>(reinterpret_cast<char*>(lds) + ProjLds<DEPTH>::accc_off);
     unsigned* s_rowbits = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(lds) + ProjLds<DEPTH>::acc_bytes);   // [16][2]
     int* s_misc = reinterpret_cast<int*>(s_rowbits + 2 * PROJ_TH);     // [0] most addends in a cell, [1] holes, [2] negative counts
-    const int tile = band_item(blockIdx.x, gridDim.x);
-    const int per_img = g.tiles_x * g.tiles_y;
-    const int b = tile / per_img;
-    const int trem = tile - b * per_img;
-    const int tyi = trem / g.tiles_x, txi = trem - tyi * g.tiles_x;
+    const ProjTile t = proj_tile(band_item(blockIdx.x, gridDim.x), g.tiles_x, g.tiles_y);
+    const int tile = t.tile, b = t.b, tyi = t.tyi, txi = t.txi;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);    // (provably wave-uniform: scalar row offsets)
     const int ox0 = txi * PROJ_TW, oy0 = tyi * PROJ_TH;
     const bool fallback = ws[PROJ_WS_FLAG] != 0;
-    if (tile == 0 && tid == 0) {
-        ws[PROJ_WS_DIRTY] = fallback ? (int)(unsigned)(plane_floats & 0xffffffffll) : 0;
-        ws[PROJ_WS_DIRTY + 1] = fallback ? (int)(plane_floats >> 32) : 0;
-    }
+    if (tile == 0 && tid == 0) proj_mark_dirty(ws, fallback, plane_floats);
     int* entry = ws + g.off_tile + (int64_t)tile * PROJ_TILE_WORDS;
-    const int e0 = entry[0], e1 = entry[1], e2 = entry[2], e3 = entry[3], e4 = entry[4], e5 = entry[5], e6 = entry[6], e7 = entry[7];
+    const int rec[8] = {entry[0], entry[1], entry[2], entry[3], entry[4], entry[5], entry[6], entry[7]};
     const ProjPlanes pl = proj_planes<DEPTH>(src, b, g.h, g.w);
     const unsigned wbits = (unsigned)__float_as_int((float)(g.w - 1)), hbits = (unsigned)__float_as_int((float)(g.h - 1));
 
@@ -622,23 +713,8 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     __syncthreads();
     if (tid < 8) entry[tid] = 0;                            // every thread has read the record: empty for the next call
 
-    const int ux0 = 32767 - e0, uy0 = 32767 - e1;
-    const int uw = e2 - ux0, uh = e2 > 0 ? e3 - uy0 : 0;    // uh == 0: nothing lands here
-    // Fixed-point scales: a value addend is below 2^(ef + ec) and a weight below 2^ec, with 2^ef / 2^ec above the
-    // largest |fx| or |fy| (a scale per component: proj_pull_lean) / |weight| that can reach this tile (from K0), so
-    // addend * 2^(25 - e) is below 2^25.
-    // DepthFlowProjection: the weights (inverse depth, 1e-6 + exp(-d): DAIN_slowmotion.py:143) can span many
-    // orders of magnitude inside one tile, e.g. at the edge of a near object in front of sky, and a cell that only
-    // far-away sources reach must still get full relative precision (the reference's fp32 sums give it that).  So
-    // the sources are taken in up to four passes by weight class -- class j: weights within 2^(-6 j) .. 2^(-6 j - 6)
-    // of the largest, the last class everything below -- each pass with its own scale, exact integer sums, one
-    // rounding to float, and the classes' results are added.  Almost every tile has one class.
-    int efx = 0, efy = 0, ec = 0;
-    (void)frexpf(__int_as_float(e4), &efx);
-    (void)frexpf(__int_as_float(e7), &efy);
-    if constexpr (DEPTH) (void)frexpf(__int_as_float(e5), &ec);
-    const int emax = (e5 >> 23) & 0xff, emin = e6 ? ((PROJ_INV_BITS - e6) >> 23) & 0xff : emax;
-    const int ncls = DEPTH ? min(4, max(0, emax - emin) / PROJ_CLS_BITS + 1) : 1;
+    const ProjPlan plan = proj_plan<DEPTH>(rec);
+    const int ux0 = plan.ux0, uy0 = plan.uy0, uw = plan.uw, uh = plan.uh, emax = plan.emax, ncls = plan.ncls;
     // epilogue geometry: a lane owns four consecutive cells of a row, 16 lanes a row, a wave four rows
     const int q = lane & 15, rw = lane >> 4;
     const int xq = ox0 + 4 * q;
@@ -676,10 +752,8 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     // every tile, then holds no partial results in registers across the accumulation loop (two instantiations)
     auto run_class = [&](auto first_tag, int cls) {
     constexpr bool FIRST = decltype(first_tag)::value;
-    // (clamped so that 2^k stays a normal float when every addend is tiny or huge)
-    int kc = max(-100, min(100, PROJ_ADD_BITS - (ec - PROJ_CLS_BITS * cls)));
-    int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls)));
-    int kvy = max(-100, min(100, PROJ_ADD_BITS - (efy + ec - PROJ_CLS_BITS * cls)));
+    const ProjScales k0 = proj_class_scales(plan, cls);
+    int kc = k0.kc, kvx = k0.kvx, kvy = k0.kvy;
     for (int attempt = 0;; ++attempt) {
         const float svx = -ldexpf(1.0f, kvx), svy = -ldexpf(1.0f, kvy), scn = ldexpf(1.0f, kc);    // exact powers of two (the value addend is MINUS the flow)
         // The rectangle is walked in strips of up to 64 lanes.  A full strip: the workgroup's waves take its rows
@@ -710,27 +784,15 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
                 }
             }
         } else {
-            const int ux0a = ux0 & ~3;                                      // quads start at multiples of four pixels
-            const int nq = uh > 0 ? (ux0 + uw - 1 - ux0a) / 4 + 1 : 0;      // quads per row
+            const int nq = proj_quad_count(plan);
             for (int cs = 0; cs < nq; cs += 64) {
-                const int width = min(64, nq - cs), rpi = 64 / width;
-                const int lr = lane / width, lc = lane - lr * width;
-                const int px = ux0a + 4 * (cs + lc);
+                const ProjStrip sp = proj_quad_strip<PROJ_NW>(ux0, nq, cs, lane, src);
+                const int rpi = sp.rpi, lr = sp.lr, px = sp.px, step = sp.step;
                 const bool lane_on = lr < rpi;
-                const int step = PROJ_NW * rpi;
-                const int vo = (lr * src.fh + px) * 4, vod = (lr * src.dh + px) * 4;
                 for (int row0 = wave * rpi; row0 < uh; row0 += CH * step) {
                     proj_v4f qx[CH], qy[CH], qd[CH];
 #pragma unroll
-                    for (int k = 0; k < CH; ++k) {
-                        qx[k] = qy[k] = qd[k] = proj_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-                        if (row0 + k * step < uh) {                         // (wave-uniform test)
-                            const int yu = uy0 + row0 + k * step;
-                            qx[k] = buf_f32x4(pl.f0, vo, yu * src.fh * 4);
-                            qy[k] = buf_f32x4(pl.f1, vo, yu * src.fh * 4);
-                            if constexpr (DEPTH) qd[k] = buf_f32x4(pl.d, vod, yu * src.dh * 4);
-                        }
-                    }
+                    for (int k = 0; k < CH; ++k) proj_load_quad<DEPTH>(src, pl, sp, uy0, uh, row0 + k * step, qx[k], qy[k], qd[k]);
 #pragma unroll
                     for (int k = 0; k < CH; ++k) {
                         const int rowk = row0 + k * step + lr;
@@ -812,16 +874,11 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
     // normalise (flowprojection_cuda_kernel.cu:129-134) and write the tile once, 16 bytes per lane; leave the two
     // "count != 0" bitmaps for the hole filler and put the tile on its list if it has holes
     int holes = 0, negs = 0;
-    const ProjImage im = proj_image(b, src.per);
-    float* const out = dst.out[im.item] + (int64_t)im.bi * ob;
-    float* const count = dst.count[im.item] + (int64_t)im.bi * cb;
-    const __amdgpu_buffer_rsrc_t ro0 = buffer_rsrc(out, ((g.h - 1) * oh + g.w) * 4);
-    const __amdgpu_buffer_rsrc_t ro1 = buffer_rsrc(out + oc, ((g.h - 1) * oh + g.w) * 4);
-    const __amdgpu_buffer_rsrc_t rcn = buffer_rsrc(count, ((g.h - 1) * ch + g.w) * 4);
+    const ProjOut po = proj_out(dst, src.per, b, g, ob, oc, oh, cb, ch);
 #pragma unroll
     for (int it = 0; it < PROJ_EPI_ITERS; ++it) {
         const int yl = it * 4 * PROJ_NW + wave * 4 + rw, y = oy0 + yl;
-        float vxa[4], vya[4], ca[4];
+        proj_v4f vxa, vya, ca;
         unsigned nzb = 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -838,21 +895,13 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
         if (y < g.h) {
             const int so0 = (oy0 + it * 4 * PROJ_NW + wave * 4) * oh * 4, soc = (oy0 + it * 4 * PROJ_NW + wave * 4) * ch * 4;
             const int vo = (rw * oh + xq) * 4, voc = (rw * ch + xq) * 4;
-            if (vec_ok && xq + 3 < g.w) {
-                const proj_v4i vx4 = {__float_as_int(vxa[0]), __float_as_int(vxa[1]), __float_as_int(vxa[2]), __float_as_int(vxa[3])};
-                const proj_v4i vy4 = {__float_as_int(vya[0]), __float_as_int(vya[1]), __float_as_int(vya[2]), __float_as_int(vya[3])};
-                const proj_v4i c4 = {__float_as_int(ca[0]), __float_as_int(ca[1]), __float_as_int(ca[2]), __float_as_int(ca[3])};
-                __builtin_amdgcn_raw_buffer_store_b128(vx4, ro0, vo, so0, PROJ_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(vy4, ro1, vo, so0, PROJ_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(c4, rcn, voc, soc, PROJ_ST_AUX);
-            } else {
+            // (the loop stays here and in proj_pull_lean: inside a helper it is unrolled before the helper is inlined, and
+            //  the cells' constant offsets no longer fold into the store instructions)
+            if (vec_ok && xq + 3 < g.w) proj_store_quad(po, vo, so0, voc, soc, vxa, vya, ca);
+            else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (xq + j < g.w) {
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vxa[j]), ro0, vo + 4 * j, so0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vya[j]), ro1, vo + 4 * j, so0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(ca[j]), rcn, voc + 4 * j, soc, 0);
-                    }
+                    if (xq + j < g.w) proj_store_cell(po, vo + 4 * j, so0, voc + 4 * j, soc, vxa[j], vya[j], ca[j]);
             }
         }
     }
@@ -882,7 +931,7 @@ __global__ __launch_bounds__(PROJ_PULL_THREADS, PROJ_PULL_WAVES) void proj_pull(
 //  * FlowProjection divides by an integer count <= 32 times a power of two: the reciprocal is rcp + one Newton step
 //    (= the correctly rounded 1 / n for every n <= 32: tests), the quotient one multiply and one correction per
 //    component (Markstein: correctly rounded, the same bits as an IEEE division);
-//  * the record comes through the scalar cache (one s_load_dwordx8), tile coordinates from a 3-D grid (no divisions);
+//  * the record comes through the scalar cache (one s_load_dwordx8); the tile from the 1-D band_item grid, like the others;
 //  * the busiest-cell check (more than 32 addends in a cell: accumulate again with a coarser scale) rides on the
 //    epilogue's own count sums and on the barrier before the bitmaps instead of a pass and a barrier of its own: the
 //    tile is written as if every cell were fine, and written again in the rare case one was not.
@@ -902,12 +951,8 @@ template <bool DEPTH> struct PlLds {
     static constexpr int total = planes + PROJ_TH * 8 + 16;                    // + row bitmaps + four counters
 };
 static_assert(PlLds<false>::total <= 17920, "nine workgroups per CU");
-#ifndef PL_THREADS
 #define PL_THREADS 128
-#endif
-#ifndef PL_CH
 #define PL_CH 4                                     // row steps whose loads are in flight together (depth: half, for the registers)
-#endif
 #define PL_NW (PL_THREADS / 64)
 #define PL_EPI (PROJ_TH / (4 * PL_NW))              // a wave writes four rows per pass
 
@@ -940,11 +985,8 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     char* const lbase = reinterpret_cast<char*>(lds);
     unsigned* s_rowbits = reinterpret_cast<unsigned*>(lbase + LY::planes);            // [16][2]
     int* s_misc = reinterpret_cast<int*>(s_rowbits + 2 * PROJ_TH);                    // [0] most addends in a cell, [1] holes, [2] negative counts
-    const int tile = band_item(blockIdx.x, gridDim.x);
-    const int per_img = g.tiles_x * g.tiles_y;
-    const int b = tile / per_img;
-    const int trem = tile - b * per_img;
-    const int tyi = trem / g.tiles_x, txi = trem - tyi * g.tiles_x;
+    const ProjTile t = proj_tile(band_item(blockIdx.x, gridDim.x), g.tiles_x, g.tiles_y);
+    const int tile = t.tile, b = t.b, tyi = t.tyi, txi = t.txi;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ox0 = txi * PROJ_TW, oy0 = tyi * PROJ_TH;
@@ -956,10 +998,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     for (int i = tid; i < LY::total / 16; i += PL_THREADS) lds[i] = make_uint4(0u, 0u, 0u, 0u);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rec), "+s"(fb_word) :: "memory");
     const bool fallback = fb_word != 0;
-    if (tile == 0 && tid == 0) {
-        ws[PROJ_WS_DIRTY] = fallback ? (int)(unsigned)(plane_floats & 0xffffffffll) : 0;
-        ws[PROJ_WS_DIRTY + 1] = fallback ? (int)(plane_floats >> 32) : 0;
-    }
+    if (tile == 0 && tid == 0) proj_mark_dirty(ws, fallback, plane_floats);
     const ProjPlanes pl = proj_planes<DEPTH>(src, b, g.h, g.w);
     __syncthreads();
     if (tid < 8) entry[tid] = 0;                            // the record is in registers: empty for the next call
@@ -968,19 +1007,8 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
         return;
     }
 
-    const int e0 = rec[0], e1 = rec[1], e2 = rec[2], e3 = rec[3], e4 = rec[4], e5 = rec[5], e6 = rec[6], e7 = rec[7];
-    const int ux0 = 32767 - e0, uy0 = 32767 - e1;
-    const int uw = e2 - ux0, uh = e2 > 0 ? e3 - uy0 : 0;    // uh == 0: nothing lands here
-    // Fixed-point scales (see proj_pull for the weight classes).  Each flow component has its own: a tile's x scale follows the
-    // largest |fx| that reaches it, its y scale the largest |fy|, so a component that is small all over the tile's sources --
-    // the zero crossings of a smooth field, a pan along one axis -- keeps its own precision beside a large other component
-    // (one common scale left 1.6e-4 px on such cells under 256-pixel flows; SURVEY's tolerance is 1e-4).
-    int efx = 0, efy = 0, ec = 0;
-    (void)frexpf(__int_as_float(e4), &efx);
-    (void)frexpf(__int_as_float(e7), &efy);
-    if constexpr (DEPTH) (void)frexpf(__int_as_float(e5), &ec);
-    const int emax = (e5 >> 23) & 0xff, emin = e6 ? ((PROJ_INV_BITS - e6) >> 23) & 0xff : emax;
-    const int ncls = DEPTH ? min(4, max(0, emax - emin) / PROJ_CLS_BITS + 1) : 1;
+    const ProjPlan plan = proj_plan<DEPTH>(rec);
+    const int ux0 = plan.ux0, uy0 = plan.uy0, uh = plan.uh, emax = plan.emax, ncls = plan.ncls;
     // one interval per axis: valid target and inside the grid (columns ox0 - 1 .. ox0 + 63, rows oy0 - 1 .. oy0 + 15)
     const float lox = (float)max(ox0 - 1, 0), loy = (float)max(oy0 - 1, 0);
     const float hix = fminf((float)(g.w - 1), __uint_as_float(__float_as_uint((float)(ox0 + PROJ_TW)) - 1u));
@@ -996,12 +1024,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     const int q = lane & 15, rw = lane >> 4;
     const int xq = ox0 + 4 * q;
     const bool edge_x = ox0 + PROJ_TW >= g.w, edge_y = oy0 + PROJ_TH >= g.h;     // the tile touches the frame's last column / row
-    const ProjImage im = proj_image(b, src.per);
-    float* const out = dst.out[im.item] + (int64_t)im.bi * ob;
-    float* const count = dst.count[im.item] + (int64_t)im.bi * cb;
-    const __amdgpu_buffer_rsrc_t ro0 = buffer_rsrc(out, ((g.h - 1) * oh + g.w) * 4);
-    const __amdgpu_buffer_rsrc_t ro1 = buffer_rsrc(out + oc, ((g.h - 1) * oh + g.w) * 4);
-    const __amdgpu_buffer_rsrc_t rcn = buffer_rsrc(count, ((g.h - 1) * ch + g.w) * 4);
+    const ProjOut po = proj_out(dst, src.per, b, g, ob, oc, oh, cb, ch);
 
     // the 2x2 sums of one pass for the lane's four cells: lo / hi halves of the value cells; count cells: clo = weight sum
     // (depth), chi = addends
@@ -1052,15 +1075,10 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
     auto accumulate = [&](int cls, int kvx, int kvy, int kc, unsigned bias) {
         constexpr int CH = PL_CH;
         const float svx = -ldexpf(1.0f, kvx), svy = -ldexpf(1.0f, kvy), scn = ldexpf(1.0f, kc);    // exact powers of two (the value addend is MINUS the flow)
-        const int ux0a = ux0 & ~3;                                          // quads start at multiples of four pixels
-        const int nq = uh > 0 ? (ux0 + uw - 1 - ux0a) / 4 + 1 : 0;          // quads per row
+        const int nq = proj_quad_count(plan);
         for (int cs = 0; cs < nq; cs += 64) {
-            // a strip of up to 64 quads; a narrower one packs 64 / width rows into a wave instruction
-            const int width = min(64, nq - cs), rpi = 64 / width;
-            const int lr = lane / width, lc = lane - lr * width;
-            const int px = ux0a + 4 * (cs + lc);
-            const int step = PL_NW * rpi;
-            const int vo = (lr * src.fh + px) * 4, vod = (lr * src.dh + px) * 4;
+            const ProjStrip sp = proj_quad_strip<PL_NW>(ux0, nq, cs, lane, src);
+            const int rpi = sp.rpi, lr = sp.lr, px = sp.px, step = sp.step;
             // lanes beyond the strip's rows and pixels beyond the frame's last column: NaN coordinates, never inside
             float pxf[4];
 #pragma unroll
@@ -1068,19 +1086,11 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
             float yf = (float)(uy0 + wave * rpi + lr);
             const float ystep = (float)step;
             for (int row0 = wave * rpi; row0 < uh; row0 += CH * step) {
+                // (rows of the frame below the rectangle cannot reach the tile, rows below the frame read 0 and sit at
+                //  y > h - 1: both fail the interval test)
                 proj_v4f qx[CH], qy[CH], qd[CH];
 #pragma unroll
-                for (int k = 0; k < CH; ++k) {
-                    // (rows of the frame below the rectangle cannot reach the tile, rows below the frame read 0 and sit at
-                    //  y > h - 1: both fail the interval test)
-                    qx[k] = qy[k] = qd[k] = proj_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-                    if (row0 + k * step < uh) {                             // (wave-uniform)
-                        const int yu = uy0 + row0 + k * step;
-                        qx[k] = buf_f32x4(pl.f0, vo, yu * src.fh * 4);
-                        qy[k] = buf_f32x4(pl.f1, vo, yu * src.fh * 4);
-                        if constexpr (DEPTH) qd[k] = buf_f32x4(pl.d, vod, yu * src.dh * 4);
-                    }
-                }
+                for (int k = 0; k < CH; ++k) proj_load_quad<DEPTH>(src, pl, sp, uy0, uh, row0 + k * step, qx[k], qy[k], qd[k]);
 #pragma unroll
                 for (int k = 0; k < CH; ++k) {
                     if (row0 + k * step < uh) {                             // (wave-uniform)
@@ -1093,8 +1103,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                             if constexpr (DEPTH) {
                                 d = qd[k][j];
                                 if (ncls > 1) {
-                                    const int delta = emax - ((__float_as_int(d) >> 23) & 0xff);
-                                    const int mine = min((delta >= PROJ_CLS_BITS ? 1 : 0) + (delta >= 2 * PROJ_CLS_BITS ? 1 : 0) + (delta >= 3 * PROJ_CLS_BITS ? 1 : 0), ncls - 1);
+                                    const int mine = proj_weight_class(d, emax, ncls);
                                     hit = hit && mine == cls;
                                 }
                             }
@@ -1137,10 +1146,8 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
                 for (int i = tid; i < LY::planes / 16; i += PL_THREADS) lds[i] = make_uint4(0u, 0u, 0u, 0u);
                 __syncthreads();
             }
-            // (clamped so that 2^k stays a normal float when every addend is tiny or huge)
-            const int kc = max(-100, min(100, PROJ_ADD_BITS - (ec - PROJ_CLS_BITS * cls))) - shift;
-            const int kvx = max(-100, min(100, PROJ_ADD_BITS - (efx + ec - PROJ_CLS_BITS * cls))) - shift;
-            const int kvy = max(-100, min(100, PROJ_ADD_BITS - (efy + ec - PROJ_CLS_BITS * cls))) - shift;
+            const ProjScales k0 = proj_class_scales(plan, cls);
+            const int kc = k0.kc - shift, kvx = k0.kvx - shift, kvy = k0.kvy - shift;
             accumulate(cls, kvx, kvy, kc, bias);
             __syncthreads();
 #pragma unroll
@@ -1174,7 +1181,7 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
 #pragma unroll
         for (int it = 0; it < PL_EPI; ++it) {
             const int yl = it * 4 * PL_NW + wave * 4 + rw, y = oy0 + yl;
-            float vxa[4], vya[4], ca[4];
+            proj_v4f vxa, vya, ca;
             unsigned nzb = 0u;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1198,21 +1205,11 @@ __global__ __launch_bounds__(PL_THREADS, DEPTH ? 4 : 5) void proj_pull_lean(
             if (y < g.h) {
                 const int so0 = (oy0 + it * 4 * PL_NW + wave * 4) * oh * 4, soc = (oy0 + it * 4 * PL_NW + wave * 4) * ch * 4;
                 const int vo = (rw * oh + xq) * 4, voc = (rw * ch + xq) * 4;
-                if (xq + 3 < g.w) {
-                    const proj_v4i vx4 = {__float_as_int(vxa[0]), __float_as_int(vxa[1]), __float_as_int(vxa[2]), __float_as_int(vxa[3])};
-                    const proj_v4i vy4 = {__float_as_int(vya[0]), __float_as_int(vya[1]), __float_as_int(vya[2]), __float_as_int(vya[3])};
-                    const proj_v4i c4 = {__float_as_int(ca[0]), __float_as_int(ca[1]), __float_as_int(ca[2]), __float_as_int(ca[3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(vx4, ro0, vo, so0, PROJ_ST_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b128(vy4, ro1, vo, so0, PROJ_ST_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b128(c4, rcn, voc, soc, PROJ_ST_AUX);
-                } else {
+                if (xq + 3 < g.w) proj_store_quad(po, vo, so0, voc, soc, vxa, vya, ca);
+                else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (xq + j < g.w) {
-                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vxa[j]), ro0, vo + 4 * j, so0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(vya[j]), ro1, vo + 4 * j, so0, 0);
-                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(ca[j]), rcn, voc + 4 * j, soc, 0);
-                        }
+                        if (xq + j < g.w) proj_store_cell(po, vo + 4 * j, so0, voc + 4 * j, soc, vxa[j], vya[j], ca[j]);
                 }
             }
         }
@@ -1302,13 +1299,11 @@ __global__ __launch_bounds__(PROJ_FIN_THREADS) void proj_finish(
     //  lie where this call's list was, finds them empty)
     if (threadIdx.x == 0 && tflag != 0) ws[g.off_list + tile] = 0;
     if (!fallback && (!fillhole || tflag == 0)) return;
-    const int per_img = g.tiles_x * g.tiles_y;
+    const ProjTile t = proj_tile(tile, g.tiles_x, g.tiles_y);    // (behind the return most tiles take)
+    const int b = t.b, tyi = t.tyi, txi = t.txi;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool generic = g.rmw > 64 * PROJ_LINE_CHUNKS;
     const bool negatives = !fallback && (tflag & 2) != 0;
-    const int b = tile / per_img;
-    const int trem = tile - b * per_img;
-    const int tyi = trem / g.tiles_x, txi = trem - tyi * g.tiles_x;
     const int x = txi * PROJ_TW + lane, y0 = tyi * PROJ_TH + wave * PROJ_FIN_ROWS;
     const ProjImage im = proj_image(b, per);
     float* const count = dst.count[im.item] + (int64_t)im.bi * sc.b;
@@ -1317,7 +1312,7 @@ __global__ __launch_bounds__(PROJ_FIN_THREADS) void proj_finish(
     if (fallback) {
         // K1 left sums in the scratch planes: normalise (pass 2) and fill holes (pass 3) from them
         if (x >= g.w) return;
-        const int64_t npx = (int64_t)(g.ntiles / per_img) * g.h * g.w;
+        const int64_t npx = (int64_t)(g.ntiles / (g.tiles_x * g.tiles_y)) * g.h * g.w;
         const float* p0 = planes + (int64_t)b * g.h * g.w;
         const float* p1 = p0 + npx;
         const float* pc = p1 + npx;
@@ -1594,6 +1589,7 @@ static int project_forward_list(const float* const* flows, vfi_strides sf, const
     if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     // 16-byte stores need 16-byte aligned rows
     const int vec_ok = vec_out ? 1 : 0;
+    // (the two K1 families round differently on retried tiles, so which one a call gets is part of its result: keep as is)
     if (vec_in && vec_ok && g.tiles_y <= 65535 && images <= 65535)
         hipLaunchKernelGGL((proj_pull_lean<DEPTH>), dim3(g.ntiles), dim3(PL_THREADS), 0, st, src, dst, g,
                            (int64_t)s1.b, (int64_t)s1.c, (int)s1.h, (int64_t)sc.b, (int)sc.h, p.words, p.bits, p.planes, (int64_t)z.plane_floats);
