@@ -360,7 +360,8 @@ int vfi_correlation_backward(const float* input1, const float* input2, const flo
  *   PWC-Net's configuration (pad 4, kernel 1, max displacement 4, strides 1): ONE launch for all requested gradients,
  *     unless gradients x batch x channel groups exceeds a grid's z (65535).  Then, and for any other configuration, one
  *     launch per requested gradient -- the same bits.
- *   Nothing is allocated and no workspace is used: the call is legal inside a stream capture.  float32 only. */
+ *   Nothing is allocated and no workspace is used: the call is legal inside a stream capture.  float32 (the bfloat16 twin:
+ *     vfi_correlation_backward_pair_bf16, further down). */
 int vfi_correlation_backward_pair(const float* input1_a, const float* input2_a, const float* gradoutput_a,
                                   float* gradinput1_a, float* gradinput2_a,
                                   const float* input1_b, const float* input2_b, const float* gradoutput_b,
@@ -370,7 +371,7 @@ int vfi_correlation_backward_pair(const float* input1_a, const float* input2_a, 
                                   int stride1, int stride2,
                                   vfi_stream_t stream);
 /* ---- the correlation with PWC-Net's LeakyReLU fused in (PWCNet/PWCNet.py:230-301: every `self.corr(...)` is followed by
- * `self.leakyRELU(corr)` and a `torch.cat((corr, ...), 1)`).  float32 (the single entries' bfloat16 twins: further down).  Each entry is its unactivated twin with the
+ * `self.leakyRELU(corr)` and a `torch.cat((corr, ...), 1)`).  float32 (the bfloat16 twins of all four: further down).  Each entry is its unactivated twin with the
  * same argument checks, the same kernels and the same kernel choice, plus:
  *   forward:  y = v > 0 ? v : v * negative_slope applied to every mean v as it is stored -- one float multiplication, the
  *     bits of torch.nn.functional.leaky_relu on the twin's output (NaN stays NaN, -0 becomes -0 * negative_slope).
@@ -487,6 +488,60 @@ int vfi_correlation_lrelu_backward_bf16(const void* input1, const void* input2, 
                                         int pad_size, int kernel_size, int max_displacement,
                                         int stride1, int stride2, float negative_slope,
                                         vfi_stream_t stream);
+
+/* The pair entries on bfloat16 tensors: two calls of equal shape -- items a and b, the same pyramid level of a frame pair's
+ * two flow networks -- in ONE launch (forward), and any subset of their four gradients in ONE launch (backward).  The
+ * contract is the union of the float32 pair entries' above and of the bfloat16 single entries':
+ *   Layout: dense NCHW bfloat16 at any 2-byte-aligned address; `batch` is per item.  The lrelu entries take batch strides
+ *     in ELEMENTS (the 81 planes of an image contiguous); an odd stride is legal, the stores test their alignment one by one.
+ *   Result: every output equals the same-named output of the single bfloat16 entry on that item (vfi_correlation_forward_bf16,
+ *     vfi_correlation_lrelu_forward_bf16, vfi_correlation_backward_bf16, vfi_correlation_lrelu_backward_bf16) bit for bit, NaN
+ *     positions included, for every shape.  The forward kernel is therefore chosen as the single entry chooses it, on ONE
+ *     item's batch, h and w -- not on the pair's tile count, as the float32 pair does: the matrix-core kernel's float32
+ *     addition order is the hardware's and is not the one-thread-per-output kernel's chain.
+ *   Every requested output is WRITTEN in full; nothing else is touched.  Nothing is allocated, no workspace, no atomics:
+ *     the calls are legal inside a stream capture.
+ *   Backward: any of the four gradinput* may be NULL: it is not computed and no workgroup is launched for it.  An item with
+ *     both gradients NULL may be all NULL; otherwise its input1, input2, gradoutput (and y) must be non-NULL.  All four
+ *     NULL with a valid shape: VFI_OK, nothing launched.
+ *   Inputs may alias each other (at the top level item b is often item a swapped).  Two equal non-NULL outputs return
+ *     VFI_ERR_SHAPE.  So do, all before the first launch: a negative_slope that is not finite and > 0, a batch stride below
+ *     out_channels * out_h * out_w, stride1 != 1 in the backward, a shape that is not positive, a NULL tensor of an item
+ *     that needs it (a missing y included), invalid parameters, no output pixel.
+ *   Launches.  Forward: one, unless 2 * batch exceeds a grid's z (65535) where the matrix-core kernel is chosen; then one
+ *     per item.  Backward, PWC-Net's configuration (pad 4, kernel 1, max displacement 4, strides 1): one, unless gradients x
+ *     batch x channel groups exceeds 65535; then, and for any other configuration, one per requested gradient.  The bits
+ *     do not depend on it. */
+int vfi_correlation_forward_pair_bf16(const void* input1_a, const void* input2_a, void* output_a,
+                                      const void* input1_b, const void* input2_b, void* output_b,
+                                      int batch, int channel, int h, int w,
+                                      int pad_size, int kernel_size, int max_displacement,
+                                      int stride1, int stride2,
+                                      vfi_stream_t stream);
+int vfi_correlation_lrelu_forward_pair_bf16(const void* input1_a, const void* input2_a, void* output_a, int64_t output_a_batch_stride,
+                                            const void* input1_b, const void* input2_b, void* output_b, int64_t output_b_batch_stride,
+                                            int batch, int channel, int h, int w,
+                                            int pad_size, int kernel_size, int max_displacement,
+                                            int stride1, int stride2, float negative_slope,
+                                            vfi_stream_t stream);
+int vfi_correlation_backward_pair_bf16(const void* input1_a, const void* input2_a, const void* gradoutput_a,
+                                       void* gradinput1_a, void* gradinput2_a,
+                                       const void* input1_b, const void* input2_b, const void* gradoutput_b,
+                                       void* gradinput1_b, void* gradinput2_b,
+                                       int batch, int channel, int h, int w,
+                                       int pad_size, int kernel_size, int max_displacement,
+                                       int stride1, int stride2,
+                                       vfi_stream_t stream);
+int vfi_correlation_lrelu_backward_pair_bf16(const void* input1_a, const void* input2_a, const void* y_a, int64_t y_a_batch_stride,
+                                             const void* gradoutput_a, int64_t gradoutput_a_batch_stride,
+                                             void* gradinput1_a, void* gradinput2_a,
+                                             const void* input1_b, const void* input2_b, const void* y_b, int64_t y_b_batch_stride,
+                                             const void* gradoutput_b, int64_t gradoutput_b_batch_stride,
+                                             void* gradinput1_b, void* gradinput2_b,
+                                             int batch, int channel, int h, int w,
+                                             int pad_size, int kernel_size, int max_displacement,
+                                             int stride1, int stride2, float negative_slope,
+                                             vfi_stream_t stream);
 
 /* ==== glue either side of the ops above: the reference does these with torch
  * built-ins and Python; here each is one launch.  No reference binding exists for them: the

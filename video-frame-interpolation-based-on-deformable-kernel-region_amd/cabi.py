@@ -75,6 +75,11 @@ SIGNATURES = {
     "vfi_correlation_lrelu_backward": [_p, _p, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "vfi_correlation_lrelu_backward_pair": [_p, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p,
                                             _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_forward_pair_bf16": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_lrelu_forward_pair_bf16": [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vfi_correlation_backward_pair_bf16": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "vfi_correlation_lrelu_backward_pair_bf16": [_p, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p,
+                                                 _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     # glue either side of the ops
     "vfi_flow_upsample4": [_p, _p, _i, _i, _i, _i, _f, _f, Strides, Strides, _p],
     "vfi_flowprojection_forward_up4": [_p, _p, _p, _i, _i, _i, _f, _f, _i, Strides, Strides, Strides, _p],
@@ -650,19 +655,22 @@ def correlation_forward_bf16_kernel(which, input1, input2, pad_size, kernel_size
 
 
 def correlation_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displacement, stride1, stride2):
-    """(correlation_forward(a1, a2, ...), correlation_forward(b1, b2, ...)) from one launch: float32, equal shapes."""
+    """(correlation_forward(a1, a2, ...), correlation_forward(b1, b2, ...)) from one launch: equal shapes, all four float32
+    or all four bfloat16 (vfi_correlation_forward_pair_bf16: each output bit-equal to correlation_forward's on its item);
+    the outputs have the inputs' dtype."""
+    dtype, suffix = _bf16_or_f32(a1, a2, b1, b2)
     for t in (a1, a2, b1, b2):
-        _dev(t)
         if tuple(t.shape) != tuple(a1.shape):
             raise RuntimeError("correlation_forward_pair: the four inputs must have one shape")
     a1, a2, b1, b2 = (t.contiguous() for t in (a1, a2, b1, b2))
     b, c, h, w = a1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
-    outa = torch.empty((b, oc, oh, ow), device=a1.device, dtype=torch.float32)
+    outa = torch.empty((b, oc, oh, ow), device=a1.device, dtype=dtype)
     outb = torch.empty_like(outa)
-    with torch.cuda.device(_dev(a1)):
-        err = lib().vfi_correlation_forward_pair(_ptr(a1), _ptr(a2), _ptr(outa), _ptr(b1), _ptr(b2), _ptr(outb), b, c, h, w,
-                                                 pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1))
+    with torch.cuda.device(a1.device):
+        fn = getattr(lib(), "vfi_correlation_forward_pair" + suffix)
+        err = fn(_ptr(a1), _ptr(a2), _ptr(outa), _ptr(b1), _ptr(b2), _ptr(outb), b, c, h, w,
+                 pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_forward_pair: the binding returned %d" % err)
     return outa, outb
@@ -683,25 +691,26 @@ def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_
 def correlation_backward_pair(a1, a2, ga, b1, b2, gb, pad_size, kernel_size, max_displacement, stride1, stride2,
                               want=(True, True, True, True)):
     """(correlation_backward(a1, a2, ga, ...), correlation_backward(b1, b2, gb, ...)) from ONE vfi_correlation_backward_pair
-    call: float32, equal shapes.  Returns (grad a1, grad a2, grad b1, grad b2), each written in full and bit-equal to the
-    single call's; None where `want` says so or where that item's gradoutput is None (such a gradient costs nothing)."""
+    call: equal shapes, every tensor float32 or every tensor bfloat16 (vfi_correlation_backward_pair_bf16).  Returns
+    (grad a1, grad a2, grad b1, grad b2), each written in full, of the inputs' dtype and bit-equal to the single call's;
+    None where `want` says so or where that item's gradoutput is None (such a gradient costs nothing)."""
     inputs = (a1, a2, b1, b2)
     b, c, h, w = a1.shape
     gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if len(want) != 4 or any(tuple(t.shape) != tuple(a1.shape) for t in inputs) or \
             any(g is not None and tuple(g.shape) != gshape for g in (ga, gb)):
         raise RuntimeError("correlation_backward_pair: the four inputs must have one shape and the gradoutputs the output dimensions")
-    for t in inputs + tuple(g for g in (ga, gb) if g is not None):
-        _dev(t)
+    dtype, suffix = _bf16_or_f32(*inputs, *(g for g in (ga, gb) if g is not None))
     a1, a2, b1, b2 = (t.contiguous() for t in inputs)
     ga, gb = (None if g is None else g.contiguous() for g in (ga, gb))
     grads = [torch.empty_like(t) if want[i] and (ga, gb)[i // 2] is not None else None for i, t in enumerate((a1, a2, b1, b2))]
     if all(g is None for g in grads):
         return tuple(grads)
     with torch.cuda.device(a1.device):
-        err = lib().vfi_correlation_backward_pair(_ptr(a1), _ptr(a2), _opt(ga), _opt(grads[0]), _opt(grads[1]),
-                                                  _ptr(b1), _ptr(b2), _opt(gb), _opt(grads[2]), _opt(grads[3]), b, c, h, w,
-                                                  pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1))
+        fn = getattr(lib(), "vfi_correlation_backward_pair" + suffix)
+        err = fn(_ptr(a1), _ptr(a2), _opt(ga), _opt(grads[0]), _opt(grads[1]),
+                 _ptr(b1), _ptr(b2), _opt(gb), _opt(grads[2]), _opt(grads[3]), b, c, h, w,
+                 pad_size, kernel_size, max_displacement, stride1, stride2, _stream(a1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_backward_pair: the binding returned %d" % err)
     return tuple(grads)
@@ -780,7 +789,8 @@ def correlation_lrelu_forward(input1, input2, pad_size, kernel_size, max_displac
 def correlation_lrelu_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displacement, stride1, stride2, negative_slope,
                                    out=None):
     """(correlation_lrelu_forward(a1, a2, ...), correlation_lrelu_forward(b1, b2, ...)) from one launch: equal shapes.
-    out=: a pair of destinations (either may be None), each as correlation_lrelu_forward's."""
+    out=: a pair of destinations (either may be None), each as correlation_lrelu_forward's.  float32, or bfloat16 for every
+    tensor, out= included (vfi_correlation_lrelu_forward_pair_bf16: each output bit-equal to correlation_lrelu_forward's)."""
     slope = _slope(negative_slope)
     if any(tuple(t.shape) != tuple(a1.shape) for t in (a1, a2, b1, b2)):
         raise RuntimeError("correlation_lrelu_forward_pair: the four inputs must have one shape")
@@ -789,17 +799,18 @@ def correlation_lrelu_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_di
     outs = tuple(out) if out is not None else (None, None)
     if len(outs) != 2 or (outs[0] is not None and outs[0] is outs[1]):
         raise RuntimeError("correlation_lrelu_forward_pair: out= is a pair of two different destinations")
-    for o in outs:
+    for o in outs:                                          # (their shape and layout first, then everybody's dtype and device)
         if o is not None:
-            _lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair")
-    for t in (a1, a2, b1, b2):
-        _dev(t)
+            _lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair",
+                       torch.bfloat16 if a1.dtype == torch.bfloat16 else torch.float32)
+    dtype, suffix = _bf16_or_f32(a1, a2, b1, b2)
     a1, a2, b1, b2 = (t.contiguous() for t in (a1, a2, b1, b2))
-    outa, outb = (_lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair") for o in outs)
+    outa, outb = (_lrelu_out(o, (b, oc, oh, ow), a1, "correlation_lrelu_forward_pair", dtype) for o in outs)
     with torch.cuda.device(a1.device):
-        err = lib().vfi_correlation_lrelu_forward_pair(_ptr(a1), _ptr(a2), _ptr(outa), _planes(outa)[1], _ptr(b1), _ptr(b2),
-                                                       _ptr(outb), _planes(outb)[1], b, c, h, w, pad_size, kernel_size,
-                                                       max_displacement, stride1, stride2, slope, _stream(a1))
+        fn = getattr(lib(), "vfi_correlation_lrelu_forward_pair" + suffix)
+        err = fn(_ptr(a1), _ptr(a2), _ptr(outa), _planes(outa)[1], _ptr(b1), _ptr(b2),
+                 _ptr(outb), _planes(outb)[1], b, c, h, w, pad_size, kernel_size,
+                 max_displacement, stride1, stride2, slope, _stream(a1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_lrelu_forward_pair: the binding returned %d" % err)
     return outa, outb
@@ -834,7 +845,8 @@ def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, ke
                                     negative_slope, want=(True, True, True, True)):
     """(correlation_lrelu_backward(a1, a2, ya, ga, ...), correlation_lrelu_backward(b1, b2, yb, gb, ...)) from ONE
     vfi_correlation_lrelu_backward_pair call.  Returns (grad a1, grad a2, grad b1, grad b2), each written in full and
-    bit-equal to the single call's; None where `want` says so or where that item's gradoutput is None."""
+    bit-equal to the single call's; None where `want` says so or where that item's gradoutput is None.  float32, or bfloat16
+    for every tensor (vfi_correlation_lrelu_backward_pair_bf16)."""
     slope = _slope(negative_slope)
     inputs = (a1, a2, b1, b2)
     b, c, h, w = a1.shape
@@ -843,8 +855,7 @@ def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, ke
             any(g is not None and (tuple(g.shape) != gshape or y is None or tuple(y.shape) != gshape) for y, g in ((ya, ga), (yb, gb))):
         raise RuntimeError("correlation_lrelu_backward_pair: the four inputs must have one shape, and y and the gradoutputs "
                            "the output dimensions")
-    for t in inputs + tuple(t for y, g in ((ya, ga), (yb, gb)) if g is not None for t in (y, g)):
-        _dev(t)
+    dtype, suffix = _bf16_or_f32(*inputs, *(t for y, g in ((ya, ga), (yb, gb)) if g is not None for t in (y, g)))
     a1, a2, b1, b2 = (t.contiguous() for t in inputs)
     (ya, yas), (ga, gas) = ((None, 0), (None, 0)) if ga is None else (_planes(ya), _planes(ga))
     (yb, ybs), (gb, gbs) = ((None, 0), (None, 0)) if gb is None else (_planes(yb), _planes(gb))
@@ -852,10 +863,10 @@ def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, ke
     if all(g is None for g in grads):
         return tuple(grads)
     with torch.cuda.device(a1.device):
-        err = lib().vfi_correlation_lrelu_backward_pair(
-            _ptr(a1), _ptr(a2), _opt(ya), yas, _opt(ga), gas, _opt(grads[0]), _opt(grads[1]),
-            _ptr(b1), _ptr(b2), _opt(yb), ybs, _opt(gb), gbs, _opt(grads[2]), _opt(grads[3]),
-            b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope, _stream(a1))
+        fn = getattr(lib(), "vfi_correlation_lrelu_backward_pair" + suffix)
+        err = fn(_ptr(a1), _ptr(a2), _opt(ya), yas, _opt(ga), gas, _opt(grads[0]), _opt(grads[1]),
+                 _ptr(b1), _ptr(b2), _opt(yb), ybs, _opt(gb), gbs, _opt(grads[2]), _opt(grads[3]),
+                 b, c, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, slope, _stream(a1, dtype))
     if _finish(err) != 0:
         raise RuntimeError("correlation_lrelu_backward_pair: the binding returned %d" % err)
     return tuple(grads)

@@ -811,8 +811,7 @@ __global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__ha
 // (tile + 4 halo, zero padded) in LDS, double-buffered.  The sum runs in the reference's order -- 32 partial sums over
 // tc = l, l + 32, l + 64, added in sequence (correlation_cuda_kernel.cu:162-239, 255-332) -- so the result is corr_backward's
 // and the oracle's bit for bit.  The body is one function: corr_backward_k1 below is one gradient per launch, and
-// corr_backward_k1_pair runs one instance or the other per workgroup.
-typedef float CorrBwdWindow[2][CorrBwdTile::LH][CorrBwdTile::LW];
+// corr_backward_k1_pair runs one instance or the other per workgroup.  (CorrBwdWindow: correlation_dev.h)
 
 // MASK: the 81 values go through LeakyReLU's derivative as they are loaded (CorrGrad: 81 more loads per pixel and channel
 // group, outside the channel loop); the channel loop is the same code either way.
@@ -1332,20 +1331,8 @@ static int correlation_backward_pair_any(
     if (acts && !corr_slope_ok(acts[0].slope)) return VFI_ERR_SHAPE;
     CorrBwdRoles roles = {};
     CorrBwdMasks masks = {};
-    int nroles = 0;
-    for (int i = 0; i < 2; ++i) {
-        if (!gi[i][0] && !gi[i][1]) continue;               // (nothing asked of this item: its inputs may be NULL)
-        if (!in1[i] || !in2[i] || !go[i]) return VFI_ERR_SHAPE;
-        if (acts && !corr_grad_ok(acts[i], (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
-        for (int s = 0; s < 2; ++s) {
-            if (!gi[i][s]) continue;
-            for (int k = 0; k < nroles; ++k)
-                if (roles.r[k].gin == gi[i][s]) return VFI_ERR_SHAPE;
-            if (acts) { masks.y[nroles] = acts[i].y; masks.ystride[nroles] = acts[i].ystride; masks.gstride[nroles] = acts[i].gstride; }
-            roles.r[nroles++] = {s ? in1[i] : in2[i], go[i], gi[i][s], s};      // gradInput1 reads input2, gradInput2 input1
-        }
-    }
-    if (acts) masks.slope = acts[0].slope;
+    const int nroles = corr_backward_roles(in1, in2, go, gi, acts, (int64_t)oc * oh * ow, roles, masks);     // (both items carry the one slope)
+    if (nroles < 0) return VFI_ERR_SHAPE;
     if (nroles == 0) return VFI_OK;
     hipStream_t st = (hipStream_t)stream;
     if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {

@@ -13,6 +13,10 @@
 // The same with PWC-Net's LeakyReLU (vfi_correlation_lrelu_forward_bf16 / _backward_bf16): the kernels below take an epilogue
 // (forward: what is stored, and where an image begins) and a gradient mask (backward: what a gradOutput value becomes as it is
 // loaded); the plain entries instantiate them with the types that do nothing.
+//
+// Two calls of equal shape in one launch (vfi_correlation_[lrelu_]forward_pair_bf16, ..._backward_pair_bf16: the same pyramid
+// level of a frame pair's two flow networks): pair kernels that take a workgroup's item or role from blockIdx and run the same
+// bodies, so every output is its single entry's bit for bit.
 #include "bf16.h"
 #include "correlation_dev.h"
 
@@ -43,6 +47,15 @@ struct CorrBf16Lrelu {
     }
     __device__ __forceinline__ int64_t image(int b, int64_t) const { return (int64_t)b * stride; }
 };
+
+// The tensors of a launch of two calls of equal shape (the pair entries), and the two items' epilogues: each item has its
+// own output base and its own image stride, and the slope is shared.  A pair kernel indexes its own arguments with the
+// workgroup's item -- scalar loads -- and hands the body an epilogue of the single kernels' type.
+struct CorrBf16Items { const bf16_t* in1[2]; const bf16_t* in2[2]; bf16_t* out[2]; };
+struct CorrBf16PlainPair { typedef CorrBf16Plain One; };
+struct CorrBf16LreluPair { typedef CorrBf16Lrelu One; int64_t stride[2]; float slope; };
+__host__ __device__ __forceinline__ CorrBf16Plain corr_bf16_epilogue(const CorrBf16PlainPair&, int) { return {}; }
+__host__ __device__ __forceinline__ CorrBf16Lrelu corr_bf16_epilogue(const CorrBf16LreluPair& e, int item) { return {e.stride[item], e.slope}; }
 
 // What a backward kernel does with a gradOutput value g whose output position holds the saved ACTIVATED output yv, and where
 // the images of gradOutput and y begin.  CorrBf16Grad: nothing, dense.  CorrBf16GradLrelu: g' = yv > 0 ? g :
@@ -107,12 +120,12 @@ struct CorrMfmaTile {
 template <class T, class Epi>
 __device__ __forceinline__ void corr_mfma_bf16_body(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
-    int channel, int h, int w, int oh, int ow, int org, u32x4* lds, const Epi& epi) {
+    int z0, int channel, int h, int w, int oh, int ow, int org, u32x4* lds, const Epi& epi) {
     constexpr int D = T::D, TW = T::TW, TH = T::TH, MT = T::MT, NB = T::NB, BW = T::BW, LH = T::LH, KG = T::KG, NT = T::NT;
     constexpr unsigned OUTSIDE = 0x80000000u;
     const int lane = threadIdx.x, tj = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const int tid = tj * 64 + lane;
-    const int ox0 = blockIdx.x * TW, oy0 = blockIdx.y * TH, b = blockIdx.z;
+    const int ox0 = blockIdx.x * TW, oy0 = blockIdx.y * TH, b = blockIdx.z - z0;
     const int plane = h * w;
     const unsigned plane2 = 2u * (unsigned)plane;
     const bf16_t* f1 = in1 + (int64_t)b * channel * plane;
@@ -241,7 +254,22 @@ __global__ __launch_bounds__(T::NT) void corr_forward_k1_mfma_bf16(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
     int channel, int h, int w, int oh, int ow, int org, Epi epi) {
     __shared__ __attribute__((aligned(16))) u32x4 lds[T::LDS_BYTES / 16];
-    corr_mfma_bf16_body<T>(in1, in2, out, channel, h, w, oh, ow, org, lds, epi);
+    corr_mfma_bf16_body<T>(in1, in2, out, 0, channel, h, w, oh, ow, org, lds, epi);
+}
+
+// Two calls of equal shape in ONE launch (vfi_correlation_forward_pair_bf16: the same pyramid level of a frame pair's two flow
+// networks).  blockIdx.z is item x image, so the item is workgroup-uniform: its three pointers and its epilogue are scalar
+// loads from the argument block at the item's index, and the body knows nothing of items -- an item's bits are those of its
+// own corr_forward_k1_mfma_bf16 launch.
+template <class T, class Epis>
+__global__ __launch_bounds__(T::NT) void corr_forward_k1_mfma_bf16_pair(
+    CorrBf16Items items, Epis epis, int batch, int channel, int h, int w, int oh, int ow, int org) {
+    __shared__ __attribute__((aligned(16))) u32x4 lds[T::LDS_BYTES / 16];
+    const int item = blockIdx.z >= (unsigned)batch ? 1 : 0;                      // (blockIdx.z / batch, of two items)
+    const bf16_t* __restrict__ in1 = items.in1[item];
+    const bf16_t* __restrict__ in2 = items.in2[item];
+    bf16_t* __restrict__ out = items.out[item];
+    corr_mfma_bf16_body<T>(in1, in2, out, item * batch, channel, h, w, oh, ow, org, lds, corr_bf16_epilogue(epis, item));
 }
 typedef CorrMfmaTile<4, 2> CorrMfma;
 
@@ -255,7 +283,7 @@ typedef CorrMfmaTile<4, 2> CorrMfma;
 // address) and cleared by `keep`; eight channels of loads in flight (corr_forward_k1_flat's way, which this kernel stands
 // in for at the small PWC-Net levels).
 template <class Epi>
-__global__ __launch_bounds__(256) void corr_forward_generic_bf16(
+__device__ __forceinline__ void corr_generic_bf16_body(
     const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
     int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1, int s2, int dr, Epi epi) {
     const int64_t total = (int64_t)batch * oc * oh * ow;
@@ -295,6 +323,27 @@ __global__ __launch_bounds__(256) void corr_forward_generic_bf16(
     const int k = 2 * kr + 1;
     const int64_t image = (int64_t)oc * oh * ow;
     out[epi.image(b, image) + (gid - (int64_t)b * image)] = (bf16_t)(epi.pack(acc / (float)(k * k * channel), 0.0f) & 0xffffu);
+}
+
+template <class Epi>
+__global__ __launch_bounds__(256) void corr_forward_generic_bf16(
+    const bf16_t* __restrict__ in1, const bf16_t* __restrict__ in2, bf16_t* __restrict__ out,
+    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1, int s2, int dr, Epi epi) {
+    corr_generic_bf16_body(in1, in2, out, batch, channel, h, w, oc, oh, ow, pad, kr, md, s1, s2, dr, epi);
+}
+
+// Two calls in one launch: the item is blockIdx.y -- a grid dimension of its own, so that it is workgroup-uniform (a flat
+// index over both items' outputs would put two items into the workgroup at the seam) -- and blockIdx.x runs over ONE
+// item's outputs exactly as in the single launch.
+template <class Epis>
+__global__ __launch_bounds__(256) void corr_forward_generic_bf16_pair(
+    CorrBf16Items items, Epis epis, int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s1,
+    int s2, int dr) {
+    const int item = blockIdx.y;
+    const bf16_t* __restrict__ in1 = items.in1[item];
+    const bf16_t* __restrict__ in2 = items.in2[item];
+    bf16_t* __restrict__ out = items.out[item];
+    corr_generic_bf16_body(in1, in2, out, batch, channel, h, w, oc, oh, ow, pad, kr, md, s1, s2, dr, corr_bf16_epilogue(epis, item));
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward
@@ -363,68 +412,55 @@ __global__ __launch_bounds__(256) void corr_backward_bf16(
 // owns one pixel of a 64x4 tile, its 81 gradOutput values widened into registers for all channels of the group; per channel
 // the workgroup stages the other map's 12x72 window, widened, in LDS (double-buffered, zero padded).  The same float32
 // terms in the same order as corr_backward_bf16, so the same bits.  (A term the reference skips -- gradInput2, displaced
-// position outside the frame -- has g = 0 and meets the window's zero padding: fma(0, 0, s) = s.)
+// position outside the frame -- has g = 0 and meets the window's zero padding: fma(0, 0, s) = s.)  The body has one
+// definition, correlation_bf16_bwd_k1.inc, as corr_backward_k1_body is one: corr_backward_k1_bf16 is one gradient per launch,
+// and the pair kernels run one instance of the device function or the other per workgroup.  The single-gradient kernels
+// include the statements themselves: called through the function they compiled to slower code (see the .inc).
+template <bool SECOND, class Act>
+__device__ __forceinline__ void corr_backward_k1_bf16_body(
+    CorrBwdWindow& win, const CorrBwdTile& t, const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout,
+    bf16_t* __restrict__ gin, int channel, int h, int w, const Act& act) {
+#include "correlation_bf16_bwd_k1.inc"
+}
+
 template <bool SECOND, class Act>
 __global__ __launch_bounds__(256) void corr_backward_k1_bf16(
     const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
     int channel, int h, int w, int groups, int ch_per_group, Act act) {
-    typedef CorrBwdTile T;
-    constexpr int MD = T::MD, D = T::D, OC = T::OC;
-    __shared__ float win[2][T::LH][T::LW];
-    const T t(channel, groups, ch_per_group);
-    const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
-    const int bx = t.x0 + px, by = t.y0 + py;
-    const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
-    const bool in = bx < w && by < h;
-    const int64_t plane = (int64_t)h * w;
-    const bf16_t* go = gout + act.g_image(n, OC * plane);
-    const bf16_t* yo = act.y_image(n);
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group);
+#include "correlation_bf16_bwd_k1.inc"
+}
 
-    float g[OC];
-#pragma unroll
-    for (int tc = 0; tc < OC; ++tc) {
-        const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
-        if constexpr (Act::MASK) {
-            // (a skipped term loads element 0 of its image -- a valid address -- and drops it, so that the loads of a
-            //  displacement row of gradOutput and y go out together: corr_backward_k1_body, correlation.hip)
-            const bool ok = in && gy >= 0 && gy < h && gx >= 0 && gx < w;
-            const int64_t at = ok ? (int64_t)tc * plane + (int64_t)gy * w + gx : 0;
-            const bf16_t gv = go[at], yv = yo[at];
-            g[tc] = ok ? act(gv, yv) : 0.0f;
-            if (tc % D == D - 1) __builtin_amdgcn_sched_barrier(0);
-        } else {
-            g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? bf16_widen(go[(int64_t)tc * plane + (int64_t)gy * w + gx]) : 0.0f;
-        }
-    }
+// Up to four gradients of two calls of equal shape in ONE launch (vfi_correlation_backward_pair_bf16), as corr_backward_k1_pair
+// (correlation.hip): a workgroup's role comes from blockIdx.z once (CorrBwdTile), its pointers are scalar loads from the
+// argument block at the role's index, and one scalar branch picks the instance of the body.  Channel groups only partition
+// the channels, so a gradient's bits are those of its own corr_backward_k1_bf16 launch.
+typedef CorrBwdRolesT<bf16_t> CorrBf16BwdRoles;
+typedef CorrBwdMasksT<bf16_t> CorrBf16BwdMasks;
 
-    auto stage = [&](int c, int buf) {
-        const bf16_t* of = other + ((int64_t)n * channel + c) * plane;
-        for (int e = tid; e < T::LH * T::LW; e += 256) {
-            const T::Elem p = t.window(e);
-            win[buf][p.r][p.col] = (p.gy >= 0 && p.gy < h && p.gx >= 0 && p.gx < w) ? bf16_widen(of[(int64_t)p.gy * w + p.gx]) : 0.0f;
-        }
-    };
-    if (c_begin >= c_end) return;
-    stage(c_begin, 0);
-    const float nelems = (float)channel;
-    for (int c = c_begin; c < c_end; ++c) {
-        const int buf = (c - c_begin) & 1;
-        __syncthreads();                                    // window c has been written; window c - 1 has been read
-        if (c + 1 < c_end) stage(c + 1, buf ^ 1);
-        float r = 0.0f;
-#pragma unroll
-        for (int l = 0; l < 32; ++l) {
-            float s = 0.0f;
-#pragma unroll
-            for (int tc = l; tc < OC; tc += 32) {
-                const int tj = tc / D, ti = tc % D;
-                const float v = SECOND ? win[buf][py + 2 * MD - tj][px + 2 * MD - ti] : win[buf][py + tj][px + ti];
-                s = fmaf(g[tc], v, s);
-            }
-            r += s;
-        }
-        if (in) gin[((int64_t)n * channel + c) * plane + (int64_t)by * w + bx] = bf16_rne(r / nelems);
-    }
+__global__ __launch_bounds__(256) void corr_backward_k1_pair_bf16(CorrBf16BwdRoles roles, int channel, int h, int w, int groups,
+                                                                  int ch_per_group) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group, roles.per_role);
+    const bf16_t* __restrict__ other = roles.r[t.role].other;
+    const bf16_t* __restrict__ gout = roles.r[t.role].gout;
+    bf16_t* __restrict__ gin = roles.r[t.role].gin;
+    if (roles.r[t.role].second) corr_backward_k1_bf16_body<true>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
+    else corr_backward_k1_bf16_body<false>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
+}
+
+// the masked twin (vfi_correlation_lrelu_backward_pair_bf16): a role's y and strides are scalar loads at the role's index too
+__global__ __launch_bounds__(256) void corr_lrelu_backward_k1_pair_bf16(CorrBf16BwdRoles roles, CorrBf16BwdMasks masks, int channel,
+                                                                        int h, int w, int groups, int ch_per_group) {
+    __shared__ CorrBwdWindow win;
+    const CorrBwdTile t(channel, groups, ch_per_group, roles.per_role);
+    const bf16_t* __restrict__ other = roles.r[t.role].other;
+    const bf16_t* __restrict__ gout = roles.r[t.role].gout;
+    bf16_t* __restrict__ gin = roles.r[t.role].gin;
+    const CorrBf16GradLrelu act = {masks.y[t.role], masks.ystride[t.role], masks.gstride[t.role], masks.slope};
+    if (roles.r[t.role].second) corr_backward_k1_bf16_body<true>(win, t, other, gout, gin, channel, h, w, act);
+    else corr_backward_k1_bf16_body<false>(win, t, other, gout, gin, channel, h, w, act);
 }
 
 }  // namespace vfi
@@ -450,57 +486,88 @@ static bool corr_bf16_mfma_fits(int batch, int h, int w, int oh) {
     return (int64_t)h * w * 2 * CorrMfma::KC < INT_MAX && batch <= 65535 && (oh + CorrMfma::TH - 1) / CorrMfma::TH <= 65535;
 }
 
-template <class T, class Epi = CorrBf16Plain>
-static int corr_bf16_launch_mfma(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oh,
-                                 int ow, int org, hipStream_t st, const Epi& epi = Epi{}) {
-    const dim3 grid((ow + T::TW - 1) / T::TW, (oh + T::TH - 1) / T::TH, batch);
-    hipLaunchKernelGGL((corr_forward_k1_mfma_bf16<T, Epi>), grid, dim3(64, T::D, 1), 0, st, (const bf16_t*)input1, (const bf16_t*)input2,
-                       (bf16_t*)output, channel, h, w, oh, ow, org, epi);
-    return launch_status();
+// The launchers take one item or two (nitems; `batch` is one item's).  Two items are ONE launch of the pair kernel where the
+// doubled blockIdx.z fits; otherwise, and for one item, the single kernel per item -- the same bits either way.
+template <class T, class Epis>
+static int corr_bf16_launch_mfma(const CorrBf16Items& t, int nitems, const Epis& epis, int batch, int channel, int h, int w, int oh,
+                                 int ow, int org, hipStream_t st) {
+    const unsigned tx = (ow + T::TW - 1) / T::TW, ty = (oh + T::TH - 1) / T::TH;
+    if (nitems == 2 && corr_bf16_mfma_fits(2 * batch, h, w, oh)) {
+        hipLaunchKernelGGL((corr_forward_k1_mfma_bf16_pair<T, Epis>), dim3(tx, ty, 2 * batch), dim3(64, T::D, 1), 0, st, t, epis, batch,
+                           channel, h, w, oh, ow, org);
+        return launch_status();
+    }
+    for (int i = 0; i < nitems; ++i) {
+        hipLaunchKernelGGL((corr_forward_k1_mfma_bf16<T, typename Epis::One>), dim3(tx, ty, batch), dim3(64, T::D, 1), 0, st, t.in1[i],
+                           t.in2[i], t.out[i], channel, h, w, oh, ow, org, corr_bf16_epilogue(epis, i));
+        if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
+    }
+    return VFI_OK;
 }
 
-template <class Epi = CorrBf16Plain>
-static int corr_bf16_launch_generic(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int oc,
+template <class Epis>
+static int corr_bf16_launch_generic(const CorrBf16Items& t, int nitems, const Epis& epis, int batch, int channel, int h, int w, int oc,
                                     int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
-                                    hipStream_t st, const Epi& epi = Epi{}) {
-    const int64_t total = (int64_t)batch * oc * oh * ow;
+                                    hipStream_t st) {
+    const int64_t total = (int64_t)batch * oc * oh * ow;                 // of one item: blockIdx.x
     if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipLaunchKernelGGL(corr_forward_generic_bf16<Epi>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)input1,
-                       (const bf16_t*)input2, (bf16_t*)output, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2,
-                       max_displacement, stride1, stride2, max_displacement / stride2, epi);
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
+    if (nitems == 2) {
+        hipLaunchKernelGGL(corr_forward_generic_bf16_pair<Epis>, dim3(blocks, 2), dim3(256), 0, st, t, epis, batch, channel, h, w, oc, oh,
+                           ow, pad_size, kr, max_displacement, stride1, stride2, dr);
+        return launch_status();
+    }
+    hipLaunchKernelGGL(corr_forward_generic_bf16<typename Epis::One>, dim3(blocks), dim3(256), 0, st, t.in1[0], t.in2[0], t.out[0], batch,
+                       channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride1, stride2, dr, corr_bf16_epilogue(epis, 0));
     return launch_status();
 }
 
-// the forward of both entries: the checks, the kernel choice, one launch
-template <class Epi>
-static int corr_bf16_forward(const void* input1, const void* input2, void* output, int batch, int channel, int h, int w, int pad_size,
-                             int kernel_size, int max_displacement, int stride1, int stride2, vfi_stream_t stream, const Epi& epi,
-                             int64_t image_stride) {
+// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
+static bool corr_bf16_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
+
+static bool corr_bf16_epilogue_ok(const CorrBf16PlainPair&, int, int64_t) { return true; }
+static bool corr_bf16_epilogue_ok(const CorrBf16LreluPair& e, int nitems, int64_t image) {
+    return corr_bf16_slope_ok(e.slope) && e.stride[0] >= image && e.stride[nitems - 1] >= image;
+}
+
+// The forward of all four entries: the checks, the kernel choice, one launch.  `batch` is one item's, and the choice is made
+// on ONE item's tile count, for a pair too: the MFMA kernel's float32 addition order is the hardware's and not the generic
+// kernel's chain, so only the single entry's own choice gives each item of a pair the single entry's bits.  (The float32
+// pair chooses on the pair's count: its kernels all give the same bits.)
+template <class Epis>
+static int corr_bf16_forward(const CorrBf16Items& t, int nitems, const Epis& epis, int batch, int channel, int h, int w, int pad_size,
+                             int kernel_size, int max_displacement, int stride1, int stride2, vfi_stream_t stream) {
     int oc, oh, ow;
-    if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
-                   &oc, &oh, &ow))
+    const int last = nitems - 1;
+    if (corr_check({t.in1[0], t.in2[0], t.out[0], t.in1[last], t.in2[last], t.out[last]}, batch, channel, h, w, pad_size, kernel_size,
+                   max_displacement, stride1, stride2, false, &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
-    if (image_stride < (int64_t)oc * oh * ow) return VFI_ERR_SHAPE;     // (the plain entry passes its dense stride)
+    if (nitems == 2 && t.out[0] == t.out[1]) return VFI_ERR_SHAPE;
+    if (!corr_bf16_epilogue_ok(epis, nitems, (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
     if (corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) && corr_bf16_mfma_fits(batch, h, w, oh)) {
         const int64_t mfma_tiles = (int64_t)((ow + CorrMfma::TW - 1) / CorrMfma::TW) * ((oh + CorrMfma::TH - 1) / CorrMfma::TH) * batch;
         if (mfma_tiles >= corr_bf16_mfma_threshold) {
-            return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size,
-                                                   (hipStream_t)stream, epi);
+            return corr_bf16_launch_mfma<CorrMfma>(t, nitems, epis, batch, channel, h, w, oh, ow, max_displacement - pad_size,
+                                                   (hipStream_t)stream);
         }
     }
-    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
-                                    stride1, stride2, (hipStream_t)stream, epi);
+    return corr_bf16_launch_generic(t, nitems, epis, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement, stride1,
+                                    stride2, (hipStream_t)stream);
+}
+
+static CorrBf16Items corr_bf16_items(const void* input1_a, const void* input2_a, void* output_a, const void* input1_b = nullptr,
+                                     const void* input2_b = nullptr, void* output_b = nullptr) {
+    return {{(const bf16_t*)input1_a, (const bf16_t*)input1_b}, {(const bf16_t*)input2_a, (const bf16_t*)input2_b},
+            {(bf16_t*)output_a, (bf16_t*)output_b}};
 }
 
 extern "C" int vfi_correlation_forward_bf16(const void* input1, const void* input2, void* output, int batch, int channel,
                                              int h, int w, int pad_size, int kernel_size, int max_displacement,
                                              int stride1, int stride2, vfi_stream_t stream) {
-    return corr_bf16_forward(input1, input2, output, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
-                             stream, CorrBf16Plain{}, INT64_MAX);
+    return corr_bf16_forward(corr_bf16_items(input1, input2, output), 1, CorrBf16PlainPair{}, batch, channel, h, w, pad_size, kernel_size,
+                             max_displacement, stride1, stride2, stream);
 }
-
-// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
-static bool corr_bf16_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
 
 // vfi_correlation_forward_bf16 with PWC-Net's LeakyReLU applied to every stored value, into an output whose images lie
 // output_batch_stride elements apart: the same kernels and the same choice, with the epilogue compiled in.
@@ -508,9 +575,31 @@ extern "C" int vfi_correlation_lrelu_forward_bf16(const void* input1, const void
                                                    int batch, int channel, int h, int w, int pad_size, int kernel_size,
                                                    int max_displacement, int stride1, int stride2, float negative_slope,
                                                    vfi_stream_t stream) {
-    if (!corr_bf16_slope_ok(negative_slope)) return VFI_ERR_SHAPE;
-    return corr_bf16_forward(input1, input2, output, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2,
-                             stream, CorrBf16Lrelu{output_batch_stride, negative_slope}, output_batch_stride);
+    return corr_bf16_forward(corr_bf16_items(input1, input2, output), 1,
+                             CorrBf16LreluPair{{output_batch_stride, output_batch_stride}, negative_slope}, batch, channel, h, w, pad_size,
+                             kernel_size, max_displacement, stride1, stride2, stream);
+}
+
+// Two forward calls of equal shape in ONE launch -- the same pyramid level of the two flow networks of a frame pair: each
+// output is its single entry's, bit for bit, for every shape (the kernel is the one the single entry takes for ONE item).
+extern "C" int vfi_correlation_forward_pair_bf16(const void* input1_a, const void* input2_a, void* output_a,
+                                                  const void* input1_b, const void* input2_b, void* output_b,
+                                                  int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                                                  int max_displacement, int stride1, int stride2, vfi_stream_t stream) {
+    return corr_bf16_forward(corr_bf16_items(input1_a, input2_a, output_a, input1_b, input2_b, output_b), 2, CorrBf16PlainPair{}, batch,
+                             channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream);
+}
+
+extern "C" int vfi_correlation_lrelu_forward_pair_bf16(const void* input1_a, const void* input2_a, void* output_a,
+                                                        int64_t output_a_batch_stride,
+                                                        const void* input1_b, const void* input2_b, void* output_b,
+                                                        int64_t output_b_batch_stride,
+                                                        int batch, int channel, int h, int w, int pad_size, int kernel_size,
+                                                        int max_displacement, int stride1, int stride2, float negative_slope,
+                                                        vfi_stream_t stream) {
+    return corr_bf16_forward(corr_bf16_items(input1_a, input2_a, output_a, input1_b, input2_b, output_b), 2,
+                             CorrBf16LreluPair{{output_a_batch_stride, output_b_batch_stride}, negative_slope}, batch, channel, h, w,
+                             pad_size, kernel_size, max_displacement, stride1, stride2, stream);
 }
 
 // One kernel of vfi_correlation_forward_bf16 whatever the tile count (internal: the tests and tools/bench_corr_bf16.py run
@@ -522,12 +611,14 @@ extern "C" int vfi_correlation_forward_bf16_kernel(int which, const void* input1
     if (corr_check({input1, input2, output}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, false,
                    &oc, &oh, &ow))
         return VFI_ERR_SHAPE;
+    const CorrBf16Items t = corr_bf16_items(input1, input2, output);
     if (which == 0) {
         if (!corr_bf16_is_pwc(kernel_size, max_displacement, stride1, stride2) || !corr_bf16_mfma_fits(batch, h, w, oh)) return VFI_ERR_SHAPE;
-        return corr_bf16_launch_mfma<CorrMfma>(input1, input2, output, batch, channel, h, w, oh, ow, max_displacement - pad_size, (hipStream_t)stream);
+        return corr_bf16_launch_mfma<CorrMfma>(t, 1, CorrBf16PlainPair{}, batch, channel, h, w, oh, ow, max_displacement - pad_size,
+                                               (hipStream_t)stream);
     }
     if (which != 1) return VFI_ERR_SHAPE;
-    return corr_bf16_launch_generic(input1, input2, output, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
+    return corr_bf16_launch_generic(t, 1, CorrBf16PlainPair{}, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size, max_displacement,
                                     stride1, stride2, (hipStream_t)stream);
 }
 
@@ -590,4 +681,75 @@ extern "C" int vfi_correlation_lrelu_backward_bf16(const void* input1, const voi
     const CorrBf16GradLrelu act = {(const bf16_t*)y, y_batch_stride, gradoutput_batch_stride, negative_slope};
     return corr_bf16_backward(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
                               max_displacement, stride1, stride2, stream, act, y_batch_stride, gradoutput_batch_stride);
+}
+
+// The backward of two calls of equal shape with any subset of the four gradients, as correlation_backward_pair_any
+// (correlation.hip) and with its compaction: PWC-Net's configuration is ONE launch of the pair kernel whose roles are the
+// requested gradients, the channel groups sized on the whole launch (tiles x batch x roles).  Any other configuration, or
+// roles x batch x groups beyond a grid's z: one launch per requested gradient with the kernels
+// vfi_correlation_backward_bf16 uses.  Either way a gradient's bits are that entry's.  `acts` (or NULL): the two items' masks.
+static int corr_bf16_backward_pair(const bf16_t* const (&in1)[2], const bf16_t* const (&in2)[2], const bf16_t* const (&go)[2],
+                                   bf16_t* const (&gi)[2][2], const CorrBf16GradLrelu* acts, int batch, int channel, int h, int w,
+                                   int pad_size, int kernel_size, int max_displacement, int stride1, int stride2, vfi_stream_t stream) {
+    int oc, oh, ow;
+    if (corr_check({}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, true, &oc, &oh, &ow))
+        return VFI_ERR_SHAPE;
+    if (acts && !corr_bf16_slope_ok(acts[0].slope)) return VFI_ERR_SHAPE;
+    CorrBf16BwdRoles roles = {};
+    CorrBf16BwdMasks masks = {};
+    const int nroles = corr_backward_roles(in1, in2, go, gi, acts, (int64_t)oc * oh * ow, roles, masks);
+    if (nroles < 0) return VFI_ERR_SHAPE;
+    if (nroles == 0) return VFI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {
+        int ch_per_group;
+        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch * nroles, channel, &ch_per_group);
+        if (groups) {
+            roles.per_role = batch * groups;
+            const dim3 grid((w + 63) / 64, (h + 3) / 4, nroles * roles.per_role);
+            if (acts) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, masks, channel, h, w, groups, ch_per_group);
+            else hipLaunchKernelGGL(corr_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
+            return launch_status();
+        }
+    }
+    for (int k = 0; k < nroles; ++k) {
+        const CorrBwdRoleT<bf16_t>& r = roles.r[k];
+        const CorrBf16GradLrelu act = {masks.y[k], masks.ystride[k], masks.gstride[k], masks.slope};
+        const int err = acts ? corr_bf16_backward_one(r.second != 0, r.other, r.gout, r.gin, batch, channel, h, w, oc, oh, ow, pad_size,
+                                                      kernel_size, max_displacement, stride2, st, act)
+                             : corr_bf16_backward_one(r.second != 0, r.other, r.gout, r.gin, batch, channel, h, w, oc, oh, ow, pad_size,
+                                                      kernel_size, max_displacement, stride2, st, CorrBf16Grad{});
+        if (err != VFI_OK) return err;
+    }
+    return VFI_OK;
+}
+
+extern "C" int vfi_correlation_backward_pair_bf16(
+    const void* input1_a, const void* input2_a, const void* gradoutput_a, void* gradinput1_a, void* gradinput2_a,
+    const void* input1_b, const void* input2_b, const void* gradoutput_b, void* gradinput1_b, void* gradinput2_b,
+    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+    vfi_stream_t stream) {
+    const bf16_t* const in1[2] = {(const bf16_t*)input1_a, (const bf16_t*)input1_b};
+    const bf16_t* const in2[2] = {(const bf16_t*)input2_a, (const bf16_t*)input2_b};
+    const bf16_t* const go[2] = {(const bf16_t*)gradoutput_a, (const bf16_t*)gradoutput_b};
+    bf16_t* const gi[2][2] = {{(bf16_t*)gradinput1_a, (bf16_t*)gradinput2_a}, {(bf16_t*)gradinput1_b, (bf16_t*)gradinput2_b}};
+    return corr_bf16_backward_pair(in1, in2, go, gi, nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
+                                   stride2, stream);
+}
+
+extern "C" int vfi_correlation_lrelu_backward_pair_bf16(
+    const void* input1_a, const void* input2_a, const void* y_a, int64_t y_a_batch_stride, const void* gradoutput_a,
+    int64_t gradoutput_a_batch_stride, void* gradinput1_a, void* gradinput2_a,
+    const void* input1_b, const void* input2_b, const void* y_b, int64_t y_b_batch_stride, const void* gradoutput_b,
+    int64_t gradoutput_b_batch_stride, void* gradinput1_b, void* gradinput2_b,
+    int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
+    float negative_slope, vfi_stream_t stream) {
+    const bf16_t* const in1[2] = {(const bf16_t*)input1_a, (const bf16_t*)input1_b};
+    const bf16_t* const in2[2] = {(const bf16_t*)input2_a, (const bf16_t*)input2_b};
+    const bf16_t* const go[2] = {(const bf16_t*)gradoutput_a, (const bf16_t*)gradoutput_b};
+    bf16_t* const gi[2][2] = {{(bf16_t*)gradinput1_a, (bf16_t*)gradinput2_a}, {(bf16_t*)gradinput1_b, (bf16_t*)gradinput2_b}};
+    const CorrBf16GradLrelu acts[2] = {{(const bf16_t*)y_a, y_a_batch_stride, gradoutput_a_batch_stride, negative_slope},
+                                       {(const bf16_t*)y_b, y_b_batch_stride, gradoutput_b_batch_stride, negative_slope}};
+    return corr_bf16_backward_pair(in1, in2, go, gi, acts, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
+                                   stride2, stream);
 }

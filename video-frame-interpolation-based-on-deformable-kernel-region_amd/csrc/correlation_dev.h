@@ -108,14 +108,44 @@ struct CorrGrad {
         else return g;
     }
 };
-// the masks of a vfi_correlation_lrelu_backward_pair launch, by role (CorrBwdRoles)
-struct CorrBwdMasks { const float* y[4]; int64_t ystride[4], gstride[4]; float slope; };
+// the masks of a vfi_correlation_lrelu_backward_pair launch, by role (CorrBwdRoles); E: the storage type (float, or the
+// bfloat16 bits of vfi_correlation_lrelu_backward_pair_bf16)
+template <class E>
+struct CorrBwdMasksT { const E* y[4]; int64_t ystride[4], gstride[4]; float slope; };
+typedef CorrBwdMasksT<float> CorrBwdMasks;
 
 // The gradients of one vfi_correlation_backward_pair launch: a role is one requested gradient of one item -- the map its
 // window is staged from, the item's gradOutput, where it goes, and which of the two gradients it is.  The host compacts the
 // requested ones (at most four) to the front; role i owns blockIdx.z in [i * per_role, (i + 1) * per_role).
-struct CorrBwdRole { const float* other; const float* gout; float* gin; int second; };
-struct CorrBwdRoles { CorrBwdRole r[4]; int per_role; };
+template <class E>
+struct CorrBwdRoleT { const E* other; const E* gout; E* gin; int second; };
+template <class E>
+struct CorrBwdRolesT { CorrBwdRoleT<E> r[4]; int per_role; };
+typedef CorrBwdRolesT<float> CorrBwdRoles;
+
+// The host's compaction, for either storage type: the requested gradients of the two items become roles 0 .. n - 1, each
+// with its item's mask (`acts`, or NULL for the unmasked entries: two structs with y, ystride, gstride and slope).  An item
+// with nothing requested is skipped and may be all NULL.  Returns n, or -1 for what the entries refuse: a requested
+// gradient whose item lacks an input, its gradOutput or its y, a mask stride below `image` elements, two equal outputs.
+template <class E, class Act>
+inline int corr_backward_roles(const E* const (&in1)[2], const E* const (&in2)[2], const E* const (&go)[2], E* const (&gi)[2][2],
+                               const Act* acts, int64_t image, CorrBwdRolesT<E>& roles, CorrBwdMasksT<E>& masks) {
+    int nroles = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (!gi[i][0] && !gi[i][1]) continue;               // (nothing asked of this item: its inputs may be NULL)
+        if (!in1[i] || !in2[i] || !go[i]) return -1;
+        if (acts && (!acts[i].y || acts[i].ystride < image || acts[i].gstride < image)) return -1;
+        for (int s = 0; s < 2; ++s) {
+            if (!gi[i][s]) continue;
+            for (int k = 0; k < nroles; ++k)
+                if (roles.r[k].gin == gi[i][s]) return -1;
+            if (acts) { masks.y[nroles] = acts[i].y; masks.ystride[nroles] = acts[i].ystride; masks.gstride[nroles] = acts[i].gstride; }
+            roles.r[nroles++] = {s ? in1[i] : in2[i], go[i], gi[i][s], s};      // gradInput1 reads input2, gradInput2 input1
+        }
+    }
+    if (acts) masks.slope = acts[0].slope;
+    return nroles;
+}
 
 // The tile of the tiled backward kernels (PWC-Net's configuration: k == 1, strides 1, pad == md == 4): a workgroup owns 64x4
 // pixels of one image and one channel group, and stages the other map's window (tile + 4 halo, zero padded) per channel.
@@ -139,6 +169,8 @@ struct CorrBwdTile {
         return {r, col, y0 - MD + r, x0 - MD + col};
     }
 };
+// the two staged windows of a workgroup, float for every storage type (bfloat16 is widened as it is staged)
+typedef float CorrBwdWindow[2][CorrBwdTile::LH][CorrBwdTile::LW];
 
 // Host side, defined in correlation.hip and shared with correlation_bf16.hip: the checks every entry makes before it
 // launches, and the tiled backward kernels' split of the channels into groups.

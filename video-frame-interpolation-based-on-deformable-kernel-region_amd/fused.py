@@ -751,7 +751,8 @@ def warp_corr(c1, c2, flo, align_corners=True, one_launch=False):
 class _CorrPair(torch.autograd.Function):
     """`corr_pair` with its backward: the forward is the one vfi_correlation_forward_pair launch, the backward ONE
     vfi_correlation_backward_pair call for the gradients autograd needs -- each bit-equal to `_Corr`'s.  A cost volume
-    the loss did not use arrives as None (not as zeros), and its item's gradients are None at no cost."""
+    the loss did not use arrives as None (not as zeros), and its item's gradients are None at no cost.  float32 or
+    bfloat16 (all tensors of one dtype: `cabi.correlation_forward_pair` / `correlation_backward_pair` dispatch on it)."""
 
     @staticmethod
     def forward(ctx, c1_a, c2_a, c1_b, c2_b):
@@ -772,7 +773,11 @@ def corr_pair(c1_a, c2_a, c1_b, c2_b):
     300 for the (I0, I1) network and again for (I1, I0): networks/DAIN.py:196-202) in one launch; returns both cost volumes.
     Differentiable when grad mode is on and one of the four inputs requires grad: the backward is then ONE call for the
     gradients that are needed (each bit-equal to the single correlation's; reproducible).  Otherwise the plain forward
-    launch (no grad_fn).  float32 only: bfloat16 and float16 tensors raise (the single correlation takes them)."""
+    launch (no grad_fn).  float32 only, as it has always been: bfloat16 and float16 tensors raise.  On bfloat16 the pair is
+    `corr_pair_lrelu` (what a PWC-Net level needs) or, without the activation, `_CorrPair.apply(c1_a, c2_a, c1_b, c2_b)`
+    (trainable) / `cabi.correlation_forward_pair`: one launch each way, every tensor bit-equal to the single bfloat16
+    correlation's."""
+    _float32_only("corr_pair", "corr_pair_lrelu and _CorrPair.apply take bfloat16", c1_a, c2_a, c1_b, c2_b)
     if _wants_grad(c1_a, c2_a, c1_b, c2_b):
         return _CorrPair.apply(c1_a, c2_a, c1_b, c2_b)
     return cabi.correlation_forward_pair(c1_a, c2_a, c1_b, c2_b, 4, 1, 4, 1, 1)
@@ -802,7 +807,7 @@ class _CorrLrelu(torch.autograd.Function):
 class _CorrPairLrelu(torch.autograd.Function):
     """`_CorrPair` with the LeakyReLU fused into both directions: one forward launch, ONE
     vfi_correlation_lrelu_backward_pair call for the gradients autograd needs.  A cost volume the loss did not use arrives
-    as None, and its item's gradients are None at no cost."""
+    as None, and its item's gradients are None at no cost.  float32 or bfloat16, as `_CorrLrelu`."""
 
     @staticmethod
     def forward(ctx, c1_a, c2_a, c1_b, c2_b, slope):
@@ -830,7 +835,7 @@ def corr_lrelu(c1, c2, negative_slope=0.1, out=None):
     the bits of F.leaky_relu on the correlation's output.  Differentiable when grad mode is on and an input requires grad
     (one backward call, which masks the gradient as it loads it and takes torch.cat's strided gradient without a copy).
     Otherwise the plain launch, and out= may name where to write: buf[:, k:k + 81] of the contiguous NCHW buffer the
-    reference would get from `torch.cat((corr, ...), 1)`.  float32 only, as `corr_pair_lrelu` is: bfloat16 and float16 tensors
+    reference would get from `torch.cat((corr, ...), 1)`.  float32 only: bfloat16 and float16 tensors
     raise, as they always have.  On bfloat16 use `warp_corr_lrelu` (the warped levels), and for a level without a warp
     `_CorrLrelu.apply(c1, c2, slope)` (trainable) or `cabi.correlation_lrelu_forward(..., out=)`: the bits of F.leaky_relu on
     the bfloat16 cost volume -- the mean rounded first, the activation rounded again."""
@@ -858,7 +863,9 @@ def corr_pair_lrelu(c1_a, c2_a, c1_b, c2_b, negative_slope=0.1, out=None):
     """`corr_pair` followed by the reference's LeakyReLU on both cost volumes, from the one launch.  Differentiable when
     grad mode is on and one of the four inputs requires grad: ONE backward call for the gradients that are needed, each
     bit-equal to `F.leaky_relu(corr_pair(...))`'s.  Otherwise the plain launch; out= is then a pair of destinations
-    (either may be None), each as `corr_lrelu`'s."""
+    (either may be None), each as `corr_lrelu`'s.  float32, or bfloat16 for all four features (and out=): the level of both
+    flow networks under torch.autocast(dtype=torch.bfloat16) in one launch each way, every tensor bit-equal to
+    `_CorrLrelu.apply`'s on its item -- F.leaky_relu on the bfloat16 cost volume, and autograd through it.  float16 raises."""
     if _wants_grad(c1_a, c2_a, c1_b, c2_b):
         _no_out_in_grad_mode(out, "corr_pair_lrelu")
         return _CorrPairLrelu.apply(c1_a, c2_a, c1_b, c2_b, float(negative_slope))
