@@ -9,7 +9,8 @@
  * and the ctypes loader in the package are both thin callers of this ABI.
  *
  * Conventions (kept from the reference bindings unless stated):
- *  - tensors are float32, NCHW, innermost (w) stride 1; `*_s` arguments are the
+ *  - tensors are float32, NCHW, innermost (w) stride 1 (the one exception: the
+ *    vfi_filterinterp_forward_ori_nhwc_* entries, which say so); `*_s` arguments are the
  *    batch / channel / row strides IN ELEMENTS (int64: a 196-channel 4K tensor
  *    overflows the reference's 32-bit offsets for batch >= 2);
  *  - all pointers are DEVICE pointers valid on the device `stream` belongs to;
@@ -138,6 +139,46 @@ int vfi_filterinterp_forward_ori_multi_to_bf16(const void* input1_bf16, const fl
                                                int batch, int channel, int h, int w, int filter_channels,
                                                vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides s_out,
                                                vfi_stream_t stream);
+
+/* ---- channels_last (NHWC) images: the one exception to "NCHW, innermost stride 1" above ----
+ * The context warp for a network that keeps its activations in torch.channels_last (the layout 16-bit convolutions are
+ * usually run in): vfi_filterinterp_forward_ori_multi_to[_bf16] on an image and destinations whose CHANNEL stride is 1,
+ * without a .contiguous() copy of the image on the way in and a channels_last copy of every output on the way out.
+ * Forward only.
+ *   input1, outputs[t]   [batch, channel, h, w] with channel stride 1; batch, row and pixel strides in ELEMENTS in a
+ *                        vfi_strides_nhwc.  input1 (s1) may be a dense channels_last tensor or a channel slice of a wider
+ *                        one.  Every output has the layout s_out, which is its own: all three strides are free, so
+ *                        buf[:, 45:45 + channel] of a channels_last [batch, 437, h, w] buffer is a legal destination.
+ *   flows[t], input3     float32, four element strides each (s2 for every flow, s3): NCHW and channels_last are both
+ *                        accepted.  Per pixel they are 2 + filter_channels scalar reads shared by all channels.
+ * Values: every output element is, bit for bit, what the NCHW entry writes for the same logical tensors --
+ * vfi_filterinterp_forward_ori_multi in float32, vfi_filterinterp_forward_ori_multi_to_bf16 in bfloat16 (bf16_rne of the
+ * float32 result on the widened image).  NaN stays NaN at the same positions; an invalid pixel copies the input's bits
+ * through; every filter_channels >= 1 is accepted (filter_size 4 reads the first 16 filter channels, as there).
+ * Alignment: an access is 16, 8 or 4 bytes wide or one element, the widest that divides the address of input1, the address
+ * of EVERY output and every stride of s1 and s_out that the shape uses (a dense bfloat16 tensor of 196 channels: 8 bytes;
+ * an odd channel offset or an odd pixel stride: one element).  No misaligned vector access is issued, and every width
+ * writes the same bits.  channel need not be a multiple of the width.
+ * Refusals, all VFI_ERR_SHAPE before any launch: a null pointer (a null entry of flows or outputs included), nflows < 1,
+ * batch, channel, h, w or filter_channels < 1, batch > 65535, more than 2^28 tiles of 32 x 4 pixels.  The destinations
+ * must not overlap input1, the flows, input3 or each other: documented, not checked, as for the entries above.  One
+ * launch per flow, no allocation, no synchronisation: legal inside a stream capture. */
+typedef struct vfi_strides_nhwc {
+    int64_t b, h, w;                  /* channel stride is 1 by contract */
+} vfi_strides_nhwc;
+typedef struct vfi_strides4 {
+    int64_t b, c, h, w;
+} vfi_strides4;
+int vfi_filterinterp_forward_ori_nhwc_multi_to(const float* input1, const float* const* flows, const float* input3,
+                                               float* const* outputs, int nflows,
+                                               int batch, int channel, int h, int w, int filter_channels,
+                                               vfi_strides_nhwc s1, vfi_strides4 s2, vfi_strides4 s3,
+                                               vfi_strides_nhwc s_out, vfi_stream_t stream);
+int vfi_filterinterp_forward_ori_nhwc_multi_to_bf16(const void* input1_bf16, const float* const* flows, const float* input3,
+                                                    void* const* outputs_bf16, int nflows,
+                                                    int batch, int channel, int h, int w, int filter_channels,
+                                                    vfi_strides_nhwc s1, vfi_strides4 s2, vfi_strides4 s3,
+                                                    vfi_strides_nhwc s_out, vfi_stream_t stream);
 
 /* vfi_filterinterp_backward_ori_image_multi on bfloat16 gradients: gradoutputs[t] (strides sg) and gradinput1 (strides s1)
  * are bfloat16 tensors, flows and filter float32.  gradinput1 is, bit for bit, bf16_rne of what the float32 entry writes

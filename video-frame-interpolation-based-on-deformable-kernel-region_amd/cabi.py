@@ -23,6 +23,16 @@ class Strides(ctypes.Structure):
     _fields_ = [("b", ctypes.c_int64), ("c", ctypes.c_int64), ("h", ctypes.c_int64)]
 
 
+class StridesNhwc(ctypes.Structure):
+    """vfi_strides_nhwc: batch, row and pixel strides of a tensor whose channel stride is 1"""
+    _fields_ = [("b", ctypes.c_int64), ("h", ctypes.c_int64), ("w", ctypes.c_int64)]
+
+
+class Strides4(ctypes.Structure):
+    """vfi_strides4: all four element strides"""
+    _fields_ = [("b", ctypes.c_int64), ("c", ctypes.c_int64), ("h", ctypes.c_int64), ("w", ctypes.c_int64)]
+
+
 VFI_OK, VFI_ERR_SHAPE, VFI_ERR_LAUNCH = 0, 1, -2
 DEFOR_OFFSET, DEFOR_REGION, DEFOR_NOFILTER = 0, 1, 2
 
@@ -35,6 +45,10 @@ SIGNATURES = {
     "vfi_filterinterp_forward_ori_multi_to": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_backward_ori_image_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_multi_to_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides, _p],
+    "vfi_filterinterp_forward_ori_nhwc_multi_to": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4, Strides4,
+                                                   StridesNhwc, _p],
+    "vfi_filterinterp_forward_ori_nhwc_multi_to_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4, Strides4,
+                                                        StridesNhwc, _p],
     "vfi_filterinterp_backward_ori_image_multi_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides,
                                                        _p],
     "vfi_filterinterp_forward_defor": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
@@ -116,6 +130,8 @@ INTERNAL_SIGNATURES = {
     "vfi_filterinterp_forward_ori_f16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides, _p],
     "vfi_filterinterp_forward_ori_multi_to_bf16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides,
                                                           _p],
+    # (the access width, in elements, the NHWC entries choose for these layouts)
+    "vfi_filterinterp_nhwc_access_width": [_i, _p, _p, _i, _i, _i, _i, _i, StridesNhwc, StridesNhwc],
     "vfi_filterinterp_forward_defor_general": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                                Strides, _p],
     # (which kernel: 0 the MFMA kernel, 1 the generic kernel)
@@ -151,6 +167,14 @@ def _st(t):
 
 def _st_tuple(t):
     return (t.stride(0), t.stride(1), t.stride(2), t.stride(3))
+
+
+def _st_nhwc(t):
+    return StridesNhwc(t.stride(0), t.stride(2), t.stride(3))
+
+
+def _st4(t):
+    return Strides4(*t.stride())
 
 
 def _ptr(t):
@@ -268,6 +292,46 @@ def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs, direct=Fal
     with torch.cuda.device(_dev(input1)):
         return _finish(lib().vfi_filterinterp_forward_ori_multi_to(_ptr(input1), fp, _ptr(input3), op, n, b, c, h, w, input3.size(1),
                                                                    _st(input1), _st(flows[0]), _st(input3), so, _stream(input1)))
+
+
+def _channels_innermost(t):
+    """channel stride 1 (the stride of a one-channel tensor addresses nothing)"""
+    return t.size(1) == 1 or t.stride(1) == 1
+
+
+def filterinterp_forward_nhwc_multi_to(image, flows, filt, outs):
+    """filterinterp_forward_ori_multi_to for a channels_last image: outs[t] = FilterInterpolation(image, flows[t], filt), bit
+    for bit what the NCHW call writes for the same logical tensors.  image and every output have channel stride 1: a dense
+    channels_last tensor or a channel slice of a wider one; the outputs share one layout of their own, all strides free.
+    image and outputs float32, or all bfloat16; flows (one layout) and filter float32, in NCHW or channels_last.  Forward only.
+    A shape or layout the library does not take returns 1; a dtype or device it does not take raises, both before any
+    library call.  The destinations must not overlap the inputs or each other (not checked)."""
+    n = len(flows)
+    if n == 0 or len(outs) != n or image.dim() != 4 or filt.dim() != 4:
+        return 1
+    b, c, h, w = image.shape
+    if not _channels_innermost(image) or not _fi_filter_ok(image, filt) or filt.size(1) < 1 or 0 in image.shape:
+        return 1
+    for fl, out in zip(flows, outs):
+        if fl.dim() != 4 or tuple(fl.shape) != (b, 2, h, w) or not _same_strides(fl, flows[0]):
+            return 1
+        if out.dim() != 4 or out.shape != image.shape or not _channels_innermost(out) or not _same_strides(out, outs[0]):
+            return 1
+    dtype, suffix = _fi_image_dtype((image, *outs), (filt, *flows))
+    fp = (ctypes.c_void_p * n)(*[fl.data_ptr() for fl in flows])
+    op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    with torch.cuda.device(image.device):
+        fn = getattr(lib(), "vfi_filterinterp_forward_ori_nhwc_multi_to" + suffix)
+        return _finish(fn(_ptr(image), fp, _ptr(filt), op, n, b, c, h, w, filt.size(1), _st_nhwc(image), _st4(flows[0]),
+                          _st4(filt), _st_nhwc(outs[0]), _stream(image, dtype)))
+
+
+def filterinterp_nhwc_access_width(image, filt, outs):
+    """the access width, in elements, filterinterp_forward_nhwc_multi_to runs these tensors with (host code, no launch)"""
+    op = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    b, _, h, w = image.shape
+    return lib().vfi_filterinterp_nhwc_access_width(image.element_size(), _ptr(image), op, len(outs), b, h, w, filt.size(1),
+                                                    _st_nhwc(image), _st_nhwc(outs[0]))
 
 
 def filterinterp_forward_ori_f16(input1, input2, input3, output, direct=False):

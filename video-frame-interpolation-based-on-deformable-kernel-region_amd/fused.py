@@ -383,11 +383,37 @@ def _f32_once(t):
     return t.float() if t.dtype == torch.bfloat16 else t
 
 
+def _channels_last_only(t):
+    """channel stride 1 and a pixel stride that is not: a channels_last tensor (or a channel slice of one) that the NCHW
+    entries refuse.  A [B, 1, H, W] tensor is both layouts at once and stays on the NCHW path."""
+    return t.dim() == 4 and t.stride(3) != 1 and t.stride(1) == 1
+
+
+def _refuse_channels_last_grad(*images):
+    for image in images:
+        if _channels_last_only(image) and _wants_grad(image):
+            raise RuntimeError("FilterInterpolate_ctx: the channels_last warp is forward-only (there is no channels_last "
+                               "image gradient yet); a .contiguous() context tensor trains")
+
+
+def _ctx_warp_nhwc_launch(ctx, offsets, filt):
+    # (the outputs get the input's strides, as in _ctx_warp_launch; flows and filter may be NCHW or channels_last)
+    outs = [torch.empty_strided(ctx.shape, ctx.stride(), dtype=ctx.dtype, device=ctx.device) for _ in offsets]
+    _check(cabi.filterinterp_forward_nhwc_multi_to(ctx, list(offsets), filt, outs), "filterinterp_forward_nhwc_multi_to")
+    return outs
+
+
 def _ctx_warp(image, offsets, filt):
     """one direction: the Function when the context tensor can train, today's plain launch otherwise.  With a bfloat16
-    context tensor a bfloat16 flow or filter is widened here, once per direction; float32 calls pass through untouched."""
+    context tensor a bfloat16 flow or filter is widened here, once per direction; float32 calls pass through untouched.
+    A channels_last context tensor (stride(3) != 1, stride(1) == 1) is warped in place by the NHWC entry, forward only: one
+    that requires grad in grad mode raises before any launch."""
+    nhwc = _channels_last_only(image)
+    _refuse_channels_last_grad(image)
     if image.dtype == torch.bfloat16:
         offsets, filt = [_f32_once(o) for o in offsets], _f32_once(filt)
+    if nhwc:
+        return _ctx_warp_nhwc_launch(image, offsets, filt)
     if _wants_grad(image):
         return list(_FilterInterpolateCtx.apply(image, filt, *offsets))
     return _ctx_warp_launch(image, offsets, filt)
@@ -407,7 +433,16 @@ def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
     outputs are bfloat16 -- bit for bit `.float()`, the float32 call, `.bfloat16()` -- and so is the context gradient,
     bf16_rne of the float32 backward on the widened incoming gradients.  Flow and filter stay float32 in the kernels: a
     bfloat16 flow or filter is widened once per direction with `.float()`, which is exact.  A float32 context tensor takes
-    the launches it always took."""
+    the launches it always took.
+    channels_last context tensors (float32 or bfloat16; `stride(3) != 1` and `stride(1) == 1`, a channel slice of a wider
+    channels_last tensor included) are warped where they are by vfi_filterinterp_forward_ori_nhwc_multi_to[_bf16]: the outputs
+    have the input's strides and hold, bit for bit, the NCHW call's `.contiguous(memory_format=torch.channels_last)`; flows
+    and filter may be in either layout.  "The input's strides" includes a slice's: the outputs of `wide[:, 45:241]` of a
+    437-channel tensor each span the wide tensor's footprint (437 / 196 of the dense size) -- pass a dense context, or call
+    `cabi.filterinterp_forward_nhwc_multi_to` with destinations of your own, where that matters.  The path is forward-only:
+    if either context is such a tensor and requires grad in grad mode, the call raises a RuntimeError before any launch of
+    either direction (`.contiguous()` trains).  Every tensor with `stride(3) == 1` goes where it always went."""
+    _refuse_channels_last_grad(ctx0, ctx2)                  # (both directions, before the first launch)
     out0 = _ctx_warp(ctx0, list(offsets[0]), filter[0])
     out2 = _ctx_warp(ctx2, list(offsets[1]), filter[1])
     return list(zip(out0, out2))
