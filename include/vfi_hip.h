@@ -289,8 +289,10 @@ int vfi_depthflowprojection_backward(const float* input1, const float* input2,
  * source with the largest weight `input2` that lands on it (top-left integer neighbour only) and
  * that weight in `count`.  The reference does this with an unguarded read-compare-write and is
  * scheduling dependent; this library returns what those statements give when the sources are
- * visited in raster order (largest weight above the incoming `count`, first source on ties).
- * count and output must be zero-filled by the caller (untouched targets keep their values).
+ * visited in raster order (largest weight above the incoming `count`, first source on ties;
+ * -0.0 and +0.0 are one weight, and `count` receives the winner's own bits).  The reference's
+ * wrapper zero-fills count and output.  A non-zero incoming `count` is a floor: only a weight
+ * above it is recorded, and a target no source beats keeps its incoming count and output.
  * The forward keeps a per-stream scratch buffer of about 8.3 bytes per pixel (keys + two bitmaps).  The backward gives
  * gradinput1 only: the reference never writes gradinput2 (its code for it is commented out). */
 int vfi_mindepthflowprojection_forward(const float* input1, const float* input2,

@@ -162,21 +162,22 @@ def depthflowproj_bwd(flow, depth, count, out, gout):
     return gflow, gdepth
 
 
-def mindepthflowproj_fwd(flow, weight, fillhole=1, count0=None):
-    """count0: optional incoming `count` (the reference wrapper passes zeros); out starts at zero."""
+def mindepthflowproj_fwd(flow, weight, fillhole=1, count0=None, out0=None):
+    """count0, out0: optional incoming `count` and `output` (the reference wrapper passes zeros for both)."""
     flow, weight = _f32(flow), _f32(weight)
     B, _, H, W = flow.shape
     count = np.zeros((B, 1, H, W), np.float32) if count0 is None else _f32(count0).copy()
-    out = np.zeros_like(flow)
+    out = np.zeros_like(flow) if out0 is None else _f32(out0).copy()
     _check(lib().vfi_oracle_mindepthflowproj_fwd(_p(flow), _p(weight), _p(count), _p(out), B, H, W, int(fillhole)),
            "mindepthflowproj_fwd")
     return out, count
 
 
-def mindepthflowproj_bwd(flow, weight, count, gout):
+def mindepthflowproj_bwd(flow, weight, count, gout, start=None):
+    """start: what gradinput1 holds before the call (the C function adds into it); zeros by default."""
     flow, weight, count, gout = _f32(flow), _f32(weight), _f32(count), _f32(gout)
     B, _, H, W = flow.shape
-    gflow = np.zeros_like(flow)
+    gflow = np.zeros_like(flow) if start is None else _f32(start).copy()
     _check(lib().vfi_oracle_mindepthflowproj_bwd(_p(flow), _p(weight), _p(count), _p(gout), _p(gflow), B, H, W),
            "mindepthflowproj_bwd")
     return gflow
@@ -208,11 +209,20 @@ def sepconv_fwd(img, v, h, fmad=0):
     return out
 
 
-def sepconv_bwd(img, v, h, gout):
+def _start(like, given):
+    if given is None:
+        return np.zeros_like(like)
+    assert given.shape == like.shape
+    return _f32(given).copy()
+
+
+def sepconv_bwd(img, v, h, gout, start=None):
+    """start: (gimg, gv, gh) as the three gradients hold them before the call -- vfi_oracle_sepconv_bwd adds every term
+    into the arrays it is handed, in the sequential loop's order; zeros by default."""
     img, v, h, gout = _f32(img), _f32(v), _f32(h), _f32(gout)
     B, C, H, W = img.shape
     fs = v.shape[1]
-    gimg, gv, gh = np.zeros_like(img), np.zeros_like(v), np.zeros_like(h)
+    gimg, gv, gh = (_start(a, g) for a, g in zip((img, v, h), start or (None, None, None)))
     _check(lib().vfi_oracle_sepconv_bwd(_p(img), _p(v), _p(h), _p(gout), _p(gimg), _p(gv), _p(gh), B, C, H, W, fs),
            "sepconv_bwd")
     return gimg, gv, gh
@@ -226,10 +236,12 @@ def sepconvflow_fwd(v, h, H, W, fmad=0):
     return out
 
 
-def sepconvflow_bwd(v, h, gflow, H, W, fmad=0):
+def sepconvflow_bwd(v, h, gflow, H, W, fmad=0, start=None):
+    """start: (gv, gh) before the call -- vfi_oracle_sepconvflow_bwd stores into gv and adds into gh, each only where
+    the tap sum is not zero, and leaves every other element as handed; zeros by default."""
     v, h, gflow = _f32(v), _f32(h), _f32(gflow)
     B, fs = v.shape[0], v.shape[1]
-    gv, gh = np.zeros_like(v), np.zeros_like(h)
+    gv, gh = (_start(a, g) for a, g in zip((v, h), start or (None, None)))
     _check(lib().vfi_oracle_sepconvflow_bwd(_p(v), _p(h), _p(gflow), _p(gv), _p(gh), B, H, W, fs, int(fmad)),
            "sepconvflow_bwd")
     return gv, gh

@@ -184,6 +184,11 @@ def cases(extra=False):
     c["corr_k3s2"] = _corr_case(rng, (3, 3, 4, 1, 2), 2, 5, 7, 8)
     c["corr_flownet"] = _corr_case(rng, (20, 1, 20, 2, 2), 1, 5, 6, 7)
     c["corr_pwc_3x2"] = _corr_case(rng, pwc, 2, 5, 3, 2)
+    # MinDepthFlowProjection's tie rule on signed zeros (tests/side_ops.py): two sources whose weights are -0.0 and +0.0, in
+    # both raster orders (item 1, item 0), over an incoming count of -1 -- the first source keeps the target
+    from tests import side_ops as so
+    flow, weight, count0, _ = so.md_zero_tie("item 1")
+    c["mindepth_zero_tie"] = Case("planted", dict(flow=flow, weight=weight, count0=count0), what="mindepth_floor")
     if extra:
         rng = np.random.default_rng(7)
         for fs in (2, 4, 5, 6):
@@ -225,6 +230,21 @@ def cases(extra=False):
         c["x_fi_ori_planted"] = Case("planted", dict(img=img, flow=flow, filt=filt), what="fi_ori")
         img, flow = fe.small_interp_inputs(rng)
         c["x_interp_planted"] = Case("planted", dict(img=img, flow=flow), what="interp")
+        # the side ops on planted inputs (tests/side_ops.py), small versions: Interpolation's border decisions, SeparableConv
+        # and SeparableConvFlow with non-finite, huge, subnormal and signed-zero values, MinDepthFlowProjection's ties of
+        # signed zeros over a negative floor.  Every planted flow fails the validity test or is exactly representable
+        # inside the frame, as above
+        img, flow, _ = so.interp_border()
+        c["x_interp_border"] = Case("planted", dict(img=img, flow=flow), what="interp_border")
+        d = so.sep_planted(5, so.SMALL_FRAME)
+        c["x_sepconv_planted"] = Case("planted", {k: d[k] for k in ("img", "v", "h", "gout")}, what="sepconv")
+        d = so.sepflow_planted(so.SMALL_FRAME, step=1)
+        c["x_sepconvflow_planted"] = Case("planted", {k: d[k] for k in ("img", "v", "h", "gflow")}, what="sepconvflow")
+        for name in so.MD_TIE_NAMES:
+            flow, weight, count0, _ = so.md_zero_tie(name)
+            if flow.shape[2:] == so.SMALL_FRAME[2:]:
+                c["x_mindepth_zero_tie_" + name.replace(",", "").replace(" ", "_")] = Case(
+                    "planted", dict(flow=flow, weight=weight, count0=count0), what="mindepth_floor")
     return c
 
 
@@ -333,7 +353,17 @@ def run_ref(R, case, given=None):
             (o["out0"], o["count"]), (o["out1"], _) = (R.depthflowproj_fwd(i["flow"], i["depth"], fh) for fh in (0, 1))
         elif what == "fi_ori":
             o["out"] = R.filterinterp_ori_fwd(i["img"], i["flow"], i["filt"])
-        else:
+        elif what == "sepconv":
+            o["out"] = R.sepconv_fwd(i["img"], i["v"], i["h"])
+            o["gimg"], o["gv"], o["gh"] = R.sepconv_bwd(i["img"], i["v"], i["h"], i["gout"])
+        elif what == "sepconvflow":
+            H, W = i["img"].shape[2:]
+            o["out"] = R.sepconvflow_fwd(i["v"], i["h"], H, W)
+            o["gv"], o["gh"] = R.sepconvflow_bwd(i["v"], i["h"], i["gflow"], H, W)
+        elif what == "mindepth_floor":
+            (o["out0"], o["count"]), (o["out1"], _) = (R.mindepthflowproj_fwd(i["flow"], i["weight"], fh, count0=i["count0"])
+                                                       for fh in (0, 1))
+        else:                                                          # "interp", "interp_border"
             o["out"] = R.interp_fwd(i["img"], i["flow"])
     else:
         raise KeyError(op)
@@ -395,6 +425,16 @@ def run_oracle(O, case, ref):
             (o["out0"], o["count"]), (o["out1"], _) = (O.depthflowproj_fwd(i["flow"], i["depth"], fh) for fh in (0, 1))
         elif what == "fi_ori":
             o["out"] = O.filterinterp_ori_fwd(i["img"], i["flow"], i["filt"], fmad=0)
+        elif what == "sepconv":
+            o["out"] = O.sepconv_fwd(i["img"], i["v"], i["h"], fmad=0)
+            o["gimg"], o["gv"], o["gh"] = O.sepconv_bwd(i["img"], i["v"], i["h"], i["gout"])
+        elif what == "sepconvflow":
+            H, W = i["img"].shape[2:]
+            o["out"] = O.sepconvflow_fwd(i["v"], i["h"], H, W, fmad=0)
+            o["gv"], o["gh"] = O.sepconvflow_bwd(i["v"], i["h"], i["gflow"], H, W, fmad=0)
+        elif what == "mindepth_floor":
+            (o["out0"], o["count"]), (o["out1"], _) = (O.mindepthflowproj_fwd(i["flow"], i["weight"], fh, count0=i["count0"])
+                                                       for fh in (0, 1))
         else:
             o["out"] = O.interp_fwd(i["img"], i["flow"], fmad=0)
     else:
@@ -504,7 +544,9 @@ def check(name, case, ref_raster, got, ref_blocks=None):
             assert corr_edges.same_bits_nan_aware(got[key], want), (name, key, "oracle != reference",
                                                                     corr_edges.describe_difference(got[key], want))
             assert np.isfinite(want).mean() >= 0.5, (name, key)
-        if what == "flowproj":
+        if what in ("interp_border", "sepconv", "sepconvflow", "mindepth_floor"):
+            check_side_op(name, case, ref_raster)
+        elif what == "flowproj":
             assert all(np.isfinite(v).all() for v in ref_raster.values()), (name, "no planted flow is a valid source")
         elif what == "depthproj":
             cnt = ref_raster["count"]
@@ -552,6 +594,35 @@ def check(name, case, ref_raster, got, ref_blocks=None):
         else:
             assert within(blk, want, tol, absolute=tol == PROJ_TOL), (name, key, np.abs(blk - want).max())
             assert within(got[key], blk, tol, absolute=tol == PROJ_TOL), (name, key)
+
+
+def check_side_op(name, case, ref):
+    """The planted side-op cases (tests/side_ops.py): the plants did decide, in the reference's own results."""
+    from tests import side_ops as so
+    what, i = case.params["what"], case.inputs
+    if what == "interp_border":
+        img, flow, expect = so.interp_border()
+        assert so.same_bits_nan_aware(ref["out"], so.interp_border_expected(img, expect)), name
+    elif what == "sepconv":
+        for key in ("out", "gimg", "gv", "gh"):
+            _, nan, pinf, ninf = so.nonfinite_census(ref[key])
+            assert nan and (pinf or ninf), (name, key)
+    elif what == "sepconvflow":
+        for x, want in so.sepflow_expected(step=1):
+            for got in (ref["out"][:, 1, so.SEPFLOW_ROW_V, x], ref["out"][:, 0, so.SEPFLOW_ROW_H, x]):
+                assert np.isnan(got).all() if np.isnan(want) else (got == f32(want)).all(), (name, x, want, got)
+    else:
+        bits = lambda a: np.ascontiguousarray(a).view(np.uint32)      # noqa: E731
+        for b in range(i["flow"].shape[0]):              # per item: every valid source lands on one target; the first wins
+            srcs = np.argwhere(i["flow"][b, 0] != so.INVALID)
+            if not len(srcs):
+                continue
+            sy, sx = (int(v) for v in srcs[0])
+            ty, tx = int(sy + i["flow"][b, 1, sy, sx]), int(sx + i["flow"][b, 0, sy, sx])
+            assert len(srcs) >= 2 and {int(v) for v in bits(i["weight"])[b, 0][tuple(srcs.T)]} == {0, 0x80000000}, name
+            for key in ("out0", "out1"):
+                assert np.array_equal(ref[key][b, :, ty, tx], -i["flow"][b, :, sy, sx]), (name, key, "the first source's flow")
+            assert bits(ref["count"])[b, 0, ty, tx] == bits(i["weight"])[b, 0, sy, sx], (name, "the first source's weight bits")
 
 
 def flatten(name, case, ref, seen):

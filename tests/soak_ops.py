@@ -2,7 +2,7 @@
 """Soak of the other hot-path entry points against the CPU oracle on random shapes (larger and more varied than the
 hypothesis-drawn unit tests): correlation fp32 and half (every k = 1 kernel: flat, tiled, 16-byte rows), PWC-Net's warp
 alone and feeding the correlation in one launch, the x4-upsample fused into the projection, MinDepthFlowProjection,
-Interpolation, and the backward passes of FilterInterpolation, the projections, the correlation and Interpolation
+Interpolation, SeparableConv with any channel count (`require_c3=False`), and the backward passes of FilterInterpolation, the projections, the correlation and Interpolation
 (per-pixel gradients bit-exact, scattered image gradients within GRAD_TOL).
     python tests/soak_ops.py [cases] [seed]        (not collected by pytest; the oracle is the checker)
 """
@@ -130,6 +130,23 @@ for it in range(cases):
         assert cabi.separableconv_backward(g1, gv, gh, gpu(sgo), s1_, s2_, s3_) == 0
         q1, q2, q3 = oracle.sepconv_bwd(f1, v, hh, sgo)
         check("SeparableConv backward", np.array_equal(cpu(s1_), q1) and np.array_equal(cpu(s2_), q2) and np.array_equal(cpu(s3_), q3), info + " fs=%d" % fs)
+    # ---- SeparableConv with any channel count (the library's own entry: require_c3=False), a random C in 1 .. 7
+    Cs = int(rng.integers(1, 8))
+    if H >= fs and W >= fs and H * W <= 20000:
+        oh, ow = H - fs + 1, W - fs + 1
+        im = rng.standard_normal((B, Cs, H, W)).astype(f32)
+        v = rng.random((B, fs, oh, ow), dtype=f32)
+        hh = rng.random((B, fs, oh, ow), dtype=f32)
+        gim, gv, gh = gpu(im), gpu(v), gpu(hh)
+        so = torch.full((B, Cs, oh, ow), float("nan"), device=dev)
+        assert cabi.separableconv_forward(gim, gv, gh, so, require_c3=False) == 0
+        check("SeparableConv any C", np.array_equal(cpu(so), oracle.sepconv_fwd(im, v, hh, fmad=1)), info + " fs=%d Cs=%d" % (fs, Cs))
+        sgo = rng.standard_normal((B, Cs, oh, ow)).astype(f32)
+        s1_, s2_, s3_ = torch.zeros_like(gim), torch.zeros_like(gv), torch.zeros_like(gh)
+        assert cabi.separableconv_backward(gim, gv, gh, gpu(sgo), s1_, s2_, s3_, require_c3=False) == 0
+        q1, q2, q3 = oracle.sepconv_bwd(im, v, hh, sgo)
+        check("SeparableConv backward any C", np.array_equal(cpu(s1_), q1) and np.array_equal(cpu(s2_), q2) and np.array_equal(cpu(s3_), q3),
+              info + " fs=%d Cs=%d" % (fs, Cs))
     if C <= 3 and H * W <= 6000:
         filt = rng.random((B, 16, H, W), dtype=f32)
         off = (rng.standard_normal((B, 32, H, W)) * 0.7).astype(f32)

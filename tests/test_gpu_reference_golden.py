@@ -2,7 +2,8 @@
 executed on the CPU (raster order), on the edge inputs of tests/reference_cases.py.  Reads tests/golden/ only.
 
 Rules, those of test_against_golden_fixtures: forwards within 1e-5 * max(1, |ref|), gradients and projected flow
-within 1e-4 (the former relative to max(1, |ref|), the latter absolute), counts exact; the deformable variants and the
+within 1e-4 (the former relative to max(1, |ref|), the latter absolute), counts exact (the signed-zero tie of
+MinDepthFlowProjection: every output bit for bit); the deformable variants and the
 kernel_size-3 correlation only where the recorded mask is clear (there the reference read outside its buffers:
 undefined; the library clamps).
 
@@ -101,6 +102,14 @@ def run_gpu(torch, cabi, case, ref):
         assert cabi.separableconvflow_forward(t["img"], t["v"], t["h"], out) == 0
         assert cabi.separableconvflow_backward(t["img"], t["v"], t["h"], t["gflow"], g2, g3) == 0
         o = dict(out=out, gv=g2, gh=g3)
+    elif op == "planted":                                  # MinDepthFlowProjection over an incoming count (the signed-zero ties)
+        assert p["what"] == "mindepth_floor"
+        for fh in (0, 1):
+            count, out = gpu(torch, i["count0"]), z(i["flow"])
+            assert cabi.mindepthflowprojection_forward(t["flow"], t["weight"], count, out, fh) == 0
+            o["out%d" % fh] = out
+            if fh == 0:
+                o["count"] = count
     elif op == "corr":
         cfg = p["cfg"]
         o["out"] = cabi.correlation_forward(t["f1"], t["f2"], *cfg)
@@ -120,7 +129,9 @@ def test_kernels_match_recorded_reference(name, recorded, torch_mod, cabi):
     for key, val in got.items():
         assert val.shape == ref[key].shape, (name, key)
         mask = rc.mask_for(case, ref, key)
-        if key == "count" and case.op in ("flowproj", "mindepth"):
+        if case.op == "planted":                         # bit for bit, the sign of a zero count included
+            assert val.view(np.uint32).tobytes() == ref[key].view(np.uint32).tobytes(), (name, key)
+        elif key == "count" and case.op in ("flowproj", "mindepth"):
             assert np.array_equal(val, ref[key]), (name, key)
         elif key in ("out0", "out1"):
             assert near(val, ref[key], GRAD, mask, absolute=True), (name, key, np.abs(val - ref[key]).max())

@@ -586,10 +586,11 @@ def interpolation_backward(input1, input2, gradoutput, gradinput1, gradinput2, r
 
 # ---------------------------------------------------------------- separableconv_cuda / separableconvflow_cuda
 
-def _sep_checks(input1, input2, input3):
+def _sep_checks(input1, input2, input3, require_c3=True):
+    """require_c3: the reference's wrappers refuse any other channel count (separableconv_cuda.cc); the library takes any."""
     b, c, h, w = input1.shape
     fs = input2.size(1)
-    if c != 3 or input2.size(0) != b or input2.size(1) != input3.size(1):
+    if (require_c3 and c != 3) or input2.size(0) != b or input2.size(1) != input3.size(1):
         return None
     if input2.size(2) != h - fs + 1 or input2.size(3) != w - fs + 1:
         return None
@@ -600,8 +601,8 @@ def _sep_checks(input1, input2, input3):
     return b, c, h, w, fs
 
 
-def separableconv_forward(input1, input2, input3, output):
-    dims = _sep_checks(input1, input2, input3)
+def separableconv_forward(input1, input2, input3, output, require_c3=True):
+    dims = _sep_checks(input1, input2, input3, require_c3)
     if dims is None or output.stride(3) != 1:
         return 1
     b, c, h, w, fs = dims
@@ -611,8 +612,8 @@ def separableconv_forward(input1, input2, input3, output):
                                                        _stream(input1)))
 
 
-def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3):
-    dims = _sep_checks(input1, input2, input3)
+def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3, require_c3=True):
+    dims = _sep_checks(input1, input2, input3, require_c3)
     if dims is None or gradoutput.stride(3) != 1:
         return 1
     if not _addressed_as(input1, gradinput1) or not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):
@@ -627,8 +628,8 @@ def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradi
             _stream(input1)))
 
 
-def separableconvflow_forward(input1, input2, input3, flow_output):
-    dims = _sep_checks(input1, input2, input3)
+def separableconvflow_forward(input1, input2, input3, flow_output, require_c3=True):
+    dims = _sep_checks(input1, input2, input3, require_c3)
     if dims is None or flow_output.stride(3) != 1:
         return 1
     b, c, h, w, fs = dims
@@ -638,8 +639,8 @@ def separableconvflow_forward(input1, input2, input3, flow_output):
                                                            _stream(input2)))
 
 
-def separableconvflow_backward(input1, input2, input3, gradflow_output, gradinput2, gradinput3):
-    dims = _sep_checks(input1, input2, input3)
+def separableconvflow_backward(input1, input2, input3, gradflow_output, gradinput2, gradinput3, require_c3=True):
+    dims = _sep_checks(input1, input2, input3, require_c3)
     if dims is None or gradflow_output.stride(3) != 1:
         return 1
     if not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):

@@ -9,8 +9,9 @@
 // (the reference's CPU-thinkable order): the target keeps the source with the LARGEST weight
 // that exceeds the incoming `count`, the FIRST such source in raster order on ties.  It is
 // computed without a race: one 64-bit atomicMax per source on a key
-//     (order-preserving bits of the weight) << 32 | (0xffffffff - source index)
-// in a per-stream scratch plane, then one pass that decodes the winner per target and leaves bitmaps of
+//     (order-preserving bits of the weight, -0.0 keyed as +0.0) << 32 | (0xffffffff - source index)
+// in a per-stream scratch plane (the two zeros are one weight to `>`: between them the raster index decides, and the
+// winner's own weight bits are read back from input2), then one pass that decodes the winner per target and leaves bitmaps of
 // "count != 0" for the hole filler (a walk to the nearest non-hole is then a few word loads).  Hole
 // filling (:121-206) and backward (:209-331) follow the reference statement by statement; the
 // backward compares the weight with `count` at all four neighbours although the forward writes
@@ -24,13 +25,10 @@
 
 namespace vfi {
 
-// monotone map float -> uint32 (total order of the values, -0 < +0)
+// monotone map float -> uint32 in the order of `<` on the values: -0.0 and +0.0 compare equal and share a key
 __device__ __forceinline__ uint32_t md_order_bits(float v) {
-    const uint32_t u = __float_as_uint(v);
+    const uint32_t u = (v == 0.0f) ? 0u : __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float md_order_value(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 __global__ __launch_bounds__(VFI_TX * VFI_TY) void mindepth_bid(
@@ -61,8 +59,9 @@ struct MdMaps { int rmw, cmw, rowmap, colmap; };
 // eight rows of 64), so that a column's 32 row bits are one word assembled in LDS and stored without atomics.
 #define MD_ROWS 32
 __global__ __launch_bounds__(256) void mindepth_award(
-    const float* __restrict__ in1, const unsigned long long* __restrict__ keys, float* __restrict__ count,
-    float* __restrict__ out, int* __restrict__ bits, MdMaps m, int h, int w, vfi_strides s1, vfi_strides sc) {
+    const float* __restrict__ in1, const float* __restrict__ in2, const unsigned long long* __restrict__ keys,
+    float* __restrict__ count, float* __restrict__ out, int* __restrict__ bits, MdMaps m, int h, int w, vfi_strides s1,
+    vfi_strides s2, vfi_strides sc) {
     __shared__ unsigned colm[64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = blockIdx.x * 64 + lane;
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void mindepth_award(
                 float* o = out + (int64_t)b * s1.b + (int64_t)y * s1.h + x;
                 o[0] = -flow[0];                            // (:80-82)
                 o[s1.c] = -flow[s1.c];
-                c = md_order_value((uint32_t)(key >> 32));
+                c = in2[(int64_t)b * s2.b + (int64_t)sy * s2.h + sx];      // the winner's own bits (:83): the key folds -0.0
                 *cn = c;
             }
             nz = c != 0.0f;
@@ -200,7 +199,7 @@ extern "C" int vfi_mindepthflowprojection_forward(const float* input1, const flo
     const dim3 grid = pixel_grid(w, h, batch), block(VFI_TX, VFI_TY, 1);
     hipLaunchKernelGGL(mindepth_bid, grid, block, 0, st, input1, input2, count, keys, h, w, s1, s2, sc);
     hipLaunchKernelGGL(mindepth_award, dim3((unsigned)((w + 63) / 64), (unsigned)m.cmw, (unsigned)batch), dim3(256), 0, st,
-                       input1, keys, count, output, bits, m, h, w, s1, sc);
+                       input1, input2, keys, count, output, bits, m, h, w, s1, s2, sc);
     if (fillhole) hipLaunchKernelGGL(mindepth_fillhole, grid, block, 0, st, count, output, bits, m, h, w, s1, sc);
     return launch_status();
 }
