@@ -22,7 +22,7 @@ import numpy as np
 
 from tests.fi_windows import _eval, source, source_expr
 
-SRC, DEV = "correlation.hip", "correlation_dev.h"
+SRC, DEV, BWD, SRC_BF16 = "correlation.hip", "correlation_dev.h", "correlation_bwd.h", "correlation_bf16.hip"
 INT_MAX = 2 ** 31 - 1
 PWC = (4, 1, 4, 1, 1)                       # pad, kernel_size, max_displacement, stride1, stride2
 
@@ -37,13 +37,23 @@ def constants():
     return c
 
 
-def function_body(name):
-    """The text of function `name` of correlation.hip from its signature to the next function at column 0."""
-    text = source(SRC)
+def function_body(name, src=SRC):
+    """The text of function `name` of `src` (correlation.hip) from its signature to the next function at column 0."""
+    text = source(src)
     m = re.search(r"^[^\n]*\b%s\([^;{]*\{" % name, text, flags=re.M | re.S)
     if not m:
         raise AssertionError("no function %s" % name)
     end = re.search(r"^\}", text[m.end():], flags=re.M)
+    return text[m.start():m.end() + end.start()]
+
+
+def struct_body(name, src=SRC):
+    """The text of `struct name {` of `src` up to its closing brace at column 0."""
+    text = source(src)
+    m = re.search(r"^struct %s \{" % name, text, flags=re.M)
+    if not m:
+        raise AssertionError("no struct %s" % name)
+    end = re.search(r"^\};", text[m.end():], flags=re.M)
     return text[m.start():m.end() + end.start()]
 
 

@@ -227,14 +227,35 @@ def test_new_entries_share_the_dispatch_and_a_stride_counts_as_a_pointer():
         assert "CorrPlain{});" in " ".join(ce.function_body(entry).split())
     # every launch of the chain passes the epilogue it was given
     assert body.count("hipLaunchKernelGGL(") == 6 and body.count(", epi);") == 5 and body.count(", one);") == 1
-    # backward: the masked kernels are launched where the plain ones are
-    one = " ".join(ce.function_body("corr_backward_one").split())
-    assert one.count("corr_lrelu_backward_k1<true> : corr_lrelu_backward_k1<false>") == 1
-    assert one.count("corr_lrelu_backward<true> : corr_lrelu_backward<false>") == 1
-    pair = " ".join(ce.function_body("correlation_backward_pair_any").split())
-    assert "if (acts) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair," in pair and "else hipLaunchKernelGGL(corr_backward_k1_pair," in pair
-    for entry in ("vfi_correlation_backward_pair", "vfi_correlation_lrelu_backward_pair"):
-        assert "return correlation_backward_pair_any(" in " ".join(ce.function_body(entry).split())
+    # backward, float32 and bfloat16: the masked kernels are launched where the plain ones are -- each file names its
+    # kernels once, masked beside plain, and the one launcher of every storage type launches each kind in one place
+    f32 = " ".join(ce.struct_body("CorrBwdF32").split())
+    assert f32.count("if (act) hipLaunchKernelGGL(second ? corr_lrelu_backward_k1<true> : corr_lrelu_backward_k1<false>,") == 1
+    assert f32.count("else hipLaunchKernelGGL(second ? corr_backward_k1<true> : corr_backward_k1<false>,") == 1
+    assert f32.count("if (act) hipLaunchKernelGGL(second ? corr_lrelu_backward<true> : corr_lrelu_backward<false>,") == 1
+    assert f32.count("else hipLaunchKernelGGL(second ? corr_backward<true> : corr_backward<false>,") == 1
+    assert "if (masks) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair," in f32 and "else hipLaunchKernelGGL(corr_backward_k1_pair," in f32
+    assert f32.count("hipLaunchKernelGGL(") == 6
+    bf16 = " ".join(ce.struct_body("CorrBwdBf16", ce.SRC_BF16).split())
+    assert bf16.count("if (act) hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, Mask> : corr_backward_k1_bf16<false, Mask>),") == 1
+    assert bf16.count("else hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, CorrBf16Grad> : corr_backward_k1_bf16<false, CorrBf16Grad>),") == 1
+    assert bf16.count("if (act) hipLaunchKernelGGL((second ? corr_backward_bf16<true, Mask> : corr_backward_bf16<false, Mask>),") == 1
+    assert bf16.count("else hipLaunchKernelGGL((second ? corr_backward_bf16<true, CorrBf16Grad> : corr_backward_bf16<false, CorrBf16Grad>),") == 1
+    assert "if (masks) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair_bf16," in bf16 and "else hipLaunchKernelGGL(corr_backward_k1_pair_bf16," in bf16
+    assert bf16.count("hipLaunchKernelGGL(") == 6
+    one = " ".join(ce.function_body("corr_backward_one", ce.BWD).split())
+    assert one.count("K::k1(second, act,") == 1 and one.count("K::generic(second, act,") == 1 and "hipLaunchKernelGGL" not in one
+    pair = " ".join(ce.function_body("corr_backward_pair", ce.BWD).split())
+    assert pair.count("K::pair(roles, acts ? &masks : nullptr,") == 1 and pair.count("corr_backward_one<K>(") == 1
+    assert "acts ? &act : nullptr);" in pair and "hipLaunchKernelGGL" not in pair
+    # the entries only forward
+    for src, k, suffix in ((ce.SRC, "CorrBwdF32", ""), (ce.SRC_BF16, "CorrBwdBf16", "_bf16")):
+        for entry in ("vfi_correlation_backward_pair", "vfi_correlation_lrelu_backward_pair"):
+            b = " ".join(ce.function_body(entry + suffix, src).split())
+            assert "return corr_backward_pair<%s>(" % k in b and "hipLaunchKernelGGL" not in b
+        for entry in ("vfi_correlation_backward", "vfi_correlation_lrelu_backward"):
+            b = " ".join(ce.function_body(entry + suffix, src).split())
+            assert "return corr_backward_both<%s>(" % k in b and "hipLaunchKernelGGL" not in b
 
 
 def test_mirror_on_dense_and_strided_outputs():

@@ -17,12 +17,14 @@
 // levels (hundreds to a few thousand pixels, up to 196 channels) would leave most of the chip
 // idle that way; they use 16x4-pixel tiles with one WAVE PER DISPLACEMENT ROW (9 waves per
 // workgroup, 9 running sums per lane), which spreads the same work over 9x more waves.
-#include "correlation_dev.h"
+//
+// Backward: the bodies, the arithmetic and the launchers are correlation_bwd.h's, one definition for float32, half and
+// bfloat16 (correlation_bf16.hip).  This file holds the float32 and half __global__ kernels around them, the packed-half
+// tiled kernel, and the structs that name those kernels for the launchers.
+#include "correlation_bwd.h"
 
 #include <algorithm>
-#include <cfloat>
 #include <initializer_list>
-#include <type_traits>
 
 #include <hip/hip_fp16.h>
 
@@ -689,203 +691,39 @@ __global__ __launch_bounds__(256) void corr_forward_generic_f16(
     out[gid] = __float2half_rn(acc / (float)(k * k * channel));
 }
 
-// The arithmetic of a backward kernel: the element type, zero, the count the mean divides by, the term s <- s (+) g (*) v,
-// the sum of two partials and the mean.  CorrF32 is the reference's float instantiation, its `acc += a * b` fused as nvcc
-// fuses it.
-struct CorrF32 {
-    typedef float T;
-    static __device__ __forceinline__ T zero() { return 0.0f; }
-    static __device__ __forceinline__ float count(int n) { return (float)n; }
-    static __device__ __forceinline__ T term(T s, T g, T v) { return fmaf(g, v, s); }
-    static __device__ __forceinline__ T add(T r, T s) { return r + s; }
-    static __device__ __forceinline__ T mean(T r, float nelems) { return r / nelems; }
-};
-
-// The reference's at::Half instantiation of the backward (correlation_cuda_kernel.cu:151-334, dispatched at :495-541).
-// The terms, windows and skips are corr_backward's; the arithmetic is at::Half's, which goes through float and rounds back to
-// half after every operation: p = half(g * v), the 32 partials `__shared__ scalar_t prod_sum[32]` accumulate IN HALF,
-// r = half(r + s_l) for l = 0..31, gin = half(r / nelems_h) with nelems_h = half(k*k*C) (not the exact count above 2048).
-// float32 has 24 >= 2*11 + 2 significand bits, so float-then-round is the correctly rounded half operation: the products and
-// sums here are plain v_mul_f16 / v_add_f16 (never fused: -ffp-contract=off, no fma written), and the one division is done in
-// float on the two widened halves and rounded once.  A term whose other-map tap lies in the zero padding is NOT skipped: it
-// adds half(g * 0), which is NaN when g is inf or NaN.
-__device__ __forceinline__ __half corr_mean_f16(__half r, float nelems_h) {
-    float rf = __half2float(r);
-    asm volatile("" : "+v"(rf));        // (keeps the widening a v_cvt: nothing mixed-precision may be folded into the division)
-    return __float2half_rn(rf / nelems_h);
-}
-
-struct CorrF16 {
-    typedef __half T;
-    static __device__ __forceinline__ T zero() { return __float2half_rn(0.0f); }
-    static __device__ __forceinline__ float count(int n) { return __half2float(__float2half_rn((float)n)); }   // nelems_h
-    static __device__ __forceinline__ T term(T s, T g, T v) { return __hadd(s, __hmul(g, v)); }
-    static __device__ __forceinline__ T add(T r, T s) { return __hadd(r, s); }
-    static __device__ __forceinline__ T mean(T r, float nelems_h) { return corr_mean_f16(r, nelems_h); }
-};
-
-// backward, stride1 == 1, any pad / k / md / stride2 (correlation_cuda_kernel.cu:151-334).  One thread per gradient
-// element; the reference's reduction order (32 partial sums over tc = l, l+32, ..., then a sequential sum of the
-// partials) is kept.  A term whose other-map tap lies in the zero padding is not skipped: it adds g * 0 in A's arithmetic.
-// MASK (float only): every gradOutput value goes through LeakyReLU's derivative as it is loaded (CorrGrad).
-template <class A, bool SECOND, bool MASK = false>
-__device__ __forceinline__ void corr_backward_body(
-    const typename A::T* __restrict__ other, const typename A::T* __restrict__ gout, typename A::T* __restrict__ gin,
-    int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr,
-    const CorrGrad<MASK>& act = CorrGrad<false>{}) {
-    typedef typename A::T T;
-    const int64_t total = (int64_t)batch * channel * h * w;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= total) return;
-    const int bx = (int)(gid % w);
-    const int by = (int)((gid / w) % h);
-    const int c = (int)((gid / ((int64_t)w * h)) % channel);
-    const int n = (int)(gid / ((int64_t)w * h * channel));
-    const int dsz = 2 * dr + 1;
-    const int y = by + pad, x = bx + pad;                   // padded coordinates
-    const T* of = other + ((int64_t)n * channel + c) * h * w;
-    const T* go = MASK ? gout + (int64_t)n * act.gstride : gout + (int64_t)n * oc * oh * ow;
-    const float* yo = MASK ? act.y + (int64_t)n * act.ystride : nullptr;
-    const float nelems = A::count((2 * kr + 1) * (2 * kr + 1) * channel);
-    bool any = SECOND;
-    if constexpr (!SECOND) {
-        const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
-        any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
-    }
-    if (!any) {
-        gin[gid] = A::zero();   // the binding zero-fills gradInput (correlation_cuda.cc:112-113)
-        return;
-    }
-    T r = A::zero();
-    for (int l = 0; l < 32; ++l) {
-        T s = A::zero();
-        for (int tc = l; tc < oc; tc += 32) {
-            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
-            int xmin, ymin, xmax, ymax, vy, vx;
-            if constexpr (SECOND) {
-                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
-                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
-                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
-                vy = y - j2 - pad; vx = x - i2 - pad;
-            } else {
-                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
-                vy = y + j2 - pad; vx = x + i2 - pad;
-            }
-            const T val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? of[(int64_t)vy * w + vx] : A::zero();
-            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
-            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
-            const T* g = go + (int64_t)tc * oh * ow;
-            for (int j = ymin; j <= ymax; ++j)
-                for (int i = xmin; i <= xmax; ++i) {
-                    if constexpr (MASK) s = A::term(s, act(g[(int64_t)j * ow + i], yo[(int64_t)tc * oh * ow + (int64_t)j * ow + i]), val);
-                    else s = A::term(s, g[(int64_t)j * ow + i], val);
-                }
-        }
-        r = A::add(r, s);
-    }
-    gin[gid] = A::mean(r, nelems);
-}
-
+// The backward kernels.  The arithmetic (CorrF32, CorrF16), the mask (CorrNoMask, CorrGradLrelu) and both bodies are
+// correlation_bwd.h's, shared with the bfloat16 kernels of correlation_bf16.hip; the kernels here bind them to float and half.
+// One thread per gradient element, any configuration:
 #define CORR_BACKWARD_ARGS(T) const T* __restrict__ other, const T* __restrict__ gout, T* __restrict__ gin, \
     int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward(CORR_BACKWARD_ARGS(float)) {
-    corr_backward_body<CorrF32, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr);
+    corr_backward_body<CorrF32, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, CorrNoMask<CorrF32>{});
 }
 // the same through LeakyReLU's derivative (vfi_correlation_lrelu_backward*, any configuration)
 template <bool SECOND>
-__global__ __launch_bounds__(256) void corr_lrelu_backward(CORR_BACKWARD_ARGS(float), CorrGrad<true> act) {
-    corr_backward_body<CorrF32, SECOND, true>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, act);
+__global__ __launch_bounds__(256) void corr_lrelu_backward(CORR_BACKWARD_ARGS(float), CorrGradLrelu act) {
+    corr_backward_body<CorrF32, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, act);
 }
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward_f16(CORR_BACKWARD_ARGS(__half)) {
-    corr_backward_body<CorrF16, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr);
+    corr_backward_body<CorrF16, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, CorrNoMask<CorrF16>{});
 }
 #undef CORR_BACKWARD_ARGS
 
 // Backward for PWC-Net's configuration (k == 1, strides 1, pad == md == 4; round 3).  corr_backward above is one thread per
 // gradient element: 81 loads of gradOutput + 81 of the other map + 81 multiply-adds each, and a gradOutput element is
-// fetched again by every channel (1.1 ms for both gradients at 32 x 288 x 496).  Here a thread owns one PIXEL: its 81
-// gradOutput values (gradInput1: the 81 planes at the pixel; gradInput2: plane tc at the pixel moved back by displacement
-// tc) live in registers for all channels, and per channel the workgroup (64x4 pixels) stages the other map's window
-// (tile + 4 halo, zero padded) in LDS, double-buffered.  The sum runs in the reference's order -- 32 partial sums over
-// tc = l, l + 32, l + 64, added in sequence (correlation_cuda_kernel.cu:162-239, 255-332) -- so the result is corr_backward's
-// and the oracle's bit for bit.  The body is one function: corr_backward_k1 below is one gradient per launch, and
-// corr_backward_k1_pair runs one instance or the other per workgroup.  (CorrBwdWindow: correlation_dev.h)
-
-// MASK: the 81 values go through LeakyReLU's derivative as they are loaded (CorrGrad: 81 more loads per pixel and channel
-// group, outside the channel loop); the channel loop is the same code either way.
-template <bool SECOND, bool MASK = false>
-__device__ __forceinline__ void corr_backward_k1_body(
-    CorrBwdWindow& win, const CorrBwdTile& t, const float* __restrict__ other, const float* __restrict__ gout,
-    float* __restrict__ gin, int channel, int h, int w, const CorrGrad<MASK>& act = CorrGrad<false>{}) {
-    typedef CorrBwdTile T;
-    constexpr int MD = T::MD, D = T::D, OC = T::OC;
-    const int tid = threadIdx.x, px = tid & 63, py = tid >> 6;
-    const int bx = t.x0 + px, by = t.y0 + py;
-    const int n = t.n, c_begin = t.c_begin, c_end = t.c_end;
-    const bool in = bx < w && by < h;
-    const int64_t plane = (int64_t)h * w;
-    const float* go = MASK ? gout + (int64_t)n * act.gstride : gout + (int64_t)n * OC * plane;
-    const float* yo = MASK ? act.y + (int64_t)n * act.ystride : nullptr;
-
-    // the pixel's 81 gradOutput values (zero where the reference skips the term: gradInput2 near the frame's border)
-    float g[OC];
-#pragma unroll
-    for (int tc = 0; tc < OC; ++tc) {
-        const int gy = SECOND ? by - (tc / D - MD) : by, gx = SECOND ? bx - (tc % D - MD) : bx;
-        if constexpr (MASK) {
-            // (a skipped term loads element 0 of its image -- a valid address -- and drops it: loads under a branch go out one
-            //  at a time, each waited for; these go out a displacement row of gradOutput and y together)
-            const bool ok = in && gy >= 0 && gy < h && gx >= 0 && gx < w;
-            const int64_t at = ok ? (int64_t)tc * plane + (int64_t)gy * w + gx : 0;
-            const float gv = go[at], yv = yo[at];
-            g[tc] = act(ok ? gv : 0.0f, ok ? yv : 0.0f);
-            if (tc % D == D - 1) __builtin_amdgcn_sched_barrier(0);
-        } else {
-            g[tc] = (in && gy >= 0 && gy < h && gx >= 0 && gx < w) ? go[(int64_t)tc * plane + (int64_t)gy * w + gx] : 0.0f;
-        }
-    }
-    // (a term the reference skips -- gradInput2, displaced position outside the frame -- reads the other map at that same
-    //  position: the zero padding of the staged window, so the skipped term is fma(0, 0, s) = s)
-
-    auto stage = [&](int c, int buf) {
-        const float* of = other + ((int64_t)n * channel + c) * plane;
-        for (int e = tid; e < T::LH * T::LW; e += 256) {
-            const T::Elem p = t.window(e);
-            win[buf][p.r][p.col] = (p.gy >= 0 && p.gy < h && p.gx >= 0 && p.gx < w) ? of[(int64_t)p.gy * w + p.gx] : 0.0f;
-        }
-    };
-    if (c_begin >= c_end) return;
-    stage(c_begin, 0);
-    const float nelems = (float)channel;
-    for (int c = c_begin; c < c_end; ++c) {
-        const int buf = (c - c_begin) & 1;
-        __syncthreads();                                    // window c has been written; window c - 1 has been read
-        if (c + 1 < c_end) stage(c + 1, buf ^ 1);
-        float r = 0.0f;
-#pragma unroll
-        for (int l = 0; l < 32; ++l) {
-            float s = 0.0f;
-#pragma unroll
-            for (int tc = l; tc < OC; tc += 32) {
-                const int tj = tc / D, ti = tc % D;
-                const float v = SECOND ? win[buf][py + 2 * MD - tj][px + 2 * MD - ti] : win[buf][py + tj][px + ti];
-                s = fmaf(g[tc], v, s);
-            }
-            r += s;
-        }
-        if (in) gin[((int64_t)n * channel + c) * plane + (int64_t)by * w + bx] = r / nelems;
-    }
-}
-
+// fetched again by every channel (1.1 ms for both gradients at 32 x 288 x 496).  corr_backward_k1_body (correlation_bwd.h)
+// gives a thread one PIXEL and its 81 gradOutput values in registers for all channels, with the same sums in the same
+// order, so the result is corr_backward's and the oracle's bit for bit.  corr_backward_k1 below is one gradient per launch,
+// and corr_backward_k1_pair runs one instance or the other per workgroup.
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_backward_k1(
     const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
     int channel, int h, int w, int groups, int ch_per_group) {
     __shared__ CorrBwdWindow win;
     const CorrBwdTile t(channel, groups, ch_per_group);
-    corr_backward_k1_body<SECOND>(win, t, other, gout, gin, channel, h, w);
+    corr_backward_k1_body<CorrF32, SECOND>(win, t, other, gout, gin, channel, h, w, CorrNoMask<CorrF32>{});
 }
 
 // Up to four gradients of two calls of equal shape in ONE launch (vfi_correlation_backward_pair: both gradients of the same
@@ -899,19 +737,20 @@ __global__ __launch_bounds__(256) void corr_backward_k1_pair(CorrBwdRoles roles,
     const float* __restrict__ other = roles.r[t.role].other;
     const float* __restrict__ gout = roles.r[t.role].gout;
     float* __restrict__ gin = roles.r[t.role].gin;
-    if (roles.r[t.role].second) corr_backward_k1_body<true>(win, t, other, gout, gin, channel, h, w);
-    else corr_backward_k1_body<false>(win, t, other, gout, gin, channel, h, w);
+    if (roles.r[t.role].second) corr_backward_k1_body<CorrF32, true>(win, t, other, gout, gin, channel, h, w, CorrNoMask<CorrF32>{});
+    else corr_backward_k1_body<CorrF32, false>(win, t, other, gout, gin, channel, h, w, CorrNoMask<CorrF32>{});
 }
 
 // The two kernels above with the mask (vfi_correlation_lrelu_backward, ..._pair): kernels of their own, so the plain ones
 // are what they were.  A role's y and strides are scalar loads at the role's index, like its pointers.
+// (The mask is 81 more loads per pixel and channel group, outside the channel loop; the channel loop is the same code.)
 template <bool SECOND>
 __global__ __launch_bounds__(256) void corr_lrelu_backward_k1(
     const float* __restrict__ other, const float* __restrict__ gout, float* __restrict__ gin,
-    int channel, int h, int w, int groups, int ch_per_group, CorrGrad<true> act) {
+    int channel, int h, int w, int groups, int ch_per_group, CorrGradLrelu act) {
     __shared__ CorrBwdWindow win;
     const CorrBwdTile t(channel, groups, ch_per_group);
-    corr_backward_k1_body<SECOND, true>(win, t, other, gout, gin, channel, h, w, act);
+    corr_backward_k1_body<CorrF32, SECOND>(win, t, other, gout, gin, channel, h, w, act);
 }
 
 __global__ __launch_bounds__(256) void corr_lrelu_backward_k1_pair(CorrBwdRoles roles, CorrBwdMasks masks, int channel, int h, int w,
@@ -921,9 +760,9 @@ __global__ __launch_bounds__(256) void corr_lrelu_backward_k1_pair(CorrBwdRoles 
     const float* __restrict__ other = roles.r[t.role].other;
     const float* __restrict__ gout = roles.r[t.role].gout;
     float* __restrict__ gin = roles.r[t.role].gin;
-    const CorrGrad<true> act = {masks.y[t.role], masks.ystride[t.role], masks.gstride[t.role], masks.slope};
-    if (roles.r[t.role].second) corr_backward_k1_body<true, true>(win, t, other, gout, gin, channel, h, w, act);
-    else corr_backward_k1_body<false, true>(win, t, other, gout, gin, channel, h, w, act);
+    const CorrGradLrelu act = {masks.y[t.role], masks.ystride[t.role], masks.gstride[t.role], masks.slope};
+    if (roles.r[t.role].second) corr_backward_k1_body<CorrF32, true>(win, t, other, gout, gin, channel, h, w, act);
+    else corr_backward_k1_body<CorrF32, false>(win, t, other, gout, gin, channel, h, w, act);
 }
 
 // PWC-Net's configuration (k == 1, strides 1, pad == md == 4), modelled on corr_backward_k1: a workgroup owns 64x4 pixels and
@@ -1061,9 +900,6 @@ int vfi::corr_backward_groups(int tiles, int batch, int channel, int* ch_per_gro
     groups = (channel + *ch_per_group - 1) / *ch_per_group;
     return (int64_t)batch * groups <= 65535 ? groups : 0;
 }
-
-// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
-static bool corr_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
 
 // What an epilogue adds to the bits the alignment tests look at: an image stride that breaks a kernel's store alignment
 // counts exactly as a misaligned base pointer does.  Whether the strides are valid for an output of oc x oh x ow planes.
@@ -1226,81 +1062,52 @@ extern "C" int vfi_correlation_forward_f16(const void* input1, const void* input
     return launch_status();
 }
 
-// a mask the entries accept: y present, a valid slope, images at least their own planes apart
-static bool corr_grad_ok(const CorrGrad<true>& a, int64_t image) {
-    return a.y && corr_slope_ok(a.slope) && a.ystride >= image && a.gstride >= image;
-}
-
-// One gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1.  float, or the
-// reference's at::Half instantiation.  `act` (float only): gradOutput goes through LeakyReLU's derivative as it is loaded --
-// the same launches of the masked kernels.  The callers have run corr_check.
-template <class T>
-static int corr_backward_one(bool second, const T* other, const T* gout, T* gin, int batch, int channel, int h, int w, int oc, int oh,
-                             int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st,
-                             const CorrGrad<true>* act = nullptr) {
-    constexpr bool HALF = std::is_same<T, __half>::value;
-    if (HALF && act) return VFI_ERR_SHAPE;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
-        // PWC-Net's configuration: the pixel-owns-its-gradOutput kernels; channel groups over blockIdx.z fill the chip.
-        // (The half kernel reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.)
-        int ch_per_group;
-        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
-        if (groups && (!HALF || (int64_t)81 * h * w * 2 < INT_MAX)) {
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            if constexpr (HALF)
-                hipLaunchKernelGGL(second ? corr_backward_k1_f16<true> : corr_backward_k1_f16<false>, grid, dim3(128), 0, st, other, gout,
-                                   gin, channel, h, w, groups, ch_per_group);
-            else if (act)
-                hipLaunchKernelGGL(second ? corr_lrelu_backward_k1<true> : corr_lrelu_backward_k1<false>, grid, dim3(256), 0, st, other,
-                                   gout, gin, channel, h, w, groups, ch_per_group, *act);
-            else
-                hipLaunchKernelGGL(second ? corr_backward_k1<true> : corr_backward_k1<false>, grid, dim3(256), 0, st, other, gout, gin,
-                                   channel, h, w, groups, ch_per_group);
-            return launch_status();
-        }
+// The backward entries.  The checks and the launchers are correlation_bwd.h's, the same for every storage type; here the
+// file names its kernels.  float32: every kernel.
+struct CorrBwdF32 {
+    typedef float T;
+    typedef CorrGradLrelu Mask;
+    static constexpr bool MASKED = true, PAIRED = true;
+    static bool k1_fits(int, int) { return true; }
+    template <class... Args>
+    static void generic(bool second, const Mask* act, dim3 grid, hipStream_t st, Args... args) {
+        if (act) hipLaunchKernelGGL(second ? corr_lrelu_backward<true> : corr_lrelu_backward<false>, grid, dim3(256), 0, st, args..., *act);
+        else hipLaunchKernelGGL(second ? corr_backward<true> : corr_backward<false>, grid, dim3(256), 0, st, args...);
     }
-    const int64_t total = (int64_t)batch * channel * h * w;
-    const int kr = (kernel_size - 1) / 2, dr = max_displacement / stride2;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if constexpr (HALF)
-        hipLaunchKernelGGL(second ? corr_backward_f16<true> : corr_backward_f16<false>, grid, block, 0, st, other, gout, gin, batch,
-                           channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    else if (act)
-        hipLaunchKernelGGL(second ? corr_lrelu_backward<true> : corr_lrelu_backward<false>, grid, block, 0, st, other, gout, gin, batch,
-                           channel, h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr, *act);
-    else
-        hipLaunchKernelGGL(second ? corr_backward<true> : corr_backward<false>, grid, block, 0, st, other, gout, gin, batch, channel,
-                           h, w, oc, oh, ow, pad_size, kr, max_displacement, stride2, dr);
-    return launch_status();
-}
-
-// both gradients: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
-template <class T>
-static int correlation_backward_any(const T* input1, const T* input2, const T* gradoutput, T* gradinput1, T* gradinput2, int batch,
-                                    int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
-                                    int stride2, vfi_stream_t stream, const CorrGrad<true>* act = nullptr) {
-    constexpr bool HALF = std::is_same<T, __half>::value;
-    int oc, oh, ow;
-    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                   stride1, stride2, true, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (act && !corr_grad_ok(*act, (int64_t)oc * oh * ow)) return VFI_ERR_SHAPE;
-    const int64_t total = (int64_t)batch * channel * h * w;
-    if (HALF && (total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (corr_backward_one(false, input2, gradoutput, gradinput1, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
-                          max_displacement, stride2, st, act) != VFI_OK)
-        return VFI_ERR_LAUNCH;
-    return corr_backward_one(true, input1, gradoutput, gradinput2, batch, channel, h, w, oc, oh, ow, pad_size, kernel_size,
-                             max_displacement, stride2, st, act);
-}
+    template <class... Args>
+    static void k1(bool second, const Mask* act, dim3 grid, hipStream_t st, Args... args) {
+        if (act) hipLaunchKernelGGL(second ? corr_lrelu_backward_k1<true> : corr_lrelu_backward_k1<false>, grid, dim3(256), 0, st, args..., *act);
+        else hipLaunchKernelGGL(second ? corr_backward_k1<true> : corr_backward_k1<false>, grid, dim3(256), 0, st, args...);
+    }
+    template <class... Args>
+    static void pair(const CorrBwdRoles& roles, const CorrBwdMasks* masks, dim3 grid, hipStream_t st, Args... args) {
+        if (masks) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair, grid, dim3(256), 0, st, roles, *masks, args...);
+        else hipLaunchKernelGGL(corr_backward_k1_pair, grid, dim3(256), 0, st, roles, args...);
+    }
+};
+// half (the reference's at::Half instantiation): no masked and no pair kernels.  The tiled kernel has 128 threads and
+// reaches an image's gradOutput through one buffer descriptor: 81 planes of halves below 2 GB.
+struct CorrBwdF16 {
+    typedef __half T;
+    typedef void Mask;
+    static constexpr bool MASKED = false, PAIRED = false;
+    static bool k1_fits(int h, int w) { return (int64_t)81 * h * w * 2 < INT_MAX; }
+    template <class... Args>
+    static void generic(bool second, const Mask*, dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL(second ? corr_backward_f16<true> : corr_backward_f16<false>, grid, dim3(256), 0, st, args...);
+    }
+    template <class... Args>
+    static void k1(bool second, const Mask*, dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL(second ? corr_backward_k1_f16<true> : corr_backward_k1_f16<false>, grid, dim3(128), 0, st, args...);
+    }
+};
 
 extern "C" int vfi_correlation_backward(const float* input1, const float* input2, const float* gradoutput,
                                          float* gradinput1, float* gradinput2, int batch, int channel, int h, int w,
                                          int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                          vfi_stream_t stream) {
-    return correlation_backward_any(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
-                                    max_displacement, stride1, stride2, stream);
+    return corr_backward_both<CorrBwdF32>(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                          max_displacement, stride1, stride2, stream);
 }
 
 // vfi_correlation_backward of gradOutput masked by LeakyReLU's derivative: the same two launches of the masked kernels.
@@ -1309,50 +1116,9 @@ extern "C" int vfi_correlation_lrelu_backward(const float* input1, const float* 
                                                float* gradinput2, int batch, int channel, int h, int w, int pad_size,
                                                int kernel_size, int max_displacement, int stride1, int stride2,
                                                float negative_slope, vfi_stream_t stream) {
-    const CorrGrad<true> act = {y, y_batch_stride, gradoutput_batch_stride, negative_slope};
-    return correlation_backward_any(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
-                                    max_displacement, stride1, stride2, stream, &act);
-}
-
-// The backward of two calls of equal shape -- the same pyramid level of the two flow networks of a frame pair, whose forward
-// is vfi_correlation_forward_pair -- with any subset of the four gradients.  PWC-Net's configuration: the requested
-// gradients are the roles of ONE corr_backward_k1_pair launch, and the channel groups are sized on the whole launch
-// (tiles x batch x roles).  Any other configuration, or role x batch x groups beyond a grid's z: one launch per requested
-// gradient with the kernels vfi_correlation_backward uses.  Either way a gradient's bits are that entry's.
-// `acts` (or NULL): the two items' masks -- vfi_correlation_lrelu_backward_pair, the same compaction and launches with the
-// masked kernels; a role carries its item's mask.
-static int correlation_backward_pair_any(
-    const float* const (&in1)[2], const float* const (&in2)[2], const float* const (&go)[2], float* const (&gi)[2][2],
-    const CorrGrad<true>* acts, int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement,
-    int stride1, int stride2, vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (corr_check({}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, true, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (acts && !corr_slope_ok(acts[0].slope)) return VFI_ERR_SHAPE;
-    CorrBwdRoles roles = {};
-    CorrBwdMasks masks = {};
-    const int nroles = corr_backward_roles(in1, in2, go, gi, acts, (int64_t)oc * oh * ow, roles, masks);     // (both items carry the one slope)
-    if (nroles < 0) return VFI_ERR_SHAPE;
-    if (nroles == 0) return VFI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {
-        int ch_per_group;
-        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch * nroles, channel, &ch_per_group);
-        if (groups) {
-            roles.per_role = batch * groups;
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, nroles * roles.per_role);
-            if (acts) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair, grid, dim3(256), 0, st, roles, masks, channel, h, w, groups, ch_per_group);
-            else hipLaunchKernelGGL(corr_backward_k1_pair, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
-            return launch_status();
-        }
-    }
-    for (int k = 0; k < nroles; ++k) {
-        const CorrGrad<true> act = {masks.y[k], masks.ystride[k], masks.gstride[k], masks.slope};
-        if (corr_backward_one(roles.r[k].second != 0, roles.r[k].other, roles.r[k].gout, roles.r[k].gin, batch, channel, h, w, oc, oh,
-                              ow, pad_size, kernel_size, max_displacement, stride2, st, acts ? &act : nullptr) != VFI_OK)
-            return VFI_ERR_LAUNCH;
-    }
-    return VFI_OK;
+    const CorrGradLrelu act = {y, y_batch_stride, gradoutput_batch_stride, negative_slope};
+    return corr_backward_both<CorrBwdF32>(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                          max_displacement, stride1, stride2, stream, &act);
 }
 
 extern "C" int vfi_correlation_backward_pair(
@@ -1360,12 +1126,9 @@ extern "C" int vfi_correlation_backward_pair(
     const float* input1_b, const float* input2_b, const float* gradoutput_b, float* gradinput1_b, float* gradinput2_b,
     int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
     vfi_stream_t stream) {
-    const float* const in1[2] = {input1_a, input1_b};
-    const float* const in2[2] = {input2_a, input2_b};
-    const float* const go[2] = {gradoutput_a, gradoutput_b};
-    float* const gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
-    return correlation_backward_pair_any(in1, in2, go, gi, nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                                         stride1, stride2, stream);
+    return corr_backward_pair<CorrBwdF32>(corr_backward_items<float>(input1_a, input2_a, gradoutput_a, gradinput1_a, gradinput2_a, input1_b,
+                                                                     input2_b, gradoutput_b, gradinput1_b, gradinput2_b),
+                                          nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream);
 }
 
 extern "C" int vfi_correlation_lrelu_backward_pair(
@@ -1375,21 +1138,18 @@ extern "C" int vfi_correlation_lrelu_backward_pair(
     int64_t gradoutput_b_batch_stride, float* gradinput1_b, float* gradinput2_b,
     int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
     float negative_slope, vfi_stream_t stream) {
-    const float* const in1[2] = {input1_a, input1_b};
-    const float* const in2[2] = {input2_a, input2_b};
-    const float* const go[2] = {gradoutput_a, gradoutput_b};
-    float* const gi[2][2] = {{gradinput1_a, gradinput2_a}, {gradinput1_b, gradinput2_b}};
-    const CorrGrad<true> acts[2] = {{y_a, y_a_batch_stride, gradoutput_a_batch_stride, negative_slope},
-                                    {y_b, y_b_batch_stride, gradoutput_b_batch_stride, negative_slope}};
-    return correlation_backward_pair_any(in1, in2, go, gi, acts, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                                         stride1, stride2, stream);
+    const CorrGradLrelu acts[2] = {{y_a, y_a_batch_stride, gradoutput_a_batch_stride, negative_slope},
+                                   {y_b, y_b_batch_stride, gradoutput_b_batch_stride, negative_slope}};
+    return corr_backward_pair<CorrBwdF32>(corr_backward_items<float>(input1_a, input2_a, gradoutput_a, gradinput1_a, gradinput2_a, input1_b,
+                                                                     input2_b, gradoutput_b, gradinput1_b, gradinput2_b),
+                                          acts, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream);
 }
 
 extern "C" int vfi_correlation_backward_f16(const void* input1, const void* input2, const void* gradoutput,
                                              void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
                                              int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                              vfi_stream_t stream) {
-    return correlation_backward_any((const __half*)input1, (const __half*)input2, (const __half*)gradoutput, (__half*)gradinput1,
-                                    (__half*)gradinput2, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
-                                    stride2, stream);
+    return corr_backward_both<CorrBwdF16>(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                          max_displacement, stride1, stride2, stream);
 }
+

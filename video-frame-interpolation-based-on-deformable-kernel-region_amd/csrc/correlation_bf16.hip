@@ -8,7 +8,8 @@
 //     C[x1][x2] = sum_c f1[c][y][x1] * f2[c][y + tj - 4][x2],
 // a 16-pixel block of x1 needs 24 columns x2, and two 16x16x32 MFMAs per 32 channels form them (9 of 32 products wanted).
 // Forward, anything else, and small PWC-Net levels: one thread per output, the float32 generic kernel's arithmetic.
-// Backward: the float32 kernels' arithmetic (correlation.hip: corr_backward, corr_backward_k1) on widened values.
+// Backward: the float32 kernels' arithmetic on widened values -- the bodies and the launchers of correlation_bwd.h, which
+// correlation.hip's float32 and half kernels share, bound to bfloat16 by the kernels of this file.
 //
 // The same with PWC-Net's LeakyReLU (vfi_correlation_lrelu_forward_bf16 / _backward_bf16): the kernels below take an epilogue
 // (forward: what is stored, and where an image begins) and a gradient mask (backward: what a gradOutput value becomes as it is
@@ -17,11 +18,7 @@
 // Two calls of equal shape in one launch (vfi_correlation_[lrelu_]forward_pair_bf16, ..._backward_pair_bf16: the same pyramid
 // level of a frame pair's two flow networks): pair kernels that take a workgroup's item or role from blockIdx and run the same
 // bodies, so every output is its single entry's bit for bit.
-#include "bf16.h"
-#include "correlation_dev.h"
-
-#include <cfloat>
-#include <climits>
+#include "correlation_bwd.h"
 
 namespace vfi {
 
@@ -56,29 +53,6 @@ struct CorrBf16PlainPair { typedef CorrBf16Plain One; };
 struct CorrBf16LreluPair { typedef CorrBf16Lrelu One; int64_t stride[2]; float slope; };
 __host__ __device__ __forceinline__ CorrBf16Plain corr_bf16_epilogue(const CorrBf16PlainPair&, int) { return {}; }
 __host__ __device__ __forceinline__ CorrBf16Lrelu corr_bf16_epilogue(const CorrBf16LreluPair& e, int item) { return {e.stride[item], e.slope}; }
-
-// What a backward kernel does with a gradOutput value g whose output position holds the saved ACTIVATED output yv, and where
-// the images of gradOutput and y begin.  CorrBf16Grad: nothing, dense.  CorrBf16GradLrelu: g' = yv > 0 ? g :
-// bf16_rne(float(g) * slope) -- torch's bfloat16 leaky_relu backward, a materialised bfloat16 g' -- with images gstride /
-// ystride elements apart (gradOutput: the narrow() view torch.cat's backward hands down).
-struct CorrBf16Grad {
-    static constexpr bool MASK = false;
-    __device__ __forceinline__ const bf16_t* y_image(int) const { return nullptr; }
-    __device__ __forceinline__ int64_t g_image(int n, int64_t dense) const { return (int64_t)n * dense; }
-    __device__ __forceinline__ float operator()(bf16_t g, bf16_t) const { return bf16_widen(g); }
-};
-struct CorrBf16GradLrelu {
-    static constexpr bool MASK = true;
-    const bf16_t* y;
-    int64_t ystride, gstride;
-    float slope;
-    __device__ __forceinline__ const bf16_t* y_image(int n) const { return y + (int64_t)n * ystride; }
-    __device__ __forceinline__ int64_t g_image(int n, int64_t) const { return (int64_t)n * gstride; }
-    __device__ __forceinline__ float operator()(bf16_t g, bf16_t yv) const {
-        const float gf = bf16_widen(g);
-        return bf16_widen(yv) > 0.0f ? gf : bf16_widen(bf16_rne(gf * slope));
-    }
-};
 
 // ---------------------------------------------------------------------------------------------------------------- forward, MFMA
 //
@@ -348,88 +322,30 @@ __global__ __launch_bounds__(256) void corr_forward_generic_bf16_pair(
 
 // ---------------------------------------------------------------------------------------------------------------- backward
 //
-// corr_backward (correlation.hip) on bfloat16 storage: one thread per gradient element, float32 terms s = fmaf(g, v, s) in 32
-// partials over tc = l, l + 32, ..., the partials added in sequence, r / (float)(k*k*C), rounded to bfloat16 once.  A term
-// whose other-map tap lies in the zero padding is not skipped (g * 0: NaN for an infinite g).
+// The float32 backward on bfloat16 storage.  The arithmetic (CorrBf16: float32 terms on exactly widened values, the mean
+// rounded to bfloat16 once), the masks (CorrNoMask, CorrBf16GradLrelu) and both bodies are correlation_bwd.h's, shared with
+// the float32 and half kernels of correlation.hip; the kernels here bind them to bfloat16.
+// One thread per gradient element, any configuration:
 template <bool SECOND, class Act>
 __global__ __launch_bounds__(256) void corr_backward_bf16(
     const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
     int batch, int channel, int h, int w, int oc, int oh, int ow, int pad, int kr, int md, int s2, int dr, Act act) {
-    const int64_t total = (int64_t)batch * channel * h * w;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= total) return;
-    const int bx = (int)(gid % w);
-    const int by = (int)((gid / w) % h);
-    const int c = (int)((gid / ((int64_t)w * h)) % channel);
-    const int n = (int)(gid / ((int64_t)w * h * channel));
-    const int dsz = 2 * dr + 1;
-    const int y = by + pad, x = bx + pad;                   // padded coordinates
-    const bf16_t* of = other + ((int64_t)n * channel + c) * h * w;
-    const bf16_t* go = gout + act.g_image(n, (int64_t)oc * oh * ow);
-    const bf16_t* yo = act.y_image(n);
-    const float nelems = (float)((2 * kr + 1) * (2 * kr + 1) * channel);
-    bool any = SECOND;
-    if constexpr (!SECOND) {
-        const int xmin = x - kr - md, ymin = y - kr - md, xmax = x + kr - md, ymax = y + kr - md;
-        any = !(xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax);
-    }
-    if (!any) {
-        gin[gid] = 0;                                       // +0: the binding zero-fills gradInput
-        return;
-    }
-    float r = 0.0f;
-    for (int l = 0; l < 32; ++l) {
-        float s = 0.0f;
-        for (int tc = l; tc < oc; tc += 32) {
-            const int i2 = (tc % dsz - dr) * s2, j2 = (tc / dsz - dr) * s2;
-            int xmin, ymin, xmax, ymax, vy, vx;
-            if constexpr (SECOND) {
-                xmin = x - kr - md - i2; ymin = y - kr - md - j2;
-                xmax = x + kr - md - i2; ymax = y + kr - md - j2;
-                if (xmax < 0 || ymax < 0 || xmin >= ow || ymin >= oh || xmin > xmax || ymin > ymax) continue;
-                vy = y - j2 - pad; vx = x - i2 - pad;
-            } else {
-                xmin = x - kr - md; ymin = y - kr - md; xmax = x + kr - md; ymax = y + kr - md;
-                vy = y + j2 - pad; vx = x + i2 - pad;
-            }
-            const float val = (vy >= 0 && vy < h && vx >= 0 && vx < w) ? bf16_widen(of[(int64_t)vy * w + vx]) : 0.0f;
-            xmin = max(0, xmin); xmax = min(ow - 1, xmax);
-            ymin = max(0, ymin); ymax = min(oh - 1, ymax);
-            const bf16_t* g = go + (int64_t)tc * oh * ow;
-            for (int j = ymin; j <= ymax; ++j)
-                for (int i = xmin; i <= xmax; ++i) {
-                    const int64_t at = (int64_t)j * ow + i;
-                    const bf16_t yv = Act::MASK ? yo[(int64_t)tc * oh * ow + at] : (bf16_t)0;
-                    s = fmaf(act(g[at], yv), val, s);
-                }
-        }
-        r += s;
-    }
-    gin[gid] = bf16_rne(r / nelems);
+    corr_backward_body<CorrBf16, SECOND>(other, gout, gin, batch, channel, h, w, oc, oh, ow, pad, kr, md, s2, dr, act);
 }
 
-// corr_backward_k1 (correlation.hip) on bfloat16 storage, PWC-Net's configuration (k == 1, strides 1, pad == md == 4): a thread
-// owns one pixel of a 64x4 tile, its 81 gradOutput values widened into registers for all channels of the group; per channel
-// the workgroup stages the other map's 12x72 window, widened, in LDS (double-buffered, zero padded).  The same float32
-// terms in the same order as corr_backward_bf16, so the same bits.  (A term the reference skips -- gradInput2, displaced
-// position outside the frame -- has g = 0 and meets the window's zero padding: fma(0, 0, s) = s.)  The body has one
-// definition, correlation_bf16_bwd_k1.inc, as corr_backward_k1_body is one: corr_backward_k1_bf16 is one gradient per launch,
-// and the pair kernels run one instance of the device function or the other per workgroup.  The single-gradient kernels
-// include the statements themselves: called through the function they compiled to slower code (see the .inc).
-template <bool SECOND, class Act>
-__device__ __forceinline__ void corr_backward_k1_bf16_body(
-    CorrBwdWindow& win, const CorrBwdTile& t, const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout,
-    bf16_t* __restrict__ gin, int channel, int h, int w, const Act& act) {
-#include "correlation_bf16_bwd_k1.inc"
-}
+// PWC-Net's configuration (k == 1, strides 1, pad == md == 4): the tiled body, the same float32 terms in the same order as
+// corr_backward_bf16, so the same bits.  corr_backward_k1_bf16 is one gradient per launch and includes the body's statements
+// themselves: called through corr_backward_k1_body it compiled to slower code (see correlation_bwd_k1.inc).
+typedef CorrNoMask<CorrBf16> CorrBf16Grad;
 
 template <bool SECOND, class Act>
 __global__ __launch_bounds__(256) void corr_backward_k1_bf16(
     const bf16_t* __restrict__ other, const bf16_t* __restrict__ gout, bf16_t* __restrict__ gin,
     int channel, int h, int w, int groups, int ch_per_group, Act act) {
+    typedef CorrBf16 A;
     __shared__ CorrBwdWindow win;
     const CorrBwdTile t(channel, groups, ch_per_group);
-#include "correlation_bf16_bwd_k1.inc"
+#include "correlation_bwd_k1.inc"
 }
 
 // Up to four gradients of two calls of equal shape in ONE launch (vfi_correlation_backward_pair_bf16), as corr_backward_k1_pair
@@ -446,8 +362,8 @@ __global__ __launch_bounds__(256) void corr_backward_k1_pair_bf16(CorrBf16BwdRol
     const bf16_t* __restrict__ other = roles.r[t.role].other;
     const bf16_t* __restrict__ gout = roles.r[t.role].gout;
     bf16_t* __restrict__ gin = roles.r[t.role].gin;
-    if (roles.r[t.role].second) corr_backward_k1_bf16_body<true>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
-    else corr_backward_k1_bf16_body<false>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
+    if (roles.r[t.role].second) corr_backward_k1_body<CorrBf16, true>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
+    else corr_backward_k1_body<CorrBf16, false>(win, t, other, gout, gin, channel, h, w, CorrBf16Grad{});
 }
 
 // the masked twin (vfi_correlation_lrelu_backward_pair_bf16): a role's y and strides are scalar loads at the role's index too
@@ -459,8 +375,8 @@ __global__ __launch_bounds__(256) void corr_lrelu_backward_k1_pair_bf16(CorrBf16
     const bf16_t* __restrict__ gout = roles.r[t.role].gout;
     bf16_t* __restrict__ gin = roles.r[t.role].gin;
     const CorrBf16GradLrelu act = {masks.y[t.role], masks.ystride[t.role], masks.gstride[t.role], masks.slope};
-    if (roles.r[t.role].second) corr_backward_k1_bf16_body<true>(win, t, other, gout, gin, channel, h, w, act);
-    else corr_backward_k1_bf16_body<false>(win, t, other, gout, gin, channel, h, w, act);
+    if (roles.r[t.role].second) corr_backward_k1_body<CorrBf16, true>(win, t, other, gout, gin, channel, h, w, act);
+    else corr_backward_k1_body<CorrBf16, false>(win, t, other, gout, gin, channel, h, w, act);
 }
 
 }  // namespace vfi
@@ -523,12 +439,9 @@ static int corr_bf16_launch_generic(const CorrBf16Items& t, int nitems, const Ep
     return launch_status();
 }
 
-// LeakyReLU's slope as the fused entries take it: finite and positive (the backward reads the pre-activation's sign off y)
-static bool corr_bf16_slope_ok(float slope) { return slope > 0.0f && slope <= FLT_MAX; }
-
 static bool corr_bf16_epilogue_ok(const CorrBf16PlainPair&, int, int64_t) { return true; }
 static bool corr_bf16_epilogue_ok(const CorrBf16LreluPair& e, int nitems, int64_t image) {
-    return corr_bf16_slope_ok(e.slope) && e.stride[0] >= image && e.stride[nitems - 1] >= image;
+    return corr_slope_ok(e.slope) && e.stride[0] >= image && e.stride[nitems - 1] >= image;
 }
 
 // The forward of all four entries: the checks, the kernel choice, one launch.  `batch` is one item's, and the choice is made
@@ -622,53 +535,35 @@ extern "C" int vfi_correlation_forward_bf16_kernel(int which, const void* input1
                                     stride1, stride2, (hipStream_t)stream);
 }
 
-// one gradient, one launch: gradInput1 (second == false) from other = input2, gradInput2 from other = input1
-template <class Act>
-static int corr_bf16_backward_one(bool second, const bf16_t* other, const bf16_t* gout, bf16_t* gin, int batch, int channel, int h, int w,
-                                  int oc, int oh, int ow, int pad_size, int kernel_size, int max_displacement, int stride2, hipStream_t st,
-                                  const Act& act) {
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4) {
-        int ch_per_group;
-        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch, channel, &ch_per_group);
-        if (groups) {
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, batch * groups);
-            hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, Act> : corr_backward_k1_bf16<false, Act>), grid, dim3(256), 0, st, other,
-                               gout, gin, channel, h, w, groups, ch_per_group, act);
-            return launch_status();
-        }
+// The backward entries: correlation_bwd.h's checks and launchers (the float32 entries' own) with this file's kernels.
+struct CorrBwdBf16 {
+    typedef bf16_t T;
+    typedef CorrBf16GradLrelu Mask;
+    static constexpr bool MASKED = true, PAIRED = true;
+    static bool k1_fits(int, int) { return true; }
+    template <class... Args>
+    static void generic(bool second, const Mask* act, dim3 grid, hipStream_t st, Args... args) {
+        if (act) hipLaunchKernelGGL((second ? corr_backward_bf16<true, Mask> : corr_backward_bf16<false, Mask>), grid, dim3(256), 0, st, args..., *act);
+        else hipLaunchKernelGGL((second ? corr_backward_bf16<true, CorrBf16Grad> : corr_backward_bf16<false, CorrBf16Grad>), grid, dim3(256), 0, st, args..., CorrBf16Grad{});
     }
-    const int64_t total = (int64_t)batch * channel * h * w;
-    if ((total + 255) / 256 > INT_MAX) return VFI_ERR_SHAPE;
-    hipLaunchKernelGGL((second ? corr_backward_bf16<true, Act> : corr_backward_bf16<false, Act>), dim3((unsigned)((total + 255) / 256)),
-                       dim3(256), 0, st, other, gout, gin, batch, channel, h, w, oc, oh, ow, pad_size, (kernel_size - 1) / 2,
-                       max_displacement, stride2, max_displacement / stride2, act);
-    return launch_status();
-}
-
-// both gradients of both entries: gradInput1 from (input2, gradOutput), then gradInput2 from (input1, gradOutput)
-template <class Act>
-static int corr_bf16_backward(const void* input1, const void* input2, const void* gradoutput, void* gradinput1, void* gradinput2,
-                              int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1,
-                              int stride2, vfi_stream_t stream, const Act& act, int64_t ystride, int64_t gstride) {
-    int oc, oh, ow;
-    if (corr_check({input1, input2, gradoutput, gradinput1, gradinput2}, batch, channel, h, w, pad_size, kernel_size, max_displacement,
-                   stride1, stride2, true, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (ystride < (int64_t)oc * oh * ow || gstride < (int64_t)oc * oh * ow) return VFI_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int err = corr_bf16_backward_one(false, (const bf16_t*)input2, (const bf16_t*)gradoutput, (bf16_t*)gradinput1, batch, channel, h, w,
-                                           oc, oh, ow, pad_size, kernel_size, max_displacement, stride2, st, act);
-    if (err != VFI_OK) return err;
-    return corr_bf16_backward_one(true, (const bf16_t*)input1, (const bf16_t*)gradoutput, (bf16_t*)gradinput2, batch, channel, h, w, oc,
-                                  oh, ow, pad_size, kernel_size, max_displacement, stride2, st, act);
-}
+    template <class... Args>
+    static void k1(bool second, const Mask* act, dim3 grid, hipStream_t st, Args... args) {
+        if (act) hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, Mask> : corr_backward_k1_bf16<false, Mask>), grid, dim3(256), 0, st, args..., *act);
+        else hipLaunchKernelGGL((second ? corr_backward_k1_bf16<true, CorrBf16Grad> : corr_backward_k1_bf16<false, CorrBf16Grad>), grid, dim3(256), 0, st, args..., CorrBf16Grad{});
+    }
+    template <class... Args>
+    static void pair(const CorrBf16BwdRoles& roles, const CorrBf16BwdMasks* masks, dim3 grid, hipStream_t st, Args... args) {
+        if (masks) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, *masks, args...);
+        else hipLaunchKernelGGL(corr_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, args...);
+    }
+};
 
 extern "C" int vfi_correlation_backward_bf16(const void* input1, const void* input2, const void* gradoutput,
                                               void* gradinput1, void* gradinput2, int batch, int channel, int h, int w,
                                               int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
                                               vfi_stream_t stream) {
-    return corr_bf16_backward(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
-                              max_displacement, stride1, stride2, stream, CorrBf16Grad{}, INT64_MAX, INT64_MAX);
+    return corr_backward_both<CorrBwdBf16>(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                           max_displacement, stride1, stride2, stream);
 }
 
 // vfi_correlation_backward_bf16 of gradOutput masked by LeakyReLU's derivative: the same two launches of the masked kernels.
@@ -677,51 +572,9 @@ extern "C" int vfi_correlation_lrelu_backward_bf16(const void* input1, const voi
                                                     void* gradinput2, int batch, int channel, int h, int w, int pad_size,
                                                     int kernel_size, int max_displacement, int stride1, int stride2,
                                                     float negative_slope, vfi_stream_t stream) {
-    if (!y || !corr_bf16_slope_ok(negative_slope)) return VFI_ERR_SHAPE;
     const CorrBf16GradLrelu act = {(const bf16_t*)y, y_batch_stride, gradoutput_batch_stride, negative_slope};
-    return corr_bf16_backward(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
-                              max_displacement, stride1, stride2, stream, act, y_batch_stride, gradoutput_batch_stride);
-}
-
-// The backward of two calls of equal shape with any subset of the four gradients, as correlation_backward_pair_any
-// (correlation.hip) and with its compaction: PWC-Net's configuration is ONE launch of the pair kernel whose roles are the
-// requested gradients, the channel groups sized on the whole launch (tiles x batch x roles).  Any other configuration, or
-// roles x batch x groups beyond a grid's z: one launch per requested gradient with the kernels
-// vfi_correlation_backward_bf16 uses.  Either way a gradient's bits are that entry's.  `acts` (or NULL): the two items' masks.
-static int corr_bf16_backward_pair(const bf16_t* const (&in1)[2], const bf16_t* const (&in2)[2], const bf16_t* const (&go)[2],
-                                   bf16_t* const (&gi)[2][2], const CorrBf16GradLrelu* acts, int batch, int channel, int h, int w,
-                                   int pad_size, int kernel_size, int max_displacement, int stride1, int stride2, vfi_stream_t stream) {
-    int oc, oh, ow;
-    if (corr_check({}, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, true, &oc, &oh, &ow))
-        return VFI_ERR_SHAPE;
-    if (acts && !corr_bf16_slope_ok(acts[0].slope)) return VFI_ERR_SHAPE;
-    CorrBf16BwdRoles roles = {};
-    CorrBf16BwdMasks masks = {};
-    const int nroles = corr_backward_roles(in1, in2, go, gi, acts, (int64_t)oc * oh * ow, roles, masks);
-    if (nroles < 0) return VFI_ERR_SHAPE;
-    if (nroles == 0) return VFI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (kernel_size == 1 && stride2 == 1 && max_displacement == 4 && pad_size == 4 && batch <= 65535) {
-        int ch_per_group;
-        const int groups = corr_backward_groups(((w + 63) / 64) * ((h + 3) / 4), batch * nroles, channel, &ch_per_group);
-        if (groups) {
-            roles.per_role = batch * groups;
-            const dim3 grid((w + 63) / 64, (h + 3) / 4, nroles * roles.per_role);
-            if (acts) hipLaunchKernelGGL(corr_lrelu_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, masks, channel, h, w, groups, ch_per_group);
-            else hipLaunchKernelGGL(corr_backward_k1_pair_bf16, grid, dim3(256), 0, st, roles, channel, h, w, groups, ch_per_group);
-            return launch_status();
-        }
-    }
-    for (int k = 0; k < nroles; ++k) {
-        const CorrBwdRoleT<bf16_t>& r = roles.r[k];
-        const CorrBf16GradLrelu act = {masks.y[k], masks.ystride[k], masks.gstride[k], masks.slope};
-        const int err = acts ? corr_bf16_backward_one(r.second != 0, r.other, r.gout, r.gin, batch, channel, h, w, oc, oh, ow, pad_size,
-                                                      kernel_size, max_displacement, stride2, st, act)
-                             : corr_bf16_backward_one(r.second != 0, r.other, r.gout, r.gin, batch, channel, h, w, oc, oh, ow, pad_size,
-                                                      kernel_size, max_displacement, stride2, st, CorrBf16Grad{});
-        if (err != VFI_OK) return err;
-    }
-    return VFI_OK;
+    return corr_backward_both<CorrBwdBf16>(input1, input2, gradoutput, gradinput1, gradinput2, batch, channel, h, w, pad_size, kernel_size,
+                                           max_displacement, stride1, stride2, stream, &act);
 }
 
 extern "C" int vfi_correlation_backward_pair_bf16(
@@ -729,12 +582,9 @@ extern "C" int vfi_correlation_backward_pair_bf16(
     const void* input1_b, const void* input2_b, const void* gradoutput_b, void* gradinput1_b, void* gradinput2_b,
     int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
     vfi_stream_t stream) {
-    const bf16_t* const in1[2] = {(const bf16_t*)input1_a, (const bf16_t*)input1_b};
-    const bf16_t* const in2[2] = {(const bf16_t*)input2_a, (const bf16_t*)input2_b};
-    const bf16_t* const go[2] = {(const bf16_t*)gradoutput_a, (const bf16_t*)gradoutput_b};
-    bf16_t* const gi[2][2] = {{(bf16_t*)gradinput1_a, (bf16_t*)gradinput2_a}, {(bf16_t*)gradinput1_b, (bf16_t*)gradinput2_b}};
-    return corr_bf16_backward_pair(in1, in2, go, gi, nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
-                                   stride2, stream);
+    return corr_backward_pair<CorrBwdBf16>(corr_backward_items<bf16_t>(input1_a, input2_a, gradoutput_a, gradinput1_a, gradinput2_a, input1_b,
+                                                                       input2_b, gradoutput_b, gradinput1_b, gradinput2_b),
+                                           nullptr, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream);
 }
 
 extern "C" int vfi_correlation_lrelu_backward_pair_bf16(
@@ -744,12 +594,9 @@ extern "C" int vfi_correlation_lrelu_backward_pair_bf16(
     int64_t gradoutput_b_batch_stride, void* gradinput1_b, void* gradinput2_b,
     int batch, int channel, int h, int w, int pad_size, int kernel_size, int max_displacement, int stride1, int stride2,
     float negative_slope, vfi_stream_t stream) {
-    const bf16_t* const in1[2] = {(const bf16_t*)input1_a, (const bf16_t*)input1_b};
-    const bf16_t* const in2[2] = {(const bf16_t*)input2_a, (const bf16_t*)input2_b};
-    const bf16_t* const go[2] = {(const bf16_t*)gradoutput_a, (const bf16_t*)gradoutput_b};
-    bf16_t* const gi[2][2] = {{(bf16_t*)gradinput1_a, (bf16_t*)gradinput2_a}, {(bf16_t*)gradinput1_b, (bf16_t*)gradinput2_b}};
     const CorrBf16GradLrelu acts[2] = {{(const bf16_t*)y_a, y_a_batch_stride, gradoutput_a_batch_stride, negative_slope},
                                        {(const bf16_t*)y_b, y_b_batch_stride, gradoutput_b_batch_stride, negative_slope}};
-    return corr_bf16_backward_pair(in1, in2, go, gi, acts, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1,
-                                   stride2, stream);
+    return corr_backward_pair<CorrBwdBf16>(corr_backward_items<bf16_t>(input1_a, input2_a, gradoutput_a, gradinput1_a, gradinput2_a, input1_b,
+                                                                       input2_b, gradoutput_b, gradinput1_b, gradinput2_b),
+                                           acts, batch, channel, h, w, pad_size, kernel_size, max_displacement, stride1, stride2, stream);
 }
