@@ -1,10 +1,19 @@
 """ctypes caller of libvfi_hip.so (include/vfi_hip.h) for torch GPU tensors.
 
-Each function is the ctypes twin of one reference binding: it applies the
-binding's own shape/stride checks (returning 1 silently on a mismatch, like
-`filterinterpolation_cuda.cc:543-583`), then passes raw device pointers, sizes,
-element strides and torch's current HIP stream to the C ABI.  No arithmetic
-happens on this side.  torch is used for memory and streams only.
+Each function is the ctypes twin of one reference binding: it checks its
+tensors, then passes raw device pointers, sizes, element strides and torch's
+current HIP stream to the C ABI.  No arithmetic happens on this side.  torch is
+used for memory and streams only.
+
+The contract of every wrapper (tests/binding_cases.py states it as a table):
+a shape, rank or layout the library does not take returns 1, silently, like
+`filterinterpolation_cuda.cc:543-583` (a wrapper that allocates and returns
+tensors raises RuntimeError); a dtype or device it does not take raises
+RuntimeError; both before any library call.  The reference bindings check the
+flow's shape and a few strides; the checks here follow what the C entry
+addresses: every tensor's shape (`_shaped`, `_is4`), the layout of a tensor the
+entry reads or writes with another's strides (`_addressed_as`), and the dtype
+and device of all of them (`_on_gpu`).
 """
 import ctypes
 import math
@@ -189,6 +198,30 @@ def _dev(t, dtype=torch.float32):
     return t.device
 
 
+def _on_gpu(dtype, *tensors):
+    """same device and dtype, all of them (None entries: absent optional tensors); the device"""
+    device = None
+    for t in tensors:
+        if t is None:
+            continue
+        d = _dev(t, dtype)
+        if device is None:
+            device = d
+        elif d != device:
+            raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device (%s and %s)" % (device, d))
+    return device
+
+
+def _shaped(t, *shape):
+    """shape equals: a tensor of exactly these sizes, none of them zero"""
+    return t is not None and t.dim() == len(shape) and tuple(t.shape) == tuple(shape) and 0 not in shape
+
+
+def _is4(*tensors):
+    """NCHW tensors with something in them"""
+    return all(t is not None and t.dim() == 4 and 0 not in t.shape for t in tensors)
+
+
 def _stream(t, dtype=torch.float32):
     return ctypes.c_void_p(torch.cuda.current_stream(_dev(t, dtype)).cuda_stream)
 
@@ -202,12 +235,17 @@ def _finish(err):
 # ---------------------------------------------------------------- filterinterpolation_cuda
 
 def _fi_checks(input1, input2, input3, out_like):
+    """The reference binding's checks (filterinterpolation_cuda.cc:543-583) and what it leaves to the caller: the flow is
+    [B, 2, H, W], the filter one plane of taps per pixel, and out_like -- addressed with input1's strides -- is laid out as
+    input1."""
+    if not _is4(input1, input2, input3):
+        return None
     b, c, h, w = input1.shape
-    if input2.size(0) != b or input2.size(1) != 2 or input2.size(2) != h or input2.size(3) != w:
+    if not _shaped(input2, b, 2, h, w) or not _fi_filter_ok(input1, input3):
         return None
     if input1.stride(3) != 1 or input2.stride(3) != 1 or input3.stride(3) != 1:
         return None
-    if out_like is not None and (input1.stride(0) != out_like.stride(0) or input1.stride(1) != out_like.stride(1)):
+    if out_like is not None and not _addressed_as(input1, out_like):
         return None
     return b, c, h, w
 
@@ -217,7 +255,7 @@ def filterinterp_forward_ori(input1, input2, input3, output, direct=False):
     if dims is None:
         return 1
     b, c, h, w = dims
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, output)):
         fn = lib().vfi_filterinterp_forward_ori_direct if direct else lib().vfi_filterinterp_forward_ori
         return _finish(fn(_ptr(input1), _ptr(input2), _ptr(input3), _ptr(output), b, c, h, w, input3.size(1),
                           _st(input1), _st(input2), _st(input3), _stream(input1)))
@@ -228,8 +266,9 @@ def _fi_image_dtype(images, floats):
     all bfloat16 -- the `_bf16` entries -- or all float32; the flows and the filter (`floats`) are float32 either way.
     float16 and every mix raise here, before any library call."""
     dtype, suffix = _bf16_or_f32(*images)
-    for t in floats:
-        _dev(t)
+    _on_gpu(torch.float32, *floats)
+    if _dev(floats[0]) != images[0].device:
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
     return dtype, suffix
 
 
@@ -238,7 +277,7 @@ def filterinterp_forward_ori_multi(input1, flows, input3, outputs):
     input1 and the outputs float32, or all bfloat16 (vfi_filterinterp_forward_ori_multi_to_bf16 with the outputs laid out as
     input1: bf16_rne of the float32 call on the widened image, bit for bit); flows and filter float32 always."""
     n = len(flows)
-    if n == 0 or len(outputs) != n:
+    if n == 0 or len(outputs) != n or None in flows or None in outputs:
         return 1
     for fl, out in zip(flows, outputs):
         # (layouts compared as _same_strides does: the stride of a size-1 dimension is arbitrary, e.g. after slicing)
@@ -266,7 +305,7 @@ def filterinterp_forward_ori_multi_to(input1, flows, input3, outputs, direct=Fal
     bfloat16 destination slice needs 2-byte alignment only); direct=True (bfloat16 only): the one-thread-per-pixel kernel,
     an internal entry point the tests compare the staged kernel with."""
     n = len(flows)
-    if n == 0 or len(outputs) != n:
+    if n == 0 or len(outputs) != n or None in flows or None in outputs:
         return 1
     for fl, out in zip(flows, outputs):
         if _fi_checks(input1, fl, input3, None) is None or not _same_strides(fl, flows[0]):
@@ -307,7 +346,7 @@ def filterinterp_forward_nhwc_multi_to(image, flows, filt, outs):
     A shape or layout the library does not take returns 1; a dtype or device it does not take raises, both before any
     library call.  The destinations must not overlap the inputs or each other (not checked)."""
     n = len(flows)
-    if n == 0 or len(outs) != n or image.dim() != 4 or filt.dim() != 4:
+    if n == 0 or len(outs) != n or None in flows or None in outs or image.dim() != 4 or filt.dim() != 4:
         return 1
     b, c, h, w = image.shape
     if not _channels_innermost(image) or not _fi_filter_ok(image, filt) or filt.size(1) < 1 or 0 in image.shape:
@@ -328,6 +367,13 @@ def filterinterp_forward_nhwc_multi_to(image, flows, filt, outs):
 
 def filterinterp_nhwc_access_width(image, filt, outs):
     """the access width, in elements, filterinterp_forward_nhwc_multi_to runs these tensors with (host code, no launch)"""
+    if len(outs) == 0 or None in outs or not _is4(image, filt, *outs) or not _fi_filter_ok(image, filt) or \
+            not _channels_innermost(image) or \
+            not all(o.shape == image.shape and _channels_innermost(o) and _same_strides(o, outs[0]) for o in outs):
+        raise RuntimeError("filterinterp_nhwc_access_width: not the tensors of a filterinterp_forward_nhwc_multi_to call")
+    _bf16_or_f32(image, *outs)
+    if _dev(filt) != image.device:
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
     op = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
     b, _, h, w = image.shape
     return lib().vfi_filterinterp_nhwc_access_width(image.element_size(), _ptr(image), op, len(outs), b, h, w, filt.size(1),
@@ -340,8 +386,9 @@ def filterinterp_forward_ori_f16(input1, input2, input3, output, direct=False):
     if dims is None or output.stride(3) != 1:
         return 1
     b, c, h, w = dims
-    _dev(input2), _dev(input3), _dev(output, torch.float16)
-    with torch.cuda.device(_dev(input1, torch.float16)):
+    if _on_gpu(torch.float32, input2, input3) != _on_gpu(torch.float16, input1, output):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
+    with torch.cuda.device(input1.device):
         fn = lib().vfi_filterinterp_forward_ori_f16_direct if direct else lib().vfi_filterinterp_forward_ori_f16
         return _finish(fn(_ptr(input1), _ptr(input2), _ptr(input3), _ptr(output), b, c, h, w, input3.size(1),
                           _st(input1), _st(input2), _st(input3), _stream(input2)))
@@ -356,7 +403,7 @@ def filterinterp_backward_ori(input1, input2, input3, gradoutput, gradinput1, gr
             not _addressed_as(input3, gradinput3) or not _fi_filter_ok(input1, input3):
         return 1
     b, c, h, w = dims
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)):
         return _finish(lib().vfi_filterinterp_backward_ori(
             _ptr(input1), _ptr(input2), _ptr(input3), _ptr(gradoutput), _ptr(gradinput1), _ptr(gradinput2),
             _ptr(gradinput3), b, c, h, w, input3.size(1), _st(input1), _st(input2), _st(input3), _stream(input1)))
@@ -368,11 +415,11 @@ def filterinterp_backward_ori_image_multi(flows, input3, gradoutputs, gradinput1
     The gradients and gradinput1 float32, or all bfloat16 (vfi_filterinterp_backward_ori_image_multi_bf16: bf16_rne of the
     float32 call on the widened gradients, bit for bit); flows and filter float32 always."""
     n = len(flows)
-    if n == 0 or len(gradoutputs) != n:
+    if n == 0 or len(gradoutputs) != n or None in flows or None in gradoutputs:
         return 1
     for fl, g in zip(flows, gradoutputs):
         # gradinput1 in the image's place: the binding's checks, then one layout per list and the gradients shaped like gradinput1
-        if _fi_checks(gradinput1, fl, input3, None) is None or not _same_strides(fl, flows[0]) or \
+        if _fi_checks(gradinput1, fl, input3, None) is None or not _same_strides(fl, flows[0]) or g is None or \
                 g.dim() != 4 or g.shape != gradinput1.shape or g.stride(3) != 1 or not _same_strides(g, gradoutputs[0]):
             return 1
     if not _fi_filter_ok(gradinput1, input3):
@@ -390,19 +437,24 @@ def filterinterp_backward_ori_image_multi(flows, input3, gradoutputs, gradinput1
 def filterinterp_forward_defor(variant, input1, input2, input3, input4, output, general=False):
     """variant: DEFOR_OFFSET (4-input forward), DEFOR_REGION (deforconv), DEFOR_NOFILTER (input4 = None).
     general=True: always the one-thread-per-pixel kernel (an internal entry point the tests compare the staged one with)."""
-    dims = _fi_checks(input1, input2, input3, output if variant == DEFOR_NOFILTER else None)
+    # (the kernels address the output with input1's strides in every variant)
+    dims = _fi_checks(input1, input2, input3, output)
     if dims is None:
         return 1
     b, c, h, w = dims
     if variant == DEFOR_NOFILTER:
         fs = int(math.sqrt(input3.size(1) // 2))
         p4, s4 = ctypes.c_void_p(0), _st(input3)
-    else:
-        if input4.stride(3) != 1:
+        if 2 * fs * fs > input3.size(1):
             return 1
+        input4 = None
+    else:
         fs = int(math.sqrt(input3.size(1)))
+        # input4: the 2 * fs * fs offsets of every pixel
+        if not _is4(input4) or input4.stride(3) != 1 or not _fi_filter_ok(input1, input4) or input4.size(1) < 2 * fs * fs:
+            return 1
         p4, s4 = _ptr(input4), _st(input4)
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, input4, output)):
         fn = lib().vfi_filterinterp_forward_defor_general if general else lib().vfi_filterinterp_forward_defor
         return _finish(fn(variant, _ptr(input1), _ptr(input2), _ptr(input3), p4, _ptr(output), b, c, h, w, fs, _st(input1),
                           _st(input2), _st(input3), s4, _stream(input1)))
@@ -421,12 +473,15 @@ def filterinterp_backward_defor(variant, input1, input2, input3, input4, gradout
     if variant == DEFOR_NOFILTER:
         fs = int(math.sqrt(input3.size(1) // 2))
         p4, g4, s4 = ctypes.c_void_p(0), ctypes.c_void_p(0), _st(input3)
+        input4 = gradinput4 = None
     else:
-        if input4.stride(3) != 1 or not _addressed_as(input4, gradinput4) or not _fi_filter_ok(input1, input4):
-            return 1
         fs = int(math.sqrt(input3.size(1)))
+        if not _is4(input4) or input4.stride(3) != 1 or not _addressed_as(input4, gradinput4) or \
+                not _fi_filter_ok(input1, input4) or input4.size(1) < 2 * fs * fs:
+            return 1
         p4, g4, s4 = _ptr(input4), _ptr(gradinput4), _st(input4)
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, input4, gradoutput, gradinput1, gradinput2, gradinput3,
+                                   gradinput4)):
         return _finish(lib().vfi_filterinterp_backward_defor(
             variant, _ptr(input1), _ptr(input2), _ptr(input3), p4, _ptr(gradoutput), _ptr(gradinput1),
             _ptr(gradinput2), _ptr(gradinput3), g4, b, c, h, w, fs, _st(input1), _st(input2), _st(input3), s4,
@@ -435,13 +490,24 @@ def filterinterp_backward_defor(variant, input1, input2, input3, input4, gradout
 
 # ---------------------------------------------------------------- flowprojection_cuda / depthflowprojection_cuda
 
-def flowprojection_forward(input1, count, output, fillhole):
-    if input1.size(1) != 2:
-        return 1
-    if input1.stride(0) != output.stride(0) or input1.stride(1) != output.stride(1):
-        return 1
+def _proj_checks(input1, planes, like_input1):
+    """(b, h, w) of a projection call: the flow [B, 2, H, W], `planes` (count, depth) [B, 1, H, W] with strides of their own,
+    `like_input1` (the output, the gradients) addressed with the flow's strides; w stride 1 everywhere"""
+    if not _is4(input1) or input1.size(1) != 2:
+        return None
     b, _, h, w = input1.shape
-    with torch.cuda.device(_dev(input1)):
+    if not all(_shaped(t, b, 1, h, w) for t in planes) or not _addressed_as(input1, *like_input1) or \
+            not _nchw_ok(input1, *planes):
+        return None
+    return b, h, w
+
+
+def flowprojection_forward(input1, count, output, fillhole):
+    dims = _proj_checks(input1, (count,), (output,))
+    if dims is None:
+        return 1
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, count, output)):
         return _finish(lib().vfi_flowprojection_forward(_ptr(input1), _ptr(count), _ptr(output), b, h, w,
                                                         int(fillhole), _st(input1), _st(count), _stream(input1)))
 
@@ -450,26 +516,29 @@ def flowprojection_forward_batch(inputs1, counts, outputs, fillhole, inputs2=Non
     """The list form of flowprojection_forward / depthflowprojection_forward (inputs2: one depth tensor per item, or one
     tensor shared by all): every item in one launch triple.  Items share shape and strides."""
     n = len(inputs1)
-    if n == 0 or len(counts) != n or len(outputs) != n:
+    if n == 0 or len(counts) != n or len(outputs) != n or None in inputs1 or None in counts or None in outputs:
         return 1
     if inputs2 is not None and not isinstance(inputs2, (list, tuple)):
         inputs2 = [inputs2] * n
-    if inputs2 is not None and len(inputs2) != n:
+    if inputs2 is not None and (len(inputs2) != n or None in inputs2):
         return 1
     f0, c0 = inputs1[0], counts[0]
+    if _proj_checks(f0, (c0,), (outputs[0],)) is None:
+        return 1
     b, _, h, w = f0.shape
     for i in range(n):
         fl, cn, out = inputs1[i], counts[i], outputs[i]
-        if fl.size(1) != 2 or tuple(fl.shape) != tuple(f0.shape) or tuple(out.shape) != tuple(f0.shape) or tuple(cn.shape) != (b, 1, h, w):
+        if fl.dim() != 4 or fl.size(1) != 2 or tuple(fl.shape) != tuple(f0.shape) or tuple(out.shape) != tuple(f0.shape) or tuple(cn.shape) != (b, 1, h, w):
             return 1
         if not _same_strides(fl, f0) or not _same_strides(out, f0) or not _same_strides(cn, c0):
             return 1
         _dev(fl), _dev(cn), _dev(out)
         if inputs2 is not None:
             d = inputs2[i]
-            if tuple(d.shape) != (b, 1, h, w) or not _same_strides(d, inputs2[0]):
+            if not _shaped(d, b, 1, h, w) or d.stride(3) != 1 or not _same_strides(d, inputs2[0]):
                 return 1
             _dev(d)
+    _on_gpu(torch.float32, *inputs1, *counts, *outputs, *(inputs2 or ()))
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])     # noqa: E731
     with torch.cuda.device(_dev(f0)):
         if inputs2 is None:
@@ -493,37 +562,34 @@ def release_workspaces():
 
 
 def flowprojection_backward(input1, count, gradoutput, gradinput1):
-    b, _, h, w = input1.shape
-    if input1.size(1) != 2 or tuple(count.shape) != (b, 1, h, w):
+    dims = _proj_checks(input1, (count,), (gradoutput, gradinput1))
+    if dims is None:
         return 1
-    if not _addressed_as(input1, gradoutput, gradinput1):
-        return 1
-    with torch.cuda.device(_dev(input1)):
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, count, gradoutput, gradinput1)):
         return _finish(lib().vfi_flowprojection_backward(_ptr(input1), _ptr(count), _ptr(gradoutput),
                                                          _ptr(gradinput1), b, h, w, _st(input1), _st(count),
                                                          _stream(input1)))
 
 
 def depthflowprojection_forward(input1, input2, count, output, fillhole):
-    if input1.size(1) != 2 or input2.size(1) != 1:
+    dims = _proj_checks(input1, (input2, count), (output,))
+    if dims is None:
         return 1
-    if input1.stride(0) != output.stride(0) or input1.stride(1) != output.stride(1):
-        return 1
-    b, _, h, w = input1.shape
-    with torch.cuda.device(_dev(input1)):
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, count, output)):
         return _finish(lib().vfi_depthflowprojection_forward(
             _ptr(input1), _ptr(input2), _ptr(count), _ptr(output), b, h, w, int(fillhole), _st(input1), _st(input2),
             _st(count), _stream(input1)))
 
 
 def depthflowprojection_backward(input1, input2, count, output, gradoutput, gradinput1, gradinput2):
-    b, _, h, w = input1.shape
-    if input1.size(1) != 2 or tuple(input2.shape) != (b, 1, h, w) or tuple(count.shape) != (b, 1, h, w):
-        return 1
     # output, gradoutput and gradinput1 are addressed with input1's strides, gradinput2 with input2's
-    if not _addressed_as(input1, output, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2):
+    dims = _proj_checks(input1, (input2, count), (output, gradoutput, gradinput1))
+    if dims is None or not _addressed_as(input2, gradinput2):
         return 1
-    with torch.cuda.device(_dev(input1)):
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, count, output, gradoutput, gradinput1, gradinput2)):
         return _finish(lib().vfi_depthflowprojection_backward(
             _ptr(input1), _ptr(input2), _ptr(count), _ptr(output), _ptr(gradoutput), _ptr(gradinput1),
             _ptr(gradinput2), b, h, w, _st(input1), _st(input2), _st(count), _stream(input1)))
@@ -531,12 +597,11 @@ def depthflowprojection_backward(input1, input2, count, output, gradoutput, grad
 
 def mindepthflowprojection_forward(input1, input2, count, output, fillhole):
     """mindepthflowprojection_cuda.cc:12-66; count and output zero-filled by the caller."""
-    if input1.size(1) != 2 or input2.size(1) != 1:
+    dims = _proj_checks(input1, (input2, count), (output,))
+    if dims is None:
         return 1
-    if input1.stride(0) != output.stride(0) or input1.stride(1) != output.stride(1):
-        return 1
-    b, _, h, w = input1.shape
-    with torch.cuda.device(_dev(input1)):
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, count, output)):
         return _finish(lib().vfi_mindepthflowprojection_forward(
             _ptr(input1), _ptr(input2), _ptr(count), _ptr(output), b, h, w, int(fillhole), _st(input1), _st(input2),
             _st(count), _stream(input1)))
@@ -544,12 +609,11 @@ def mindepthflowprojection_forward(input1, input2, count, output, fillhole):
 
 def mindepthflowprojection_backward(input1, input2, count, output, gradoutput, gradinput1, gradinput2):
     """mindepthflowprojection_cuda.cc:68-139; `output` and `gradinput2` are accepted and unused, as in the reference."""
-    b, _, h, w = input1.shape
-    if input1.size(1) != 2 or tuple(input2.shape) != (b, 1, h, w) or tuple(count.shape) != (b, 1, h, w):
+    dims = _proj_checks(input1, (input2, count), (gradoutput, gradinput1))
+    if dims is None:
         return 1
-    if not _addressed_as(input1, gradoutput, gradinput1):
-        return 1
-    with torch.cuda.device(_dev(input1)):
+    b, h, w = dims
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, count, gradoutput, gradinput1)):
         return _finish(lib().vfi_mindepthflowprojection_backward(
             _ptr(input1), _ptr(input2), _ptr(count), _ptr(gradoutput), _ptr(gradinput1), b, h, w, _st(input1),
             _st(input2), _st(count), _stream(input1)))
@@ -558,27 +622,31 @@ def mindepthflowprojection_backward(input1, input2, count, output, gradoutput, g
 # ---------------------------------------------------------------- interpolation_cuda / interpolationch_cuda
 
 def interpolation_forward(input1, input2, output, require_c3=False):
+    if not _is4(input1):
+        return 1
     b, c, h, w = input1.shape
     if require_c3 and c != 3:
         return 1
-    if tuple(input2.shape) != (b, 2, h, w):
+    if not _shaped(input2, b, 2, h, w) or not _nchw_ok(input1, input2):
         return 1
-    if input1.stride(0) != output.stride(0) or input1.stride(1) != output.stride(1):
+    if not _addressed_as(input1, output):
         return 1
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, output)):
         return _finish(lib().vfi_interpolation_forward(_ptr(input1), _ptr(input2), _ptr(output), b, c, h, w,
                                                        _st(input1), _st(input2), _stream(input1)))
 
 
 def interpolation_backward(input1, input2, gradoutput, gradinput1, gradinput2, require_c3=False):
+    if not _is4(input1):
+        return 1
     b, c, h, w = input1.shape
     if require_c3 and c != 3:
         return 1
-    if tuple(input2.shape) != (b, 2, h, w) or input1.stride(3) != 1 or input2.stride(3) != 1:
+    if not _shaped(input2, b, 2, h, w) or input1.stride(3) != 1 or input2.stride(3) != 1:
         return 1
     if not _addressed_as(input1, gradoutput, gradinput1) or not _addressed_as(input2, gradinput2):
         return 1
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, gradoutput, gradinput1, gradinput2)):
         return _finish(lib().vfi_interpolation_backward(_ptr(input1), _ptr(input2), _ptr(gradoutput),
                                                         _ptr(gradinput1), _ptr(gradinput2), b, c, h, w, _st(input1),
                                                         _st(input2), _stream(input1)))
@@ -588,11 +656,13 @@ def interpolation_backward(input1, input2, gradoutput, gradinput1, gradinput2, r
 
 def _sep_checks(input1, input2, input3, require_c3=True):
     """require_c3: the reference's wrappers refuse any other channel count (separableconv_cuda.cc); the library takes any."""
+    if not _is4(input1, input2, input3):
+        return None
     b, c, h, w = input1.shape
     fs = input2.size(1)
     if (require_c3 and c != 3) or input2.size(0) != b or input2.size(1) != input3.size(1):
         return None
-    if input2.size(2) != h - fs + 1 or input2.size(3) != w - fs + 1:
+    if input2.size(2) != h - fs + 1 or input2.size(3) != w - fs + 1 or input3.shape != input2.shape:
         return None
     if input1.stride(3) != 1 or input2.stride(3) != 1 or input3.stride(3) != 1:
         return None
@@ -603,10 +673,12 @@ def _sep_checks(input1, input2, input3, require_c3=True):
 
 def separableconv_forward(input1, input2, input3, output, require_c3=True):
     dims = _sep_checks(input1, input2, input3, require_c3)
-    if dims is None or output.stride(3) != 1:
+    if dims is None:
         return 1
     b, c, h, w, fs = dims
-    with torch.cuda.device(_dev(input1)):
+    if not _shaped(output, b, c, h - fs + 1, w - fs + 1) or output.stride(3) != 1:
+        return 1
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, output)):
         return _finish(lib().vfi_separableconv_forward(_ptr(input1), _ptr(input2), _ptr(input3), _ptr(output), b, c,
                                                        h, w, fs, _st(input1), _st(input2), _st(input3), _st(output),
                                                        _stream(input1)))
@@ -614,14 +686,14 @@ def separableconv_forward(input1, input2, input3, output, require_c3=True):
 
 def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3, require_c3=True):
     dims = _sep_checks(input1, input2, input3, require_c3)
-    if dims is None or gradoutput.stride(3) != 1:
+    if dims is None or gradoutput is None or gradoutput.dim() != 4 or gradoutput.stride(3) != 1:
         return 1
     if not _addressed_as(input1, gradinput1) or not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):
         return 1
     b, c, h, w, fs = dims
     if tuple(gradoutput.shape) != (b, c, h - fs + 1, w - fs + 1):
         return 1
-    with torch.cuda.device(_dev(input1)):
+    with torch.cuda.device(_on_gpu(torch.float32, input1, input2, input3, gradoutput, gradinput1, gradinput2, gradinput3)):
         return _finish(lib().vfi_separableconv_backward(
             _ptr(input1), _ptr(input2), _ptr(input3), _ptr(gradoutput), _ptr(gradinput1), _ptr(gradinput2),
             _ptr(gradinput3), b, c, h, w, fs, _st(input1), _st(input2), _st(input3), _st(gradoutput),
@@ -630,10 +702,12 @@ def separableconv_backward(input1, input2, input3, gradoutput, gradinput1, gradi
 
 def separableconvflow_forward(input1, input2, input3, flow_output, require_c3=True):
     dims = _sep_checks(input1, input2, input3, require_c3)
-    if dims is None or flow_output.stride(3) != 1:
+    if dims is None:
         return 1
     b, c, h, w, fs = dims
-    with torch.cuda.device(_dev(input2)):
+    if not _shaped(flow_output, b, 2, h - fs + 1, w - fs + 1) or flow_output.stride(3) != 1:
+        return 1
+    with torch.cuda.device(_on_gpu(torch.float32, input2, input1, input3, flow_output)):
         return _finish(lib().vfi_separableconvflow_forward(_ptr(input2), _ptr(input3), _ptr(flow_output), b, h, w,
                                                            fs, _st(input2), _st(input3), _st(flow_output),
                                                            _stream(input2)))
@@ -641,14 +715,14 @@ def separableconvflow_forward(input1, input2, input3, flow_output, require_c3=Tr
 
 def separableconvflow_backward(input1, input2, input3, gradflow_output, gradinput2, gradinput3, require_c3=True):
     dims = _sep_checks(input1, input2, input3, require_c3)
-    if dims is None or gradflow_output.stride(3) != 1:
+    if dims is None or gradflow_output is None or gradflow_output.dim() != 4 or gradflow_output.stride(3) != 1:
         return 1
     if not _addressed_as(input2, gradinput2) or not _addressed_as(input3, gradinput3):
         return 1
     b, c, h, w, fs = dims
     if tuple(gradflow_output.shape) != (b, 2, h - fs + 1, w - fs + 1):
         return 1
-    with torch.cuda.device(_dev(input2)):
+    with torch.cuda.device(_on_gpu(torch.float32, input2, input1, input3, gradflow_output, gradinput2, gradinput3)):
         return _finish(lib().vfi_separableconvflow_backward(
             _ptr(input2), _ptr(input3), _ptr(gradflow_output), _ptr(gradinput2), _ptr(gradinput3), b, h, w, fs,
             _st(input2), _st(input3), _st(gradflow_output), _stream(input2)))
@@ -672,9 +746,8 @@ def _corr_call(f32_name, tensors, *args):
     """The float entry; for float16 tensors the reference's at::Half instantiation and for bfloat16 tensors the `_bf16` entry
     (no conversion; every tensor is checked for dtype and device), on the tensors' stream."""
     suffix = _CORR_SUFFIX.get(tensors[0].dtype)
-    for t in tensors:                                       # (a 2-byte tensor behind a float32 first one would be read past its end)
-        _dev(t, tensors[0].dtype if suffix else torch.float32)
-    device = tensors[0].device
+    # (a 2-byte tensor behind a float32 first one would be read past its end)
+    device = _on_gpu(tensors[0].dtype if suffix else torch.float32, *tensors)
     with torch.cuda.device(device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         err = getattr(lib(), f32_name + (suffix or ""))(*[_ptr(t) for t in tensors], *args, stream)
@@ -682,10 +755,18 @@ def _corr_call(f32_name, tensors, *args):
         raise RuntimeError("CUDA call failed")
 
 
+def _corr_inputs(what, first, *rest):
+    """the feature maps of a correlation call: [B, C, H, W], all of one shape (any strides: they are made contiguous)"""
+    if not _is4(first) or any(t is None or t.dim() != 4 or t.shape != first.shape for t in rest):
+        raise RuntimeError("%s: the inputs must be [B, C, H, W] tensors of one shape, none of it zero" % what)
+
+
 def correlation_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2):
     """Allocates and returns the output, as the reference binding resizes its `output` argument.  float32, float16 (the
     reference's at::Half arithmetic) or bfloat16 (exact products, float32 sums, one rounding: include/vfi_hip.h) -- the
     output has the inputs' dtype."""
+    _corr_inputs("correlation_forward", input1, input2)
+    _on_gpu(input1.dtype if input1.dtype in _CORR_SUFFIX else torch.float32, input1, input2)
     input1, input2 = input1.contiguous(), input2.contiguous()
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
@@ -700,12 +781,14 @@ def correlation_forward_bf16_kernel(which, input1, input2, pad_size, kernel_size
     """correlation_forward on bfloat16 tensors through ONE of its two kernels whatever the tile count (internal: tests and
     tools/bench_corr_bf16.py).  which: "mfma" (PWC-Net's configuration only) or "generic".  `out`: a dense bfloat16 tensor
     (or view) of the output's shape to write into."""
+    _corr_inputs("correlation_forward_bf16_kernel", input1, input2)
+    _on_gpu(torch.bfloat16, input1, input2, out)
     input1, input2 = input1.contiguous(), input2.contiguous()
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if out is None:
         out = torch.empty((b, oc, oh, ow), dtype=torch.bfloat16, device=input1.device)
-    if tuple(out.shape) != (b, oc, oh, ow) or not out.is_contiguous():
+    if out.dim() != 4 or tuple(out.shape) != (b, oc, oh, ow) or not out.is_contiguous():
         raise RuntimeError("correlation_forward_bf16_kernel: `out` must be a dense tensor of the output's shape")
     for t in (input1, input2, out):
         _dev(t, torch.bfloat16)
@@ -723,10 +806,8 @@ def correlation_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displace
     """(correlation_forward(a1, a2, ...), correlation_forward(b1, b2, ...)) from one launch: equal shapes, all four float32
     or all four bfloat16 (vfi_correlation_forward_pair_bf16: each output bit-equal to correlation_forward's on its item);
     the outputs have the inputs' dtype."""
+    _corr_inputs("correlation_forward_pair", a1, a2, b1, b2)
     dtype, suffix = _bf16_or_f32(a1, a2, b1, b2)
-    for t in (a1, a2, b1, b2):
-        if tuple(t.shape) != tuple(a1.shape):
-            raise RuntimeError("correlation_forward_pair: the four inputs must have one shape")
     a1, a2, b1, b2 = (t.contiguous() for t in (a1, a2, b1, b2))
     b, c, h, w = a1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
@@ -742,6 +823,8 @@ def correlation_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_displace
 
 
 def correlation_backward(input1, input2, gradoutput, pad_size, kernel_size, max_displacement, stride1, stride2):
+    _corr_inputs("correlation_backward", input1, input2)
+    _on_gpu(input1.dtype if input1.dtype in _CORR_SUFFIX else torch.float32, input1, input2, gradoutput)
     input1, input2, gradoutput = input1.contiguous(), input2.contiguous(), gradoutput.contiguous()
     b, c, h, w = input1.shape
     if input2.shape != input1.shape or \
@@ -760,6 +843,7 @@ def correlation_backward_pair(a1, a2, ga, b1, b2, gb, pad_size, kernel_size, max
     (grad a1, grad a2, grad b1, grad b2), each written in full, of the inputs' dtype and bit-equal to the single call's;
     None where `want` says so or where that item's gradoutput is None (such a gradient costs nothing)."""
     inputs = (a1, a2, b1, b2)
+    _corr_inputs("correlation_backward_pair", *inputs)
     b, c, h, w = a1.shape
     gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if len(want) != 4 or any(tuple(t.shape) != tuple(a1.shape) for t in inputs) or \
@@ -808,11 +892,12 @@ def _slope(negative_slope):
 def _lrelu_out(out, shape, like, what, dtype=torch.float32):
     if out is None:
         return torch.empty(shape, device=like.device, dtype=dtype)
-    if tuple(out.shape) != tuple(shape):
+    if out.dim() != 4 or tuple(out.shape) != tuple(shape):
         raise RuntimeError("%s: out= must have the output dimensions %s" % (what, tuple(shape)))
     if not _dense_planes(out):
         raise RuntimeError("%s: out= must have dense planes (a channel slice of a contiguous NCHW buffer)" % what)
-    _dev(out, dtype)
+    if _dev(out, dtype) != like.device:
+        raise RuntimeError("%s: out= must live on the inputs' device" % what)
     return out
 
 
@@ -820,8 +905,7 @@ def _bf16_or_f32(first, *rest):
     """The dtype a call with `_bf16` twins runs in -- bfloat16 when its first tensor is, float32 otherwise -- after checking
     every tensor for it and for the device (float16 and a bfloat16 / float32 mix raise here, before any library call)."""
     dtype = torch.bfloat16 if first.dtype == torch.bfloat16 else torch.float32
-    for t in (first, *rest):
-        _dev(t, dtype)
+    _on_gpu(dtype, first, *rest)
     return dtype, ("_bf16" if dtype == torch.bfloat16 else "")
 
 
@@ -832,8 +916,7 @@ def correlation_lrelu_forward(input1, input2, pad_size, kernel_size, max_displac
     out=: where to write it -- a tensor of the output's shape whose planes are dense, such as buf[:, k:k + 81] of a
     contiguous NCHW buffer; returned as it is."""
     slope = _slope(negative_slope)
-    if tuple(input2.shape) != tuple(input1.shape):
-        raise RuntimeError("correlation_lrelu_forward: the two inputs must have one shape")
+    _corr_inputs("correlation_lrelu_forward", input1, input2)
     b, c, h, w = input1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if out is not None:                                     # (its shape and layout first, then everybody's dtype and device)
@@ -857,8 +940,7 @@ def correlation_lrelu_forward_pair(a1, a2, b1, b2, pad_size, kernel_size, max_di
     out=: a pair of destinations (either may be None), each as correlation_lrelu_forward's.  float32, or bfloat16 for every
     tensor, out= included (vfi_correlation_lrelu_forward_pair_bf16: each output bit-equal to correlation_lrelu_forward's)."""
     slope = _slope(negative_slope)
-    if any(tuple(t.shape) != tuple(a1.shape) for t in (a1, a2, b1, b2)):
-        raise RuntimeError("correlation_lrelu_forward_pair: the four inputs must have one shape")
+    _corr_inputs("correlation_lrelu_forward_pair", a1, a2, b1, b2)
     b, c, h, w = a1.shape
     oc, oh, ow = correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     outs = tuple(out) if out is not None else (None, None)
@@ -889,6 +971,7 @@ def correlation_lrelu_backward(input1, input2, y, gradoutput, pad_size, kernel_s
     bfloat16 for all four tensors (vfi_correlation_lrelu_backward_bf16: g * negative_slope is rounded to bfloat16, as a
     materialised masked gradient would be)."""
     slope = _slope(negative_slope)
+    _corr_inputs("correlation_lrelu_backward", input1, input2)
     b, c, h, w = input1.shape
     gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if input2.shape != input1.shape or tuple(gradoutput.shape) != gshape or tuple(y.shape) != gshape:
@@ -914,6 +997,7 @@ def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, ke
     for every tensor (vfi_correlation_lrelu_backward_pair_bf16)."""
     slope = _slope(negative_slope)
     inputs = (a1, a2, b1, b2)
+    _corr_inputs("correlation_lrelu_backward_pair", *inputs)
     b, c, h, w = a1.shape
     gshape = (b,) + correlation_output_dims(h, w, pad_size, kernel_size, max_displacement, stride1, stride2)
     if len(want) != 4 or any(tuple(t.shape) != tuple(a1.shape) for t in inputs) or \
@@ -940,41 +1024,38 @@ def correlation_lrelu_backward_pair(a1, a2, ya, ga, b1, b2, yb, gb, pad_size, ke
 # ---------------------------------------------------------------- glue either side of the ops
 
 def _nchw_ok(*tensors):
-    return all(t.dim() == 4 and t.stride(3) == 1 for t in tensors)
+    return all(t is not None and t.dim() == 4 and t.stride(3) == 1 for t in tensors)
 
 
 def flow_upsample4(input, output, mul0, mul1):
-    b, c, hq, wq = input.shape
-    if not _nchw_ok(input, output) or tuple(output.shape) != (b, c, 4 * hq, 4 * wq):
+    if not _is4(input) or not _nchw_ok(input, output) or not _shaped(output, input.size(0), input.size(1), 4 * input.size(2), 4 * input.size(3)):
         return 1
-    _dev(output)
-    with torch.cuda.device(_dev(input)):
+    b, c, hq, wq = input.shape
+    with torch.cuda.device(_on_gpu(torch.float32, input, output)):
         return _finish(lib().vfi_flow_upsample4(_ptr(input), _ptr(output), b, c, hq, wq, mul0, mul1, _st(input),
                                                 _st(output), _stream(input)))
 
 
 def flowprojection_forward_up4(flow_q, count, output, mul0, mul1, fillhole):
+    if not _is4(flow_q) or not _nchw_ok(flow_q, count, output):
+        return 1
     b, c, hq, wq = flow_q.shape
-    if c != 2 or not _nchw_ok(flow_q, count, output):
+    if c != 2 or tuple(output.shape) != (b, 2, 4 * hq, 4 * wq) or tuple(count.shape) != (b, 1, 4 * hq, 4 * wq):
         return 1
-    if tuple(output.shape) != (b, 2, 4 * hq, 4 * wq) or tuple(count.shape) != (b, 1, 4 * hq, 4 * wq):
-        return 1
-    _dev(count), _dev(output)
-    with torch.cuda.device(_dev(flow_q)):
+    with torch.cuda.device(_on_gpu(torch.float32, flow_q, count, output)):
         return _finish(lib().vfi_flowprojection_forward_up4(_ptr(flow_q), _ptr(count), _ptr(output), b, hq, wq, mul0,
                                                             mul1, int(fillhole), _st(flow_q), _st(count), _st(output),
                                                             _stream(flow_q)))
 
 
 def depthflowprojection_forward_up4(flow_q, input2, count, output, mul0, mul1, fillhole):
+    if not _is4(flow_q) or not _nchw_ok(flow_q, input2, count, output):
+        return 1
     b, c, hq, wq = flow_q.shape
-    if c != 2 or not _nchw_ok(flow_q, input2, count, output):
-        return 1
     full = (b, 1, 4 * hq, 4 * wq)
-    if tuple(output.shape) != (b, 2, 4 * hq, 4 * wq) or tuple(count.shape) != full or tuple(input2.shape) != full:
+    if c != 2 or tuple(output.shape) != (b, 2, 4 * hq, 4 * wq) or tuple(count.shape) != full or tuple(input2.shape) != full:
         return 1
-    _dev(input2), _dev(count), _dev(output)
-    with torch.cuda.device(_dev(flow_q)):
+    with torch.cuda.device(_on_gpu(torch.float32, flow_q, input2, count, output)):
         return _finish(lib().vfi_depthflowprojection_forward_up4(
             _ptr(flow_q), _ptr(input2), _ptr(count), _ptr(output), b, hq, wq, mul0, mul1, int(fillhole), _st(flow_q),
             _st(input2), _st(count), _st(output), _stream(flow_q)))
@@ -987,15 +1068,13 @@ def _ptr_table(tensors):
 def flow_upsample4_backward(grads_full, mul0, mul1, grad_q):
     """grad_q = sum_i (mul0 * mul1[i]) U^T grads_full[i] (1..8 items of one shape and layout); grad_q is written."""
     n = len(grads_full)
-    if n == 0 or len(mul1) != n or not _nchw_ok(grad_q, *grads_full):
+    if n == 0 or len(mul1) != n or not _is4(grad_q) or not _nchw_ok(grad_q, *grads_full):
         return 1
     b, c, hq, wq = grad_q.shape
     g0 = grads_full[0]
     if tuple(g0.shape) != (b, c, 4 * hq, 4 * wq) or not _addressed_as(g0, *grads_full):
         return 1
-    for g in grads_full:
-        _dev(g)
-    with torch.cuda.device(_dev(grad_q)):
+    with torch.cuda.device(_on_gpu(torch.float32, grad_q, *grads_full)):
         return _finish(lib().vfi_flow_upsample4_backward(_ptr_table(grads_full), (_f * n)(*mul1), n, _ptr(grad_q), b, c, hq, wq,
                                                          mul0, _st(g0), _st(grad_q), _stream(grad_q)))
 
@@ -1004,7 +1083,7 @@ def flowprojection_backward_up4(flow_q, counts, gradoutputs, mul0, mul1, grad_q,
     """The backward of [depth]flowprojection_forward_up4 for the items (mul0, mul1[i]) of one flow_q.  depths (one tensor
     per item, or one shared by all) and outputs select the depth form; grad_depths: None, or one tensor or None per item."""
     n = len(counts)
-    if n == 0 or len(gradoutputs) != n or len(mul1) != n:
+    if n == 0 or len(gradoutputs) != n or len(mul1) != n or not _is4(flow_q):
         return 1
     b, c, hq, wq = flow_q.shape
     full = (b, 1, 4 * hq, 4 * wq)
@@ -1017,9 +1096,7 @@ def flowprojection_backward_up4(flow_q, counts, gradoutputs, mul0, mul1, grad_q,
         return 1
     mul = (_f * n)(*mul1)
     if depths is None:
-        for t in (grad_q, *counts, *gradoutputs):
-            _dev(t)
-        with torch.cuda.device(_dev(flow_q)):
+        with torch.cuda.device(_on_gpu(torch.float32, flow_q, grad_q, *counts, *gradoutputs)):
             return _finish(lib().vfi_flowprojection_backward_up4(
                 _ptr(flow_q), _ptr_table(counts), _ptr_table(gradoutputs), mul, n, _ptr(grad_q), b, hq, wq, mul0, _st(flow_q),
                 _st(c0), _st(g0), _st(grad_q), _stream(flow_q)))
@@ -1028,14 +1105,12 @@ def flowprojection_backward_up4(flow_q, counts, gradoutputs, mul0, mul1, grad_q,
     if outputs is None or len(depths) != n or len(outputs) != n or (grad_depths is not None and len(grad_depths) != n):
         return 1
     d0 = depths[0]
-    if tuple(d0.shape) != full or not _addressed_as(d0, *depths) or not _addressed_as(g0, *outputs):
+    if not _nchw_ok(d0) or tuple(d0.shape) != full or not _addressed_as(d0, *depths) or not _addressed_as(g0, *outputs):
         return 1
     wanted = [t for t in (grad_depths or []) if t is not None]
     if not _addressed_as(d0, *wanted):
         return 1
-    for t in (grad_q, *counts, *gradoutputs, *depths, *outputs, *wanted):
-        _dev(t)
-    with torch.cuda.device(_dev(flow_q)):
+    with torch.cuda.device(_on_gpu(torch.float32, flow_q, grad_q, *counts, *gradoutputs, *depths, *outputs, *wanted)):
         return _finish(lib().vfi_depthflowprojection_backward_up4(
             _ptr(flow_q), _ptr_table(depths), _ptr_table(counts), _ptr_table(outputs), _ptr_table(gradoutputs), mul, n,
             _ptr(grad_q), None if grad_depths is None else _ptr_table(grad_depths), b, hq, wq, mul0, _st(flow_q), _st(d0),
@@ -1064,13 +1139,11 @@ def filterinterp_blend_forward(ref0, ref2, flow0, flow2, filt0, filt2, blend, ou
     if dims is None or not (_same_strides(ref0, ref2) and _same_strides(flow0, flow2) and _same_strides(filt0, filt2)):
         return 1
     outs = [t for t in (out0, out2) if t is not None]
-    if blend.shape != ref0.shape or blend.stride(3) != 1 or not all(_same_strides(blend, t) for t in outs):
+    if not _nchw_ok(blend) or blend.shape != ref0.shape or not _addressed_as(blend, *outs):
         return 1
     b, c, h, w = dims
-    for t in (ref2, flow0, flow2, filt0, filt2, blend, *outs):
-        _dev(t)
     null = ctypes.c_void_p(0)
-    with torch.cuda.device(_dev(ref0)):
+    with torch.cuda.device(_on_gpu(torch.float32, ref0, ref2, flow0, flow2, filt0, filt2, blend, *outs)):
         return _finish(lib().vfi_filterinterp_blend_forward(
             _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), _ptr(blend),
             _ptr(out0) if out0 is not None else null, _ptr(out2) if out2 is not None else null, b, c, h, w,
@@ -1090,11 +1163,10 @@ def rectify_head_forward_bf16(ref0, ref2, flow0, flow2, filt0, filt2, head, blen
     if not _fi_filter_ok(ref0, filt0) or head.dim() != 4 or tuple(head.shape) != (b, 3 * c + 4 + 2 * filt0.size(1), h, w) or \
             head.stride(3) != 1 or (h != 1 and head.stride(2) != ref0.stride(2)):      # (a one-row tensor's row stride addresses nothing)
         return 1
-    if blend is not None and (blend.shape != ref0.shape or blend.stride(3) != 1):
+    if blend is not None and (blend.dim() != 4 or blend.shape != ref0.shape or blend.stride(3) != 1):
         return 1
-    for t in (ref0, ref2, flow0, flow2, filt0, filt2) + (() if blend is None else (blend,)):
-        _dev(t)
-    _dev(head, torch.bfloat16)
+    if _on_gpu(torch.float32, ref0, ref2, flow0, flow2, filt0, filt2, blend) != _dev(head, torch.bfloat16):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
     sh = _st(head)
     sh.h = ref0.stride(2)
     with torch.cuda.device(ref0.device):
@@ -1116,8 +1188,7 @@ def filterinterp_blend_backward(ref0, ref2, flow0, flow2, filt0, filt2, grad_ble
     if not _fi_filter_ok(ref0, filt0):
         return 1
     grads = [t for t in (grad_blend, grad_out0, grad_out2) if t is not None]
-    if grads and (grads[0].shape != ref0.shape or grads[0].stride(3) != 1 or
-                  not all(_same_strides(grads[0], t) for t in grads)):
+    if grads and (not _nchw_ok(grads[0]) or grads[0].shape != ref0.shape or not _addressed_as(grads[0], *grads)):
         return 1
     if not _addressed_as(ref0, *[t for t in (grad_ref0, grad_ref2) if t is not None]) or \
             not _addressed_as(flow0, *[t for t in (grad_flow0, grad_flow2) if t is not None]) or \
@@ -1125,11 +1196,9 @@ def filterinterp_blend_backward(ref0, ref2, flow0, flow2, filt0, filt2, grad_ble
         return 1
     b, c, h, w = dims
     outs = (grad_ref0, grad_ref2, grad_flow0, grad_flow2, grad_filt0, grad_filt2)
-    for t in (ref2, flow0, flow2, filt0, filt2, *grads, *[t for t in outs if t is not None]):
-        _dev(t)
     null = ctypes.c_void_p(0)
     opt = lambda t: _ptr(t) if t is not None else null      # noqa: E731
-    with torch.cuda.device(_dev(ref0)):
+    with torch.cuda.device(_on_gpu(torch.float32, ref0, ref2, flow0, flow2, filt0, filt2, *grads, *outs)):
         return _finish(lib().vfi_filterinterp_blend_backward(
             _ptr(ref0), _ptr(ref2), _ptr(flow0), _ptr(flow2), _ptr(filt0), _ptr(filt2), opt(grad_blend), opt(grad_out0),
             opt(grad_out2), *[opt(t) for t in outs], b, c, h, w, filt0.size(1), w0, w2, _st(ref0), _st(flow0), _st(filt0),
@@ -1145,12 +1214,14 @@ def _warp_flow_dtype(x, flow):
 
 def pwc_warp_forward(x, flow, output, align_corners=True):
     """float32, or bfloat16 x / output (vfi_pwc_warp_forward_bf16) with a float32 or a bfloat16 flow."""
-    b, c, h, w = x.shape
-    if not _nchw_ok(x, flow, output) or tuple(flow.shape) != (b, 2, h, w) or output.shape != x.shape:
+    if not _is4(x) or not _nchw_ok(x, flow, output) or tuple(flow.shape) != (x.size(0), 2, x.size(2), x.size(3)) or \
+            output.shape != x.shape:
         return 1
+    b, c, h, w = x.shape
     fdtype = _warp_flow_dtype(x, flow)
-    _dev(flow, fdtype)
     dtype, suffix = _bf16_or_f32(x, output)
+    if _dev(flow, fdtype) != x.device:
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
     with torch.cuda.device(x.device):
         if suffix:
             return _finish(lib().vfi_pwc_warp_forward_bf16(_ptr(x), _ptr(flow), int(fdtype == torch.bfloat16), _ptr(output), b, c, h, w,
@@ -1164,17 +1235,17 @@ def pwc_warp_backward(x, flow, grad_output, grad_x=None, grad_flow=None, align_c
     """grad_x and / or grad_flow (written) of pwc_warp_forward; None = not computed.  float32: grad_x is added into
     (zero-fill it).  bfloat16 x / grad_output / grad_x (vfi_pwc_warp_backward_bf16): grad_x is WRITTEN in full; the flow is
     float32 or bfloat16 and grad_flow has its dtype."""
-    b, c, h, w = x.shape
     grads = [t for t in (grad_x, grad_flow) if t is not None]
-    if not _nchw_ok(x, flow, grad_output, *grads) or tuple(flow.shape) != (b, 2, h, w) or grad_output.shape != x.shape:
+    if not _is4(x) or not _nchw_ok(x, flow, grad_output, *grads) or tuple(flow.shape) != (x.size(0), 2, x.size(2), x.size(3)) or \
+            grad_output.shape != x.shape:
         return 1
+    b, c, h, w = x.shape
     if (grad_x is not None and grad_x.shape != x.shape) or (grad_flow is not None and grad_flow.shape != flow.shape):
         return 1
     fdtype = _warp_flow_dtype(x, flow)
-    _dev(flow, fdtype)
-    if grad_flow is not None:
-        _dev(grad_flow, fdtype)
     dtype, suffix = _bf16_or_f32(x, grad_output, *([grad_x] if grad_x is not None else []))
+    if _on_gpu(fdtype, flow, grad_flow) != x.device:
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
     null = ctypes.c_void_p(0)
     with torch.cuda.device(x.device):
         tail = (_ptr(grad_output), _ptr(grad_x) if grad_x is not None else null,
@@ -1188,11 +1259,12 @@ def pwc_warp_backward(x, flow, grad_output, grad_x=None, grad_flow=None, align_c
 
 def pwc_warp_correlation_forward(input1, input2, flow, align_corners=True):
     """correlation(input1, warp(input2, flow)) of PWC-Net (pad 4, k 1, md 4, strides 1) in one launch; returns [B,81,h,w]."""
+    _corr_inputs("pwc_warp_correlation_forward", input1, input2)
     input1, input2 = input1.contiguous(), input2.contiguous()
     b, c, h, w = input1.shape
-    if tuple(input2.shape) != (b, c, h, w) or tuple(flow.shape) != (b, 2, h, w) or flow.stride(3) != 1:
+    if tuple(input2.shape) != (b, c, h, w) or not _shaped(flow, b, 2, h, w) or flow.stride(3) != 1:
         raise RuntimeError("pwc_warp_correlation_forward: shape mismatch")
-    _dev(input2), _dev(flow)
+    _on_gpu(torch.float32, input1, input2, flow)
     output = torch.empty((b, 81, h, w), dtype=torch.float32, device=input1.device)
     with torch.cuda.device(_dev(input1)):
         err = _finish(lib().vfi_pwc_warp_correlation_forward(_ptr(input1), _ptr(input2), _ptr(flow), _ptr(output), b, c, h, w,
@@ -1204,36 +1276,44 @@ def pwc_warp_correlation_forward(input1, input2, flow, align_corners=True):
 
 def frame_u8_to_planar(src_hwc, dst, pad_left, pad_right, pad_top, pad_bottom):
     """src_hwc: dense uint8 [B,h,w,3]; dst: float32 [B,3,h+pt+pb,w+pl+pr]."""
+    if not _is4(src_hwc) or not _nchw_ok(dst) or min(pad_left, pad_right, pad_top, pad_bottom) < 0:
+        return 1
     b, h, w, c = src_hwc.shape
-    if c != 3 or not src_hwc.is_contiguous() or dst.stride(3) != 1:
+    if c != 3 or not src_hwc.is_contiguous():
         return 1
     if tuple(dst.shape) != (b, 3, h + pad_top + pad_bottom, w + pad_left + pad_right):
         return 1
-    _dev(dst)
-    with torch.cuda.device(_dev(src_hwc, torch.uint8)):
+    if _dev(dst) != _dev(src_hwc, torch.uint8):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
+    with torch.cuda.device(src_hwc.device):
         return _finish(lib().vfi_frame_u8_to_planar(_ptr(src_hwc), _ptr(dst), b, h, w, pad_left, pad_right, pad_top,
                                                     pad_bottom, _st(dst), _stream(dst)))
 
 
 def planar_to_frame_u8(src, dst_hwc, top, left):
     """src: float32 [B,3,H,W]; dst_hwc: dense uint8 [B,h,w,3], the crop at (top, left)."""
+    if not _is4(dst_hwc, src):
+        return 1
     b, h, w, c = dst_hwc.shape
     if c != 3 or not dst_hwc.is_contiguous() or src.stride(3) != 1 or src.size(0) != b or src.size(1) != 3:
         return 1
     if top < 0 or left < 0 or top + h > src.size(2) or left + w > src.size(3):
         return 1
-    _dev(dst_hwc, torch.uint8)
-    with torch.cuda.device(_dev(src)):
+    if _dev(dst_hwc, torch.uint8) != _dev(src):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
+    with torch.cuda.device(src.device):
         return _finish(lib().vfi_planar_to_frame_u8(_ptr(src), _ptr(dst_hwc), b, h, w, top, left, _st(src),
                                                     _stream(src)))
 
 
 def frame_error_sums(a, b, sums):
     """a, b: dense uint8 tensors of one shape; sums: int64[2] on the GPU, zeroed by the caller."""
-    if a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous() or sums.numel() < 2:
+    if a.shape != b.shape or a.numel() == 0 or not a.is_contiguous() or not b.is_contiguous() or sums.numel() < 2 or \
+            not sums.is_contiguous():
         return 1
-    _dev(b, torch.uint8), _dev(sums, torch.int64)
-    with torch.cuda.device(_dev(a, torch.uint8)):
+    if _dev(sums, torch.int64) != _on_gpu(torch.uint8, a, b):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
+    with torch.cuda.device(a.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         return _finish(lib().vfi_frame_error_sums(_ptr(a), _ptr(b), a.numel(), _ptr(sums), stream))
 
@@ -1242,10 +1322,11 @@ def frame_ssim_sums(a, b, sums):
     """a, b: dense uint8 [B,h,w,3]; sums: int64[1] on the GPU, zeroed by the caller (2^-32 fixed point)."""
     if a.shape != b.shape or a.dim() != 4 or a.size(3) != 3 or not a.is_contiguous() or not b.is_contiguous():
         return 1
-    if sums.numel() < 1:
+    if sums.numel() < 1 or a.numel() == 0 or not sums.is_contiguous():
         return 1
-    _dev(b, torch.uint8), _dev(sums, torch.int64)
-    with torch.cuda.device(_dev(a, torch.uint8)):
+    if _dev(sums, torch.int64) != _on_gpu(torch.uint8, a, b):
+        raise RuntimeError("vfidkr_amd.cabi: tensors must live on one device")
+    with torch.cuda.device(a.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         return _finish(lib().vfi_frame_ssim_sums(_ptr(a), _ptr(b), a.size(0), a.size(1), a.size(2), _ptr(sums), stream))
 
@@ -1261,7 +1342,7 @@ def _part_loss_checks(diffs, target, flow0, flow1, img0, img1):
     if n == 0 or n > PART_LOSS_ITEMS or (flow0 is None) != (flow1 is None):
         return None
     d0 = diffs[0]
-    if not _nchw_ok(*diffs) or not _addressed_as(d0, *diffs) or (target is not None and not _addressed_as(d0, target)):
+    if not _nchw_ok(*diffs) or not _is4(d0) or not _addressed_as(d0, *diffs) or (target is not None and not _addressed_as(d0, target)):
         return None
     b, cd, h, w = d0.shape
     ci = 0
@@ -1277,9 +1358,7 @@ def _part_loss_checks(diffs, target, flow0, flow1, img0, img1):
 
 
 def _part_loss_on_device(*tensors):
-    for t in tensors:
-        if t is not None:
-            _dev(t)
+    _on_gpu(torch.float32, *tensors)
 
 
 def _opt(t):

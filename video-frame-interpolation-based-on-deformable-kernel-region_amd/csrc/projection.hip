@@ -1677,6 +1677,8 @@ extern "C" int vfi_flowprojection_forward_batch(const float* const* inputs1, flo
                                                  int batch, int h, int w, int fillhole, vfi_strides s1, vfi_strides sc,
                                                  vfi_stream_t stream) {
     if (nitems <= 0 || batch <= 0 || h <= 0 || w <= 0 || !inputs1 || !counts || !outputs) return VFI_ERR_SHAPE;
+    for (int i = 0; i < nitems; ++i)        // (a null item would reach the kernels as a pointer)
+        if (!inputs1[i] || !counts[i] || !outputs[i]) return VFI_ERR_SHAPE;
     return project_forward_items<false>(inputs1, s1, nullptr, counts, outputs, nitems, batch, h, w, fillhole, s1, s1, sc, (hipStream_t)stream);
 }
 
@@ -1684,6 +1686,8 @@ extern "C" int vfi_depthflowprojection_forward_batch(const float* const* inputs1
                                                       float* const* outputs, int nitems, int batch, int h, int w, int fillhole,
                                                       vfi_strides s1, vfi_strides s2, vfi_strides sc, vfi_stream_t stream) {
     if (nitems <= 0 || batch <= 0 || h <= 0 || w <= 0 || !inputs1 || !inputs2 || !counts || !outputs) return VFI_ERR_SHAPE;
+    for (int i = 0; i < nitems; ++i)
+        if (!inputs1[i] || !inputs2[i] || !counts[i] || !outputs[i]) return VFI_ERR_SHAPE;
     return project_forward_items<true>(inputs1, s1, inputs2, counts, outputs, nitems, batch, h, w, fillhole, s1, s2, sc, (hipStream_t)stream);
 }
 
