@@ -100,13 +100,26 @@ __global__ __launch_bounds__(256) void gradacc_zero_fp32_k(const int* __restrict
     }
 }
 
+// Zero-fills the scratch in 16-byte units.  A kernel, not hipMemsetAsync: captured into a HIP graph with a whole training
+// step, the memset nodes of the step's three gradacc calls held on the first replay and not on the second (the image
+// gradients of the blend backward and of the second warp backward came out scaled by a stale header); a kernel node is
+// ordered like the kernels around it.  The slot holds a multiple of 256 bytes (ws_get), so rounding up to 16 stays inside it.
+__global__ __launch_bounds__(256) void gradacc_clear(uint4* __restrict__ p, size_t n16) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 int gradacc_reserve(hipStream_t st, int ndirs, int64_t cells, int nflags, GradAccScratch* s) {
     *s = GradAccScratch{};
     const GradAccLayout l = gradacc_layout((size_t)ndirs, (size_t)cells, (size_t)nflags);
     if (!l.bytes) return VFI_OK;
-    char* p = static_cast<char*>(ws_get(st, WS_GRADACC, l.bytes, false, nullptr));
+    size_t capacity = 0;
+    char* p = static_cast<char*>(ws_get(st, WS_GRADACC, l.bytes, false, nullptr, &capacity));
     if (!p) return VFI_ERR_LAUNCH;
-    if (hipMemsetAsync(p, 0, l.bytes, st) != hipSuccess) return VFI_ERR_LAUNCH;
+    const size_t n16 = (l.bytes + 15) / 16;
+    if (n16 * 16 > capacity) return VFI_ERR_LAUNCH;
+    const size_t blocks = (n16 + 255) / 256;
+    hipLaunchKernelGGL(gradacc_clear, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, reinterpret_cast<uint4*>(p), n16);
+    if (launch_status() != VFI_OK) return VFI_ERR_LAUNCH;
     for (int d = 0; d < ndirs; ++d)
         s->dir[d] = GradAccDir{reinterpret_cast<unsigned long long*>(p + l.acc[d]), reinterpret_cast<int*>(p + l.hdr[d])};
     if (nflags) s->flags = reinterpret_cast<int*>(p + l.flags);

@@ -317,6 +317,10 @@ class _FilterInterpolate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_blend, g_out0, g_out2):
+        if g_blend is None and g_out0 is None and g_out2 is None:
+            # (autograd runs a node whose outputs all went unused, e.g. below a part_loss that used only its flow terms:
+            # no launch, and None instead of a tensor of zeros, as in _rectify_backward)
+            return (None,) * 8
         saved = ctx.saved_tensors
         g_blend, g_out0, g_out2 = _grad_layout([g_blend, g_out0, g_out2])
         outs = [torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) if need else None
@@ -365,7 +369,8 @@ class _FilterInterpolateCtx(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        filt, offsets = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        saved = ctx.saved_tensors                          # (read once: torch.utils.checkpoint refuses a second unpack)
+        filt, offsets = saved[0], saved[1:]
         none = (None,) * (2 + len(offsets))
         live = [i for i, g in enumerate(grads) if g is not None]
         if not live or not ctx.needs_input_grad[0]:
@@ -539,8 +544,9 @@ def _rectify_forward(ctx, bf16, ref0, ref2, filt0, filt2, ctx0, ctx2, time_offse
 def _rectify_backward(ctx, bf16, *grads):
     """bf16: the buffers' gradients are bfloat16 (the cur_output gradients float32).  The nine frame channels and the slices
     that passed through are widened (exactly) where they are used; the context channels are read in place, as bfloat16."""
-    ref0, ref2, filt0, filt2 = ctx.saved_tensors[:4]
-    offsets = ctx.saved_tensors[4:]
+    saved = ctx.saved_tensors                              # (read once: torch.utils.checkpoint refuses a second unpack)
+    ref0, ref2, filt0, filt2 = saved[:4]
+    offsets = saved[4:]
     n, m = len(ctx.time_offsets), ctx.map
     off = (offsets[:n], offsets[n:])
     g_buf, g_cur = grads[:n], grads[n:]
