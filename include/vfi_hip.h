@@ -144,7 +144,7 @@ int vfi_filterinterp_forward_ori_multi_to_bf16(const void* input1_bf16, const fl
  * The context warp for a network that keeps its activations in torch.channels_last (the layout 16-bit convolutions are
  * usually run in): vfi_filterinterp_forward_ori_multi_to[_bf16] on an image and destinations whose CHANNEL stride is 1,
  * without a .contiguous() copy of the image on the way in and a channels_last copy of every output on the way out.
- * Forward only.
+ * Forward only (the image gradient is vfi_filterinterp_backward_ori_nhwc_image_multi[_bf16], below).
  *   input1, outputs[t]   [batch, channel, h, w] with channel stride 1; batch, row and pixel strides in ELEMENTS in a
  *                        vfi_strides_nhwc.  input1 (s1) may be a dense channels_last tensor or a channel slice of a wider
  *                        one.  Every output has the layout s_out, which is its own: all three strides are free, so
@@ -191,6 +191,45 @@ int vfi_filterinterp_backward_ori_image_multi_bf16(const float* const* flows, co
                                                    int batch, int channel, int h, int w, int filter_channels,
                                                    vfi_strides s1, vfi_strides s2, vfi_strides s3, vfi_strides sg,
                                                    vfi_stream_t stream);
+
+/* ---- channels_last (NHWC) gradients: the backward of the channels_last context warp ----
+ * vfi_filterinterp_backward_ori_image_multi[_bf16] for gradients and a result whose CHANNEL stride is 1: gradinput1 = the
+ * sum over t < nflows of the image gradient of FilterInterpolation `_ori` for gradoutputs[t], without a .contiguous() copy of
+ * every incoming gradient and a channels_last copy of the result.
+ *   gradoutputs[t]       [batch, channel, h, w] with channel stride 1, all of layout sg.
+ *   gradinput1           the same shape with channel stride 1, layout s1.  Batch, row and pixel strides are free on both
+ *                        sides: a channel slice of a wider channels_last buffer is legal as a gradient and as the result.
+ *   flows[t], input3     float32, four element strides each (s2 for every flow, s3), NCHW or channels_last, as in the
+ *                        forward entries above.
+ * Values: every element of gradinput1 is, bit for bit, what vfi_filterinterp_backward_ori_image_multi writes for the same
+ * logical tensors (the _bf16 entry: bf16_rne of the float32 entry's result on the widened gradients).  The fixed-point sums do
+ * not depend on the order of the addends, every addend is formed as the NCHW kernels form it, and the scale is the NCHW
+ * call's: the largest |gradient| over all flows, the largest |filter tap|, a cell taking max(filter_channels, 4) x nflows
+ * taps of every pixel.  gradinput1 is WRITTEN, every element (+0 where no tap lands): it need not arrive zeroed.  An invalid
+ * pixel contributes nothing.  Reproducible bit for bit.  A call with a non-finite gradient or filter, or magnitudes whose
+ * product can overflow, scatters with fp32 atomics as the NCHW entries do: float32 into gradinput1, zeroed first; bfloat16
+ * as floats into the low words of the zeroed scratch cells, rounded once at the end -- no atomic touches bfloat16 storage.
+ * Kernels: filter_channels == 16 sums a tile's window slab by slab of 16 channels in LDS and flushes 128-byte runs of the
+ * [b][y][x][c] scratch; any other filter size, a call on the fp32 path or with tiny gradients (a second scale factor), and
+ * the tiles whose window does not fit, take the per-addend kernel: the same addends, the same bits.  The gradient loads are
+ * 16, 8 or 4 bytes wide or one element, the widest that divides the address of EVERY gradient and every stride of sg that the
+ * shape uses; no misaligned vector access is issued, and channel need not be a multiple of anything.
+ * Refusals, all VFI_ERR_SHAPE before any launch: a null pointer (a null entry of flows or gradoutputs included), nflows < 1,
+ * batch, channel, h, w or filter_channels < 1, batch > 65535, more than 2^28 tiles of 32 x 4 pixels (or tiles x launches of
+ * three flows past INT_MAX); and, for gradients or a result whose pixels are NOT contiguous (pixel stride != channel: a
+ * channel slice), batch x h x w > INT_MAX -- the conversion walks such a tensor pixel by pixel and counts them in an int
+ * (a dense channels_last tensor is walked row by row: w x channel <= INT_MAX there).  Scratch: 8 bytes per element of gradinput1 (the per-stream workspace); no other allocation, no
+ * synchronisation: legal inside a stream capture. */
+int vfi_filterinterp_backward_ori_nhwc_image_multi(const float* const* flows, const float* input3,
+                                                   const float* const* gradoutputs, float* gradinput1, int nflows,
+                                                   int batch, int channel, int h, int w, int filter_channels,
+                                                   vfi_strides_nhwc s1, vfi_strides4 s2, vfi_strides4 s3, vfi_strides_nhwc sg,
+                                                   vfi_stream_t stream);
+int vfi_filterinterp_backward_ori_nhwc_image_multi_bf16(const float* const* flows, const float* input3,
+                                                        const void* const* gradoutputs_bf16, void* gradinput1_bf16, int nflows,
+                                                        int batch, int channel, int h, int w, int filter_channels,
+                                                        vfi_strides_nhwc s1, vfi_strides4 s2, vfi_strides4 s3,
+                                                        vfi_strides_nhwc sg, vfi_stream_t stream);
 
 /* deformable-kernel variants (filterinterpolation_cuda.cc:11-92, 191-272, 374-447).
  * variant: 0 = FilterInterpolationLayer_gpu_forward (4 inputs, fs in {4,6}),

@@ -60,6 +60,10 @@ SIGNATURES = {
                                                         StridesNhwc, _p],
     "vfi_filterinterp_backward_ori_image_multi_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, Strides, Strides, Strides, Strides,
                                                        _p],
+    "vfi_filterinterp_backward_ori_nhwc_image_multi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4, Strides4,
+                                                       StridesNhwc, _p],
+    "vfi_filterinterp_backward_ori_nhwc_image_multi_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4,
+                                                            Strides4, StridesNhwc, _p],
     "vfi_filterinterp_forward_defor": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                        Strides, _p],
     "vfi_filterinterp_backward_defor": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides,
@@ -141,6 +145,12 @@ INTERNAL_SIGNATURES = {
                                                           _p],
     # (the access width, in elements, the NHWC entries choose for these layouts)
     "vfi_filterinterp_nhwc_access_width": [_i, _p, _p, _i, _i, _i, _i, _i, StridesNhwc, StridesNhwc],
+    # (the NHWC image gradient with every tile on the per-addend kernel, and the width of its staged kernel's gradient loads)
+    "vfi_filterinterp_backward_ori_nhwc_image_multi_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4,
+                                                              Strides4, StridesNhwc, _p],
+    "vfi_filterinterp_backward_ori_nhwc_image_multi_bf16_direct": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, StridesNhwc, Strides4,
+                                                                   Strides4, StridesNhwc, _p],
+    "vfi_filterinterp_nhwc_bwd_access_width": [_i, _p, _i, _i, _i, _i, _i, StridesNhwc],
     "vfi_filterinterp_forward_defor_general": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, Strides, Strides, Strides,
                                                Strides, _p],
     # (which kernel: 0 the MFMA kernel, 1 the generic kernel)

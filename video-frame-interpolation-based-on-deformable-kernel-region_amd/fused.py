@@ -27,7 +27,7 @@ import math
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import cabi
+from . import cabi, cabi_nhwc
 
 
 def _check(err, what):
@@ -397,8 +397,8 @@ def _channels_last_only(t):
 def _refuse_channels_last_grad(*images):
     for image in images:
         if _channels_last_only(image) and _wants_grad(image):
-            raise RuntimeError("FilterInterpolate_ctx: the channels_last warp is forward-only (there is no channels_last "
-                               "image gradient yet); a .contiguous() context tensor trains")
+            raise RuntimeError("FilterInterpolate_ctx: the channels_last warp is forward-only by default; a .contiguous() "
+                               "context tensor trains, and so does a channels_last one with train_channels_last=True")
 
 
 def _ctx_warp_nhwc_launch(ctx, offsets, filt):
@@ -408,23 +408,66 @@ def _ctx_warp_nhwc_launch(ctx, offsets, filt):
     return outs
 
 
-def _ctx_warp(image, offsets, filt):
+def _grad_layout_nhwc(grads):
+    """The incoming gradients as the NHWC image gradient reads them: channel stride 1 and one shared layout without zero
+    strides (an expanded gradient).  Gradients that are not all like that are each made dense channels_last."""
+    ref = grads[0]
+    if not cabi._channels_innermost(ref) or 0 in ref.stride() or not all(cabi._same_strides(ref, g) for g in grads):
+        return [g.contiguous(memory_format=torch.channels_last) for g in grads]
+    return grads
+
+
+class _FilterInterpolateCtxNhwc(torch.autograd.Function):
+    """`_FilterInterpolateCtx` for a channels_last context tensor: the forward is the NHWC launch, the backward ONE
+    vfi_filterinterp_backward_ori_nhwc_image_multi[_bf16] call over the outputs that received a gradient, on the gradients
+    where they are.  Only the flows and the filter are saved; they get no gradient.  The context gradient is a dense
+    channels_last tensor of the context's dtype (not laid out with a slice's strides), written in full."""
+
+    @staticmethod
+    def forward(ctx, image, filt, *offsets):
+        outs = _ctx_warp_nhwc_launch(image, offsets, filt)
+        ctx.save_for_backward(filt, *offsets)
+        ctx.image_layout = (image.shape, image.dtype)
+        ctx.set_materialize_grads(False)                   # (an unused time offset is an absent flow, not a tensor of zeros)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors                          # (read once: torch.utils.checkpoint refuses a second unpack)
+        filt, offsets = saved[0], saved[1:]
+        none = (None,) * (2 + len(offsets))
+        live = [i for i, g in enumerate(grads) if g is not None]
+        if not live or not ctx.needs_input_grad[0]:
+            return none
+        gs = _grad_layout_nhwc([grads[i] for i in live])
+        shape, dtype = ctx.image_layout
+        gimg = torch.empty(shape, dtype=dtype, device=gs[0].device, memory_format=torch.channels_last)      # (written in full)
+        _check(cabi_nhwc.filterinterp_backward_nhwc_image_multi([offsets[i] for i in live], filt, gs, gimg),
+               "filterinterp_backward_nhwc_image_multi")
+        return (gimg,) + none[1:]
+
+
+def _ctx_warp(image, offsets, filt, train_channels_last=False):
     """one direction: the Function when the context tensor can train, today's plain launch otherwise.  With a bfloat16
     context tensor a bfloat16 flow or filter is widened here, once per direction; float32 calls pass through untouched.
-    A channels_last context tensor (stride(3) != 1, stride(1) == 1) is warped in place by the NHWC entry, forward only: one
-    that requires grad in grad mode raises before any launch."""
+    A channels_last context tensor (stride(3) != 1, stride(1) == 1) is warped in place by the NHWC entry: one that requires
+    grad in grad mode raises before any launch, or, with train_channels_last, takes the NHWC Function."""
     nhwc = _channels_last_only(image)
-    _refuse_channels_last_grad(image)
+    if not train_channels_last:
+        _refuse_channels_last_grad(image)
     if image.dtype == torch.bfloat16:
         offsets, filt = [_f32_once(o) for o in offsets], _f32_once(filt)
     if nhwc:
+        if train_channels_last and _wants_grad(image):
+            return list(_FilterInterpolateCtxNhwc.apply(image, filt, *offsets))
         return _ctx_warp_nhwc_launch(image, offsets, filt)
     if _wants_grad(image):
         return list(_FilterInterpolateCtx.apply(image, filt, *offsets))
     return _ctx_warp_launch(image, offsets, filt)
 
 
-def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
+def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter, train_channels_last=False):
     """`DAIN_slowmotion.FilterInterpolate_ctx` (networks/DAIN_slowmotion.py:311-317) for every time offset of a step at
     once (the loop at :167-183 calls it once per t with the same context tensors and filters): offsets[d][t] is the
     projected flow of direction d at time offset t.  Returns [(ctx0_offset_t, ctx2_offset_t) for t], each pair what
@@ -444,20 +487,29 @@ def FilterInterpolate_ctx_all(ctx0, ctx2, offsets, filter):
     have the input's strides and hold, bit for bit, the NCHW call's `.contiguous(memory_format=torch.channels_last)`; flows
     and filter may be in either layout.  "The input's strides" includes a slice's: the outputs of `wide[:, 45:241]` of a
     437-channel tensor each span the wide tensor's footprint (437 / 196 of the dense size) -- pass a dense context, or call
-    `cabi.filterinterp_forward_nhwc_multi_to` with destinations of your own, where that matters.  The path is forward-only:
-    if either context is such a tensor and requires grad in grad mode, the call raises a RuntimeError before any launch of
-    either direction (`.contiguous()` trains).  Every tensor with `stride(3) == 1` goes where it always went."""
-    _refuse_channels_last_grad(ctx0, ctx2)                  # (both directions, before the first launch)
-    out0 = _ctx_warp(ctx0, list(offsets[0]), filter[0])
-    out2 = _ctx_warp(ctx2, list(offsets[1]), filter[1])
+    `cabi.filterinterp_forward_nhwc_multi_to` with destinations of your own, where that matters.  By default the path is
+    forward-only: if either context is such a tensor and requires grad in grad mode, the call raises a RuntimeError before any
+    launch of either direction (`.contiguous()` trains).  Every tensor with `stride(3) == 1` goes where it always went.
+    train_channels_last=True: such a context trains where it is.  In grad mode a channels_last context that requires grad
+    takes the NHWC forward launch and, in the backward, ONE vfi_filterinterp_backward_ori_nhwc_image_multi[_bf16] call over
+    the outputs the loss used: its gradient is, bit for bit, what the NCHW Function returns for the `.contiguous()` context,
+    as a dense channels_last tensor of the context's dtype (also for a channel-slice context).  Incoming gradients are read
+    where they are when they all have channel stride 1 and one layout without zero strides; otherwise each is made
+    `.contiguous(memory_format=torch.channels_last)` first.  Everything else goes where it goes without the keyword: NCHW
+    contexts, channels_last contexts that need no gradient, `[B, 1, H, W]` contexts, `no_grad` calls; the two directions may
+    differ in layout."""
+    if not train_channels_last:
+        _refuse_channels_last_grad(ctx0, ctx2)              # (both directions, before the first launch)
+    out0 = _ctx_warp(ctx0, list(offsets[0]), filter[0], train_channels_last)
+    out2 = _ctx_warp(ctx2, list(offsets[1]), filter[1], train_channels_last)
     return list(zip(out0, out2))
 
 
-def FilterInterpolate_ctx(ctx0, ctx2, offset, filter):
+def FilterInterpolate_ctx(ctx0, ctx2, offset, filter, train_channels_last=False):
     """`DAIN.FilterInterpolate_ctx` (networks/DAIN.py:544-552): (ctx0_offset, ctx2_offset) for one time offset,
     offset = [flow of direction 0, flow of direction 1].  Differentiable exactly as `FilterInterpolate_ctx_all` is:
-    towards the context tensors only."""
-    return FilterInterpolate_ctx_all(ctx0, ctx2, [[offset[0]], [offset[1]]], filter)[0]
+    towards the context tensors only; `train_channels_last` as there."""
+    return FilterInterpolate_ctx_all(ctx0, ctx2, [[offset[0]], [offset[1]]], filter, train_channels_last)[0]
 
 
 # ---------------------------------------------------------------- the rectify network's input, written in place
